@@ -8,9 +8,14 @@ all-reduce of the partial words), finalisation and the 8-byte answer copied to t
 N > 1 shards the SF100 rows by contiguous row range, one process per GPU (strong scaling,
 as BASELINE.json config "Q6 SF100 row-range sharded across 8xMI355X").
 
-Prints ONE JSON line (rank 0).  `value` = rows/s over all GPUs; kernel time = mean fused-scan
-time from HIP events on the launch stream, recorded by libvdl around the kernel inside the
-timed region.  `roofline.achieved` / `frac` are on the bytes the kernel MOVED
+Prints ONE JSON line (rank 0).  `value` = rows/s over all GPUs, `ms_per_step` = wall time of one
+timed step.  A plain run does only that: set up, warm up, time --steps steps, write the last
+step's outputs if --dump-outputs DIR is given, print the line.  Everything else runs with --full
+only: the bit-exact check against the CPU SQL loop, the CPU baseline, per-query latency, the
+roofline and the secondary measurements under "also".
+
+--full: kernel time = mean fused-scan time from HIP events on the launch stream, recorded by
+libvdl around the kernel inside the timed region.  `roofline.achieved` / `frac` are on the bytes the kernel MOVED
 (vdl_plan_scan_traffic: counted, never above the peak); the 28 B/row figure of SURVEY.md 8(d) is `algorithmic_equivalent_GBps`,
 and `read_everything_kernel` is the kernel that moves exactly those bytes, timed in the same run.
 """
@@ -123,9 +128,48 @@ def q3_checksums_of_result(plan_result, dev):
     return [int(len(okey)), int(rev.sum()), int(okey.sum()), int(date.sum()), int((okey * rev).sum())]
 
 
-def q3_measure(eng, dev, n_orders, li_range, world, steps, warmup, jit, dist=None, sharded=False):
+DUMP_LIMIT_BYTES = 64000000 - 65536          # 64 MB in all, npy headers included
+
+
+def host_array(values):
+    """one result column of a reply (list, numpy array or DeviceValues left in HBM) as a numpy int64 array"""
+    import numpy as np
+    if hasattr(values, "__cuda_array_interface__"):
+        import torch
+        return torch.as_tensor(values, device="cuda").cpu().numpy()
+    return np.asarray(values, dtype=np.int64).reshape(-1)
+
+
+def dump_outputs(directory, columns):
+    """--dump-outputs: the result columns of the last timed step as DIR/<name>.npy in float64.  Columns of equal length are
+    rows of one table; beyond DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows is kept from each of them."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    total = sum(len(v) for v in columns.values()) * 8
+    rng = np.random.default_rng(20240601)
+    picks = {}
+    for name, values in columns.items():
+        n = len(values)
+        if total > DUMP_LIMIT_BYTES:
+            if n not in picks:
+                keep = max(1, n * DUMP_LIMIT_BYTES // total)
+                picks[n] = np.sort(rng.choice(n, size=keep, replace=False)) if keep < n else None
+            if picks[n] is not None:
+                values = values[picks[n]]
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(values, dtype=np.float64))
+
+
+def reply_columns(results):
+    """{field name: int64 array} of a reply {tmpN: {".name": values}}"""
+    return {list(v.keys())[0][1:]: host_array(list(v.values())[0]) for v in results.values()}
+
+
+def q3_measure(eng, dev, n_orders, li_range, world, steps, warmup, jit, dist=None, sharded=False, full=True, dump=False):
     """Q3 over the columns register_q3_columns builds in place: `steps` executions with the four result columns left in HBM
-    (vdl_plan_set_device_outputs), wall time per query; then the same with the results copied to the host (N = 1 only).
+    (vdl_plan_set_device_outputs), wall time per query.  full: the result checked against a torch evaluation of the SQL,
+    then the same query with the results copied to the host (N = 1 only).  dump: the four result columns of the last timed
+    step copied to the host as `outputs`.
     sharded: vdl_run_sharded -- local phase on this rank's lineitem rows (orders co-partitioned), ONE count all-gather, ONE grouped
     send/receive of the surviving rows by key range over RCCL, tail on the received rows."""
     import torch
@@ -155,6 +199,10 @@ def q3_measure(eng, dev, n_orders, li_range, world, steps, warmup, jit, dist=Non
     sync()
     elapsed = time.perf_counter() - t0
     res = plan.collect()["results"]
+    out = {"plan": plan, "keep": keep, "elapsed": elapsed, "note": plan.jit_note(),
+           "outputs": [host_array(x) for x in q3_outputs(res)] if dump else None}       # (copied now: the next run reuses the buffers)
+    if not full:
+        return out
     got = q3_checksums_of_result(res, dev)
     want = q3_checksums_torch(eng, dev)
     host_ms = None
@@ -164,7 +212,8 @@ def q3_measure(eng, dev, n_orders, li_range, world, steps, warmup, jit, dist=Non
         for _ in range(5):
             torch.cuda.synchronize(); t1 = time.perf_counter(); plan.execute(); torch.cuda.synchronize(); wall.append(time.perf_counter() - t1)
         host_ms = 1e3 * sum(wall[2:]) / len(wall[2:])
-    return {"plan": plan, "keep": keep, "elapsed": elapsed, "got": got, "want": want, "host_ms": host_ms, "note": plan.jit_note()}
+    out.update(got=got, want=want, host_ms=host_ms)
+    return out
 
 
 def secondary_measurements(eng, rows, jit="tune"):
@@ -334,6 +383,7 @@ def main_q3(args):
     sharded by rows, orders co-partitioned, customer replicated; the surviving rows travel by key range in ONE grouped RCCL
     send/receive inside libvdl (vdl_run_sharded) -- the all-to-all of the north star -- and every rank ends with the groups of its
     key range.  value = lineitem rows per second over all GPUs with the four result columns left in HBM."""
+    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -380,15 +430,29 @@ def main_q3(args):
             sys.exit(2)
         transport = {"rccl": "RCCL inside libvdl: one count all-gather + ONE ncclGroupStart..End of sends/receives (rows by key range) per query",
                      "host": "libvdl host transport over gloo (REHEARSAL)"}[name]
-    r = q3_measure(eng, dev, n_orders, (lo, hi), world, args.steps, args.warmup, args.jit, dist if world > 1 else None, sharded=world > 1)
+    r = q3_measure(eng, dev, n_orders, (lo, hi), world, args.steps, args.warmup, args.jit, dist if world > 1 else None, sharded=world > 1,
+                   full=args.full, dump=bool(args.dump_outputs))
     elapsed = r["elapsed"]
-    sums = torch.tensor([r["got"], r["want"]], dtype=torch.int64)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        dist.all_reduce(sums, op=dist.ReduceOp.SUM)
-    verified = bool((sums[0] == sums[1]).all())
+    if args.dump_outputs:
+        # every rank holds the groups of its key range; the query carries no ORDER BY, so the rows are written by order key
+        cols = dict(zip(("l_orderkey", "revenue", "o_orderdate", "o_shippriority"), r["outputs"]))
+        if world > 1:
+            box = [None] * world
+            dist.all_gather_object(box, cols)
+            cols = {k: np.concatenate([b[k] for b in box]) for k in cols}
+        if rank == 0:
+            order = np.argsort(cols["l_orderkey"], kind="stable")
+            dump_outputs(args.dump_outputs, {k: v[order] for k, v in cols.items()})
+    verified = None
+    if args.full:
+        sums = torch.tensor([r["got"], r["want"]], dtype=torch.int64)
+        if world > 1:
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM)
+        verified = bool((sums[0] == sums[1]).all())
     if rank == 0:
         out = {"metric": "lineitem rows/s, TPC-H Q3 %s (join-index gathers + sparse GROUP BY; N > 1: RCCL all-to-all Partition)" % (args.sf.upper() if not args.rows else "%d lineitems" % n_li),
                "value": n_li / (elapsed / args.steps), "unit": "rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -398,16 +462,17 @@ def main_q3(args):
                           "exchange": transport, "results": "left in HBM (4 columns)"},
                "roofline": None,                  # random access through join indices: rows/s only
                "cpu_baseline": None,
-               "result_rows_all_ranks": int(sums[0][0]), "ms_per_query_results_copied_to_host": r["host_ms"],
-               "verified_vs_torch_sql_checksums": verified,
-               "checksums": {"groups, sum(revenue), sum(orderkey), sum(orderdate), sum(orderkey*revenue) mod 2^64": [int(x) for x in sums[0]]},
                "scan_kernels": r["note"]}
+        if args.full:
+            out.update({"result_rows_all_ranks": int(sums[0][0]), "ms_per_query_results_copied_to_host": r["host_ms"],
+                        "verified_vs_torch_sql_checksums": verified,
+                        "checksums": {"groups, sum(revenue), sum(orderkey), sum(orderdate), sum(orderkey*revenue) mod 2^64": [int(x) for x in sums[0]]}})
         print(json.dumps(out))
     eng.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if not verified:
+    if verified is False:
         print("VERIFICATION FAILED (q3): engine %s vs torch %s" % (sums[0].tolist(), sums[1].tolist()), file=sys.stderr)
         sys.exit(1)
 
@@ -431,6 +496,11 @@ def main():
                          "precompiled variant's rows per lane, tune (default) = rows per lane chosen by timing at that run, the precompiled kernel staying if it wins")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: check launcher / sharding / merge plumbing only (see dry_run)")
     ap.add_argument("--latency-steps", type=int, default=10, help="queries run one at a time after the timed region to report per-query latency")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: verification against the CPU, CPU baseline, per-query latency, roofline and the secondary "
+                         "measurements (the --no-* switches and --latency-steps act within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the result columns of the last timed step as DIR/<name>.npy (float64; a fixed sample beyond 64 MB)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -504,7 +574,8 @@ def main():
     plan = eng.parse(text)
     if not plan.is_fused:
         raise SystemExit("%s did not fuse:\n%s" % (args.query, plan.describe()))
-    plan.set_profiling(True)
+    if args.full:
+        plan.set_profiling(True)                  # (kernel time for the roofline: HIP events around the scan)
     plan.set_row_offset(lo)
     if args.jit != "off":
         plan.set_jit(True, tune=args.jit == "tune")
@@ -567,7 +638,7 @@ def main():
         """k full queries, pipelined: the host side of query i (and, N > 1, its collective) overlaps the scan of query
         i+1; every query runs completely and every result is produced."""
         def on_result(out):
-            if record:
+            if record and args.full:
                 scan_us.append(plan.scan_stats()[2])
         if query is not None:
             return query.run_pipelined(k, bufs, on_result, overlap_merge=os.environ.get("VDL_BENCH_SYNC_MERGE") != "1")
@@ -607,10 +678,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, reply_columns(result["results"]))
+
     # per-query latency: the same query run one at a time (local phase, merge, finalisation, answer on the host before
     # the next one starts) -- `value` above is pipelined throughput, this is what a single request waits for
     latency_ms = None
-    if args.latency_steps > 0:
+    if args.full and args.latency_steps > 0:
         lat = []
         for _ in range(args.latency_steps):
             sync_all()
@@ -624,13 +698,27 @@ def main():
         latency_ms = float(lt.item()) * 1e3
 
     revenue = result["results"]["tmp42"][".revenue"] if args.query == "q6" else None
-    kernel_label = next((k.replace("timeInMicrosecondsForFusedScan_", "") for k in result["timings"] if "FusedScan" in k), "k_scan")
     ms_per_step = elapsed / args.steps * 1e3
     rows_per_s = total_rows / (elapsed / args.steps)
-    kern_us = sum(scan_us) / len(scan_us)
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "rows/s, TPC-H %s %s (fused VDL scan), + achieved HBM GB/s in roofline" % (args.query.upper(), args.sf.upper() if not args.rows else "%d rows" % total_rows),
+            "value": rows_per_s, "unit": "rows/s", "n_gpus": n_ranks, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "latency_ms_per_query": latency_ms, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "int64", "data": "synthetic",
+            "config": {"workload": "tpch_%s_%s" % (args.query, args.sf if not args.rows else "rows%d" % args.rows),
+                       "rows_total": total_rows, "rows_per_gpu": my_rows, "bytes_per_row": q_bytes,
+                       "sharding": "row-range, one process per GPU" if world > 1 else "single GPU",
+                       "finalise": transport if world > 1 else "local"},
+            "roofline": None, "cpu_baseline": None,             # (--full)
+            "revenue": (revenue[0] if revenue else None), "verified_bit_exact_vs_cpu": None,
+            "scan_kernels": {"mode": args.jit, "note": plan.jit_note()},
+        }
+    if rank == 0 and args.full:
+        kernel_label = next((k.replace("timeInMicrosecondsForFusedScan_", "") for k in result["timings"] if "FusedScan" in k), "k_scan")
+        kern_us = sum(scan_us) / len(scan_us)
         verified = None
         cpu_baseline = None
         if not args.no_verify or not args.no_cpu_baseline:
@@ -678,7 +766,6 @@ def main():
         # rows per lane, stages, grid) over the same number of rows (tools/profile_bench.sh -> profiles/traffic.json).
         moved, moved_detail = plan.scan_traffic()
         achieved = moved / (kern_us * 1e-6) / 1e9 if kern_us > 0 else 0.0
-        tuner_note = plan.jit_note()                  # (before the read-everything run below switches the specialisation off)
         traffic, traffic_source = None, None
         tpath = os.path.join(ROOT, "profiles", "traffic.json")
         if os.path.exists(tpath):
@@ -705,15 +792,7 @@ def main():
                                    "achieved": my_rows * q_bytes / (k_us * 1e-6) / 1e9, "frac": my_rows * q_bytes / (k_us * 1e-6) / 1e9 / HBM_PEAK_GBPS}
             except Exception as exc:              # noqa: BLE001
                 read_everything = {"error": "%s: %s" % (type(exc).__name__, exc)}
-        out = {
-            "metric": "rows/s, TPC-H %s %s (fused VDL scan), + achieved HBM GB/s in roofline" % (args.query.upper(), args.sf.upper() if not args.rows else "%d rows" % total_rows),
-            "value": rows_per_s, "unit": "rows/s", "n_gpus": n_ranks, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "latency_ms_per_query": latency_ms, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "int64", "data": "synthetic",
-            "config": {"workload": "tpch_%s_%s" % (args.query, args.sf if not args.rows else "rows%d" % args.rows),
-                       "rows_total": total_rows, "rows_per_gpu": my_rows, "bytes_per_row": q_bytes,
-                       "sharding": "row-range, one process per GPU" if world > 1 else "single GPU",
-                       "finalise": transport if world > 1 else "local"},
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBPS,
                          # (the guide that names the 8 TB/s peak also measures what a plain copy reaches on this part: the practical ceiling)
@@ -739,9 +818,8 @@ def main():
                          "late_materialisation": moved < my_rows * q_bytes,
                          "read_everything_kernel": read_everything},
             "cpu_baseline": cpu_baseline,
-            "revenue": (revenue[0] if revenue else None), "verified_bit_exact_vs_cpu": verified,
-            "scan_kernels": {"mode": args.jit, "note": tuner_note},
-        }
+            "verified_bit_exact_vs_cpu": verified,
+        })
         if world == 1 and args.query == "q6" and not args.no_secondary:
             out["also"] = secondary_measurements(eng, total_rows, args.jit)
     eng.close()

@@ -63,7 +63,7 @@ def bench(args, timeout=900):
 def test_bench_q6_shards_over_rccl_and_verifies(world):
     """`bench.py --gpus N --rows 2e8`: row-range shards, the collective inside libvdl on its own RCCL communicator of exactly N
     ranks (anything else exits non-zero), revenue bit-exact against the SQL loop over the regenerated rows."""
-    out = bench(["--gpus", str(world), "--rows", "200000000", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"])
+    out = bench(["--full", "--gpus", str(world), "--rows", "200000000", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"])
     assert out["n_gpus"] == world and out["verified_bit_exact_vs_cpu"] is True
     assert "RCCL inside libvdl" in out["config"]["finalise"], out["config"]
     assert out["roofline"]["frac"] <= 1.0
@@ -71,6 +71,6 @@ def test_bench_q6_shards_over_rccl_and_verifies(world):
 
 @pytest.mark.parametrize("world", WORLDS)
 def test_bench_q3_exchanges_over_rccl_and_verifies(world):
-    out = bench(["--gpus", str(world), "--query", "q3", "--rows", "80000000", "--steps", "5", "--warmup", "2"])
+    out = bench(["--full", "--gpus", str(world), "--query", "q3", "--rows", "80000000", "--steps", "5", "--warmup", "2"])
     assert out["n_gpus"] == world and out["verified_vs_torch_sql_checksums"] is True
     assert "RCCL inside libvdl" in out["config"]["exchange"], out["config"]

@@ -76,7 +76,7 @@ def scan_rows(pmc_csv, stats_names):
 
 
 traffic = {}
-fast = ["--no-cpu-baseline", "--no-secondary"]
+fast = ["--full", "--no-cpu-baseline", "--no-secondary"]
 for query in ("q6", "q1"):
     q = ["--query", query] if query != "q6" else []
     plain = os.path.join(OUT, query + "_plain.json")
@@ -137,7 +137,7 @@ json.dump(traffic, open(os.path.join(OUT, "traffic.json"), "w"), indent=1)
 # the plain command under the kernel trace (default --jit tune, secondary measurements included): the tuner's candidates show up
 # as kernels of their own, the winner's average is the one bench.py reports
 sh(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", os.path.join(OUT, "default"), "--", "python3", BENCH, "--steps", "20", "--warmup", "3",
-    "--no-cpu-baseline"], os.path.join(OUT, "default_bench.json"))
+    "--full", "--no-cpu-baseline"], os.path.join(OUT, "default_bench.json"))
 os.replace(next(f for f in one("default") if f.endswith("kernel_stats.csv")), os.path.join(OUT, "default_kernel_stats.csv"))
 
 # the calibration the x2 rests on

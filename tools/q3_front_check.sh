@@ -3,8 +3,8 @@
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/${1:-q3}; mkdir -p $OUT
 cd $ROOT
-python3 bench.py --query q3 --sf sf10 --steps 20 --warmup 3 > $OUT/q3_sf10.json 2> $OUT/q3_sf10.err || tail -n 5 $OUT/q3_sf10.err
-python3 bench.py --query q3 --sf sf100 --steps 10 --warmup 3 > $OUT/q3_sf100.json 2> $OUT/q3_sf100.err || tail -n 5 $OUT/q3_sf100.err
+python3 bench.py --full --query q3 --sf sf10 --steps 20 --warmup 3 > $OUT/q3_sf10.json 2> $OUT/q3_sf10.err || tail -n 5 $OUT/q3_sf10.err
+python3 bench.py --full --query q3 --sf sf100 --steps 10 --warmup 3 > $OUT/q3_sf100.json 2> $OUT/q3_sf100.err || tail -n 5 $OUT/q3_sf100.err
 python3 - $OUT <<'PY'
 import json, sys
 for sf in ("sf10", "sf100"):
