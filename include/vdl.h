@@ -94,6 +94,22 @@ int  vdl_column_info(const vdl_ctx *ctx, const char *name, int *elem_bytes, int6
 /* Copy a catalog column back to the host (tests, debugging). */
 int  vdl_download_column(vdl_ctx *ctx, const char *name, void *host_ptr, size_t bytes);
 
+/* ---- column images ----------------------------------------------------------------
+ * A column whose values span few significant digits is kept a second time, narrow: its frame-of-reference image,
+ * v = base + scale * e with e in 1, 2 or 4 bytes (scale a power of ten all differences share).  Fused aggregate scans
+ * read the image instead of the column where every use of the column in that scan allows it (range filters, formula
+ * tests and aggregate factors are rewritten into the encoded domain; a pure narrowing, base 0 and scale 1, may stand
+ * in for any use), with the same results.  The catalog column itself stays as it is: vdl_column_info and
+ * vdl_download_column see it, never the image.  vdl_generate_column builds the image; uploaded and registered
+ * columns have none until vdl_encode_column is called (for a registered column the caller promises not to write
+ * it afterwards: the image would go stale).  The image goes with its column (drop, re-registration).
+ * No image is built when it would not be narrower than the column. */
+int  vdl_encode_column(vdl_ctx *ctx, const char *name);
+/* width 0: the column has no image; otherwise its width in bytes and v = base + scale * e */
+int  vdl_column_image_info(const vdl_ctx *ctx, const char *name, int *width, int64_t *base, int64_t *scale);
+/* on = 0: scans bind the catalog columns and ignore the images (tests, A/B comparisons in one process); default 1 */
+int  vdl_set_column_images(vdl_ctx *ctx, int on);
+
 /* ---- plans --------------------------------------------------------------------- */
 
 /* Parse the VDL text, check it, and build the execution plan (operator fusion included).

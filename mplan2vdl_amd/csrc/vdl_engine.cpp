@@ -111,6 +111,19 @@ static bool rowid_counts_from_the_table(const std::vector<ScanColumn> &sc) {
     return any && !as_index;
 }
 
+// Columns of an aggregate scan that must be read with their stored values, so that only a pure narrowing may stand in for them
+// (vdl_column_image.h): sources of derived columns other than formula tests, loads of the group key, the column of a FIRST aggregate
+static uint32_t raw_value_uses(const std::vector<ScanColumn> &sc, const std::vector<ScanAgg> &aggs, const std::vector<KeyStep> *key) {
+    uint32_t m = 0;
+    for (const ScanColumn &c : sc)
+        if (c.kind != VC_DIRECT && c.kind != VC_FORM) for (int src : {c.idx, c.idx2}) if (src >= 0 && src < 32) m |= 1u << src;
+    if (key) for (const KeyStep &k : *key) if (k.kind == KeyStep::LOAD && k.col >= 0 && k.col < 32) m |= 1u << k.col;
+    for (const ScanAgg &ag : aggs) if (ag.kind == AGG_FIRST) for (const ScanFactor &f : ag.fac) if (f.col >= 0 && f.col < 32) m |= 1u << f.col;
+    return m;
+}
+static const std::vector<KeyStep> *key_of(const ScanPlan &) { return nullptr; }
+static const std::vector<KeyStep> *key_of(const GroupScanPlan &gp) { return &gp.key; }
+
 template <typename PlanT>
 int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0) {
     cols = MScanCols{};
@@ -119,12 +132,13 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
     d.nagg = (int)sp.aggs.size();
     int64_t n = -1;
     *bytes_per_row = 0;
+    const uint32_t raw = raw_value_uses(sp.cols, sp.aggs, key_of(sp));
+    img::Image ims[kMaxVCols];
     for (int k = 0; k < cols.ncol; k++) {
         const ScanColumn &sc = sp.cols[(size_t)k];
         cols.kind[k] = sc.kind;
         cols.lo[k] = sc.lo; cols.hi[k] = sc.hi;
         cols.filtered[k] = (cols.lo[k] != INT64_MIN || cols.hi[k] != INT64_MAX) ? 1 : 0;
-        d.flo[k] = cols.lo[k]; d.fhi[k] = cols.hi[k];
         d.dkind[k] = sc.kind; d.dsrc[k] = sc.idx; d.dsrc2[k] = sc.idx2;
         if (sc.kind == VC_DIRECT) {
             const Column &col = find_col(c, sc.name);
@@ -132,7 +146,14 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
                 throw Error(VDL_ERR_SHAPE, "columns of table '" + sp.table + "' have different lengths in the catalog");
             n = col.n;
             cols.ptr[k] = col.dev; cols.width[k] = col.width;
-            *bytes_per_row += col.width;
+            if (c->images && col.image_buf && img::usable(col.image, (raw >> k) & 1u)) {
+                // the image instead of the column: its bounds in the encoded domain (the filtered bit stays what the plan says)
+                ims[k] = col.image;
+                cols.image |= 1u << k;
+                cols.ptr[k] = col.image_buf->p; cols.width[k] = col.image.width;
+                img::map_range(col.image, sc.lo, sc.hi, &cols.lo[k], &cols.hi[k]);
+            }
+            *bytes_per_row += cols.width[k];
         } else if (sc.kind == VC_GATHER || sc.kind == VC_INRANGE) {      // a column of another table, looked up / its length
             const Column &col = find_col(c, sc.name);
             cols.ptr[k] = col.dev; cols.width[k] = col.width;
@@ -142,7 +163,12 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
             d.dn[k] = 0;
         }
     }
+    for (int k = 0; k < cols.ncol; k++) { d.flo[k] = cols.lo[k]; d.fhi[k] = cols.hi[k]; }
     bind_forms(sp.cols, d);
+    for (int k = 0; k < cols.ncol; k++)                               // a formula's tests of a column read from its image
+        if (cols.kind[k] == VC_FORM)
+            for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dtests[k]; f++)
+                if (d.form[f].col >= 0 && ((cols.image >> d.form[f].col) & 1u)) img::map_range(ims[d.form[f].col], d.form[f].lo, d.form[f].hi, &d.form[f].lo, &d.form[f].hi);
     cols.n = n;
     cols.row0 = row0;
     cols.rowid_global = rowid_counts_from_the_table(sp.cols);
@@ -152,9 +178,11 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
         m.kind = ag.kind;
         m.constant = ag.constant;
         for (const ScanFactor &f : ag.fac) {
+            int64_t a = f.a, s = f.s;
+            if ((cols.image >> f.col) & 1u) img::compose(ims[f.col], f.a, f.s, &a, &s);     // a + s * (base + scale * e)
             m.used |= 1u << f.col;
-            if (f.a == 0 && f.s == 1) m.plain |= 1u << f.col;
-            m.fa[f.col] = f.a; m.fs[f.col] = f.s;
+            if (img::plain(a, s)) m.plain |= 1u << f.col;
+            m.fa[f.col] = a; m.fs[f.col] = s;
         }
     }
     return n;
@@ -172,10 +200,21 @@ static jit::Shape jit_shape(const MScanCols &cols, const ScanLaunch &cfg) {
     if (u && atoi(u) >= 1 && atoi(u) <= 8) sh.u = atoi(u);
     return sh;
 }
-static std::string jit_name(const jit::Shape &sh) {
+// (",img": some columns are read from their images -- a kernel that moves other bytes than the same form over the catalog columns)
+static std::string jit_name(const jit::Shape &sh, bool image) {
     return "k_mscan_specialised<" + std::to_string(sh.nc) + "," + std::to_string(sh.u) + "," + (sh.vec ? "vec" : "novec") + "," + (sh.grouped ? "grouped" : "global") +
-           (sh.der ? ",derived" : "") + ">";
+           (sh.der ? ",derived" : "") + (image ? ",img" : "") + ">";
 }
+// the precompiled kernel's name, marked the same way
+static std::string mscan_label(const ScanLaunch &cfg, const MScanCols &cols) {
+    std::string n = mscan_kernel_name(cfg);
+    if (cols.image && !n.empty() && n.back() == '>') n.insert(n.size() - 1, ",img");
+    return n;
+}
+// filter columns a staged form reads with the tile: 1, 2; 3 = the queue form (one); 4 = all of them (only aggregate inputs and the
+// sources of derived columns read late)
+static int eager_filters_of(int lazy) { return lazy == 3 ? 1 : lazy == 4 ? kMaxVCols : lazy; }
+static const char *late_suffix(int lazy) { return lazy == 3 ? ",queue" : lazy == 4 ? ",lateall" : lazy > 1 ? ",late2" : ",late"; }
 struct Specialised { std::shared_ptr<jit::Kernel> k; int grid = 0, per_cu = 0, u = 0, lazy = 0; size_t code_bytes = 0; std::string name, stages; };
 // "l_discount@1 l_quantity@2 l_extendedprice@last": which table columns a staged scan reads when (MsArgs::stages)
 static std::string stages_text(const vdl_plan *p, size_t s, const MsArgs &args) {
@@ -256,7 +295,7 @@ static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, i
     std::vector<char> code;
     MsArgs args = mscan_args(p->mcols[s]);
     if (lazy) {
-        args.stages = staged_columns(c, p->mcols[s], p->mdesc[s], grouped, &args.lazy, lazy == 3 ? 1 : lazy);
+        args.stages = staged_columns(c, p->mcols[s], p->mdesc[s], grouped, &args.lazy, eager_filters_of(lazy));
         if (!args.lazy) { why = "no column to read late"; return false; }
         if (lazy == 3) {
             // the queue form: the most selective filter column with the tile, EVERY other table column for the queued rows
@@ -286,15 +325,15 @@ static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, i
     int64_t grid = (int64_t)c->num_cus * per_cu;
     if (grid > p->mcols[s].n / tile) grid = p->mcols[s].n / tile;
     if (grid < 1) grid = 1;
-    out.grid = (int)grid; out.per_cu = per_cu; out.code_bytes = code.size(); out.name = jit_name(sh); out.u = sh.u; out.lazy = lazy;
-    if (lazy) out.name.insert(out.name.size() - 1, lazy == 3 ? ",queue" : lazy > 1 ? ",late2" : ",late");
+    out.grid = (int)grid; out.per_cu = per_cu; out.code_bytes = code.size(); out.name = jit_name(sh, p->mcols[s].image != 0); out.u = sh.u; out.lazy = lazy;
+    if (lazy) out.name.insert(out.name.size() - 1, late_suffix(lazy));
     if (lazy) out.stages = stages_text(p, s, args);
     return true;
 }
 static bool specialise_scan(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, std::string *kname) {
     Specialised sp;
     std::string why;
-    // (tests, profiles: VDL_JIT_LATE=1|2 forces the staged form -- with that many filter columns read with the tile -- where a column allows it)
+    // (tests, profiles: VDL_JIT_LATE=1|2 forces the staged form -- with that many filter columns read with the tile, 4: all of them -- where a column allows it)
     const int late = getenv("VDL_JIT_LATE") ? std::max(1, atoi(getenv("VDL_JIT_LATE"))) : 0;
     if (!(late && build_specialised(c, p, s, grouped, 0, late, sp, why)) && !build_specialised(c, p, s, grouped, 0, 0, sp, why)) { p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + why + "); "; return false; }
     p->mcfg[s].grid = sp.grid;
@@ -333,7 +372,9 @@ static void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
         // rows per lane first; then, at the winner, at 2 and at 1, the staged form that reads late (fewer rows per lane suit it:
         // its loads depend on each other, and what hides them is more waves, not more loads per wave)
         // (3 = the queue form: one filter column with the tile, the rows still in queued per wave and finished 64 at a time)
-        std::vector<std::pair<int, int>> cands = {{2, 0}, {3, 0}, {4, 0}, {6, 0}, {0, 1}, {3, 1}, {2, 1}, {1, 1}, {3, 2}, {2, 2}, {4, 2}, {4, 3}, {3, 3}, {6, 3}};
+        // (4 = every filter column with the tile, only aggregate inputs late: over narrow images the filter columns cost little)
+        std::vector<std::pair<int, int>> cands = {{2, 0}, {3, 0}, {4, 0}, {6, 0}, {0, 1}, {3, 1}, {2, 1}, {1, 1}, {3, 2}, {2, 2}, {4, 2}, {4, 3}, {3, 3}, {6, 3},
+                                                  {2, 4}, {3, 4}, {4, 4}};
         // VDL_JIT_PIN="u=3,late=2" (profiles: tools/profile_bench.sh runs the form a plain run chose, and nothing else): one candidate
         int pin_u = 0, pin_late = -1;
         if (const char *pin = getenv("VDL_JIT_PIN")) {
@@ -367,7 +408,7 @@ static void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
                 if (rep > 0) times.push_back(t);                // the first launch of a module pays for its load
             }
             const float ms = median_of(times);
-            tried += " u=" + std::to_string(u) + (lazy == 3 ? ",queue:" : lazy > 1 ? ",late2:" : lazy ? ",late:" : ":") + std::to_string((int)(ms * 1000)) + "us";
+            tried += " u=" + std::to_string(u) + (lazy ? late_suffix(lazy) : "") + ":" + std::to_string((int)(ms * 1000)) + "us";
             if (!best.k || ms < best_ms * 0.98f) { best = cand; best_ms = ms; }
             if (!lazy && (best_u == 0 || cand.k == best.k)) best_u = u;       // the staged forms start from the quickest eager shape
         }
@@ -450,7 +491,7 @@ static int64_t scan_bytes_moved(vdl_ctx *c, vdl_plan *p, std::string &detail) {
     HIP_CHECK(launch_mscan(cols, d, (const MScanDesc *)ddev->p, cfg, grouped, false, out, false, c->stream, cen.k->fn));
     unsigned long long lines[kMaxVCols] = {};
     c->fetch_to_host(counts->p, kMaxVCols, (int64_t *)lines, c->stream);
-    const MsArgs args = [&] { MsArgs a = mscan_args(cols); uint32_t lz = 0; a.stages = staged_columns(c, cols, p->mdesc[s], grouped, &lz, p->mjit_form[s].lazy == 3 ? 1 : p->mjit_form[s].lazy); a.lazy = lz; return a; }();
+    const MsArgs args = [&] { MsArgs a = mscan_args(cols); uint32_t lz = 0; a.stages = staged_columns(c, cols, p->mdesc[s], grouped, &lz, eager_filters_of(p->mjit_form[s].lazy)); a.lazy = lz; return a; }();
     for (int k = 0; k < cols.ncol; k++) {
         if (cols.kind[k] != VC_DIRECT) continue;
         const bool late = (args.lazy >> k) & 1u;
@@ -531,7 +572,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
             p->mparts[s] = dev_alloc(c, sizeof(int64_t) * (size_t)max_scan_grid(c, p, p->mcfg[s].grid) * (size_t)(p->mdesc[s].nagg + 1));
             p->mdesc[s].block_partials = (int64_t *)p->mparts[s]->p;
             if (!p->mdev[s]) p->mdev[s] = dev_alloc(c, sizeof(MScanDesc));
-            if (!p->kscan[s]) kname = (spec ? jname : std::string(mscan_kernel_name(p->mcfg[s]))) + "_grid" + std::to_string(p->mcfg[s].grid);
+            if (!p->kscan[s]) kname = (spec ? jname : mscan_label(p->mcfg[s], p->mcols[s])) + "_grid" + std::to_string(p->mcfg[s].grid);
         }
         p->word_offset[s] = off;
         off += (int64_t)sp.aggs.size() + 1;
@@ -558,7 +599,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         off += words;
         if (!gp.never && n * bpr > p->scan_bytes) {
             p->scan_bytes = n * bpr; p->scan_rows = n; p->dominant = (int)m;
-            p->dominant_kernel = (spec ? jname : std::string(mscan_kernel_name(p->mcfg[m]))) + "_grid" + std::to_string(p->mcfg[m].grid) + "_rep" + std::to_string(d.replicas);
+            p->dominant_kernel = (spec ? jname : mscan_label(p->mcfg[m], p->mcols[m])) + "_grid" + std::to_string(p->mcfg[m].grid) + "_rep" + std::to_string(d.replicas);
         }
     }
     p->bound = true;
@@ -1225,6 +1266,26 @@ int vdl_use_own_stream(vdl_ctx *c) {
     });
 }
 
+// The column's frame-of-reference image (vdl_column_image.h): min, max and shared decimal trailing zeros in one pass, the choice
+// on the host, the image in a second pass.  Replaces whatever image the column had; none when it would not be narrower.
+static void build_image(vdl_ctx *c, Column &col) {
+    col.image = img::Image{};
+    col.image_buf.reset();
+    if (col.n <= 0 || col.width <= 1) return;
+    BufP st = dev_alloc(c, 3 * sizeof(int64_t));
+    HIP_CHECK(launch_image_stats(col.dev, col.width, col.n, (unsigned long long *)st->p, c->stream));
+    int64_t w3[3] = {};
+    c->fetch_to_host(st->p, 3, w3, c->stream);
+    const int64_t mn = (int64_t)((uint64_t)w3[0] ^ 0x8000000000000000ull), mx = (int64_t)((uint64_t)w3[1] ^ 0x8000000000000000ull);
+    const img::Image im = img::choose(col.width, mn, mx, (int)w3[2]);
+    if (!im.width) return;
+    BufP buf = dev_alloc(c, (size_t)col.n * (size_t)im.width);
+    HIP_CHECK(launch_image_encode(col.dev, col.width, col.n, im.base, im.scale, buf->p, im.width, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    col.image = im;
+    col.image_buf = buf;
+}
+
 static void check_width(int w) {
     if (w != 1 && w != 2 && w != 4 && w != 8) throw Error(VDL_ERR_ARG, "elem_bytes must be 1, 2, 4 or 8");
 }
@@ -1269,8 +1330,39 @@ int vdl_generate_column(vdl_ctx *c, const char *name, int elem_bytes, int64_t ro
         col.dev = col.owned->p;
         HIP_CHECK(launch_gen_column(col.owned->p, elem_bytes, row0, nrows, seed, fnv1a(name), lo, hi, mul, add, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
+        build_image(c, col);
         c->cols[name] = col;
         c->catalog_version++;
+    });
+}
+
+int vdl_encode_column(vdl_ctx *c, const char *name) {
+    if (!c || !name) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        need_device(c);
+        auto it = c->cols.find(name);
+        if (it == c->cols.end()) throw Error(VDL_ERR_COLUMN, std::string("no column '") + name + "'");
+        build_image(c, it->second);
+        c->catalog_version++;
+    });
+}
+
+int vdl_column_image_info(const vdl_ctx *c, const char *name, int *width, int64_t *base, int64_t *scale) {
+    if (!c || !name) return VDL_ERR_ARG;
+    auto it = c->cols.find(name);
+    if (it == c->cols.end()) return VDL_ERR_COLUMN;
+    const img::Image &im = it->second.image;
+    if (width) *width = im.width;
+    if (base) *base = im.width ? im.base : 0;
+    if (scale) *scale = im.width ? im.scale : 1;
+    return VDL_OK;
+}
+
+int vdl_set_column_images(vdl_ctx *c, int on) {
+    if (!c) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        if (c->images != (on != 0)) c->catalog_version++;      // bound plans re-bind
+        c->images = on != 0;
     });
 }
 
@@ -1409,11 +1501,11 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
             std::vector<char> code;
             std::string log;
             MsArgs args = mscan_args(cols);
-            if (getenv("VDL_JIT_LATE")) args.stages = staged_columns(c, cols, *d, grouped, &args.lazy);      // the staged form of the same scan
+            if (getenv("VDL_JIT_LATE")) args.stages = staged_columns(c, cols, *d, grouped, &args.lazy, eager_filters_of(std::max(1, atoi(getenv("VDL_JIT_LATE")))));      // the staged form of the same scan
             if (getenv("VDL_JIT_LATE") && atoi(getenv("VDL_JIT_LATE")) == 3 && args.lazy) { args.queued = 1; args.stages = 0; }   // ... or its queue form
             if (!jit::compile(jit::mscan_source(args, *d, sh), c->arch, code, log))
                 throw Error(VDL_ERR_UNSUPPORTED, "scan " + std::to_string(s) + " does not build: " + log.substr(0, 2000));
-            p->jit_note += "scan " + std::to_string(s) + ": " + jit_name(sh) + (args.queued ? " (queue)" : args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";
+            p->jit_note += "scan " + std::to_string(s) + ": " + jit_name(sh, cols.image != 0) + (args.queued ? " (queue)" : args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";
         }
     });
 }

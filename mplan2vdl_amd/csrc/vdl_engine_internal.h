@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "vdl.h"
+#include "vdl_column_image.h"
 #include "vdl_exchange_analysis.h"
 #include "vdl_fuse.h"
 #include "vdl_ir.h"
@@ -88,6 +89,10 @@ struct Column {
     int width = 0;
     int64_t n = 0;
     BufP owned;
+    // the column's frame-of-reference image (vdl_column_image.h), read by aggregate scans where the rules allow: width 0 = none.
+    // Aligned and padded like a column; it goes with the column (drop, re-registration)
+    img::Image image;
+    BufP image_buf;
 };
 
 // device-side vector of the general path
@@ -180,6 +185,7 @@ struct vdl_ctx {
     std::string arch = "gfx950";           // --offload-arch of run-time specialisation (the device's, when there is one)
     std::map<std::string, Column> cols;
     uint64_t catalog_version = 1;      // bumped on every catalog change: plans re-bind only when it moved
+    bool images = true;                // aggregate scans read the columns' images where the rules allow (vdl_set_column_images)
     const std::map<std::string, Column> *overlay = nullptr;     // columns that stand in for catalog entries during one run (vdl_comm.cpp: sharded_replicate)
     uint64_t overlay_epoch = 0;                                  // moves whenever the overlay is set or cleared
     // what bindings and kernels specialised for column addresses / widths / lengths are keyed by: the catalog's state AND the overlay's

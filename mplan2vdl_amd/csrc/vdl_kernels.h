@@ -78,6 +78,10 @@ hipError_t launch_mscan_resolve_first(const MScanCols &cols, const MScanDesc &d,
 // ---- synthetic data --------------------------------------------------------------------
 hipError_t launch_gen_column(void *out, int elem_bytes, int64_t row0, int64_t n, uint64_t seed, uint64_t col_id,
                              int64_t lo, int64_t hi, int64_t mul, int64_t add, hipStream_t s);
+// frame-of-reference images of columns (vdl_image.hip; the rules: vdl_column_image.h): out3 = {min, max} as int64 ^ 2^63, then the
+// decimal trailing zeros all values share with the first row (19: all equal); then e = (v - base) / scale into img (1, 2 or 4 bytes)
+hipError_t launch_image_stats(const void *col, int elem_bytes, int64_t n, unsigned long long *out3, hipStream_t s);
+hipError_t launch_image_encode(const void *col, int elem_bytes, int64_t n, int64_t base, int64_t scale, void *img, int img_bytes, hipStream_t s);
 
 // ---- per-operator kernels -----------------------------------------------------------------
 // validity bitmaps: bit (i & 63) of word (i >> 6); nullptr = every slot holds a value.

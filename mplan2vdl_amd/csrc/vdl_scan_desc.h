@@ -100,6 +100,7 @@ struct MScanCols {                           // host-side description of a scan'
     int64_t lo[kMaxVCols] = {}, hi[kMaxVCols] = {};
     int kind[kMaxVCols] = {};                // VColKind (vdl_fuse.h); 0 = read from the scanned table
     int lazy[kMaxVCols] = {};                // projection scan: the column decides nothing about a row's survival -- read it for survivors only
+    uint32_t image = 0;                      // bit c: column c is read from its frame-of-reference image (vdl_column_image.h; bounds rewritten)
 };
 struct MAggDesc {
     int kind = 0;                            // AGG_SUM / AGG_MIN / AGG_MAX / AGG_FIRST

@@ -377,6 +377,21 @@ class Engine:
             owner = self
         return _Column()
 
+    def encode(self, name):
+        """Build the frame-of-reference image of a catalog column (vdl_encode_column; generated columns have one already).
+        For a borrowed column the caller promises not to write it afterwards."""
+        self._check(self._L.vdl_encode_column(self._c, name.encode()))
+
+    def image_info(self, name):
+        """(width, base, scale) of a column's image: v = base + scale * e; width 0 = no image"""
+        w, b, s = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._L.vdl_column_image_info(self._c, name.encode(), ctypes.byref(w), ctypes.byref(b), ctypes.byref(s)))
+        return w.value, b.value, s.value
+
+    def set_column_images(self, enabled):
+        """False: scans read the catalog columns and ignore their images (tests, A/B runs in one process)"""
+        self._check(self._L.vdl_set_column_images(self._c, 1 if enabled else 0))
+
     def drop(self, name):
         self._keep.pop(name, None)
         self._check(self._L.vdl_drop_column(self._c, name.encode()))

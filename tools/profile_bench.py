@@ -52,6 +52,8 @@ def pin_of(label):
         return None
     if ",queue>" in label:
         return "u=%s,late=3" % m.group(1)
+    if ",lateall>" in label:                       # every filter column with the tile, the aggregate inputs late
+        return "u=%s,late=4" % m.group(1)
     late = re.search(r",late(\d?)>", label)
     return "u=%s,late=%s" % (m.group(1), (late.group(1) or "1") if late else "0")
 
