@@ -144,6 +144,12 @@ int  vdl_plan_set_fusion(vdl_plan *plan, int enabled);
 int  vdl_plan_set_jit(vdl_plan *plan, int enabled);
 const char *vdl_plan_jit_note(const vdl_plan *plan);
 int  vdl_plan_jit_check(vdl_ctx *ctx, vdl_plan *plan);
+/* Which catalog columns the plan's scans read from their images, as bound at its last run or vdl_plan_jit_check: one entry
+ * per scan role that reads any -- "scan<k>" (fused aggregate scans), "front.select" / "front.take" (the two sides of a fused
+ * front), "dim<k>" (dimension scans), "semi<k>" (semi-join scans) -- each listing "table.column:width", e.g.
+ * "front.select: lineitem.l_shipdate:2 lineitem.lineitem_orders:4; dim3: orders.o_orderdate:2".  "" when none does.
+ * The text stays valid until the next call for this plan. */
+int  vdl_plan_image_columns(const vdl_plan *plan, const char **list);
 
 /* Execute: binds Loads to the catalog, runs all kernels, copies the MaterializeCompact
  * outputs to the host and synchronises. */

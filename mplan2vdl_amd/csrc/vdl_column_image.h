@@ -85,5 +85,16 @@ inline bool plain(int64_t a, int64_t s) { return a == 0 && s == 1; }
 // read only when every use is a range filter, a formula test or an aggregate factor (other than a FIRST); a pure narrowing always.
 inline bool usable(const Image &im, bool raw_use) { return im.width > 0 && (im.pure() || !raw_use); }
 
+// Uses of a column inside a scan with derived columns -- a fused front, a dimension scan, a semi-join scan.  A column whose values the
+// select pass needs only for its filters and formula tests stays in the encoded domain there (bounds rewritten as above).  A column
+// whose values it needs per row -- the source of a lookup or a difference, the position of a semi-join -- is decoded with the tile,
+// and that may only cost an add: such a column is read from its image only when the scale is 1 (its filters stay as planned).  The
+// take side of a front decodes whatever it loads for a survivor, base + scale * e in wrapping 64-bit arithmetic (outputs, operands of
+// row expressions), once per survivor, at any scale; a carried column travels decoded, or is not carried.  A pure narrowing decodes
+// to itself and costs nothing.
+inline bool usable_in_vscan(const Image &im, bool per_row_value) { return im.width > 0 && (im.scale == 1 || !per_row_value); }
+// the kernels must decode the column's values (MsArgs::decode)
+inline bool needs_decode(const Image &im) { return im.width > 0 && !im.pure(); }
+
 }  // namespace img
 }  // namespace vdl

@@ -124,6 +124,14 @@ static uint32_t raw_value_uses(const std::vector<ScanColumn> &sc, const std::vec
 static const std::vector<KeyStep> *key_of(const ScanPlan &) { return nullptr; }
 static const std::vector<KeyStep> *key_of(const GroupScanPlan &gp) { return &gp.key; }
 
+// "name:width ..." of the columns (bits of `which`) a bound scan reads from their images: its entry in vdl_plan_image_columns
+static std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u) {
+    std::string t;
+    for (int k = 0; k < cols.ncol && (size_t)k < sc.size(); k++)
+        if (((cols.image & which) >> k) & 1u) t += (t.empty() ? "" : " ") + sc[(size_t)k].name + ":" + std::to_string(cols.width[k]);
+    return t;
+}
+
 template <typename PlanT>
 int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0) {
     cols = MScanCols{};
@@ -519,6 +527,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
     p->mjit_form.assign(ns + ng, vdl_plan::JitForm{});
     p->kscan.assign(ns + ng, 0);
     p->jit_note.clear();
+    for (auto it = p->image_roles.begin(); it != p->image_roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->image_roles.erase(it) : std::next(it);
     p->jit_tuned = false;
     p->gword_offset.assign(ng, 0);
     p->reduce_ops.clear();
@@ -564,6 +573,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         if (!p->kscan[s]) {
             bpr = 0;
             n = bind_mscan(c, sp, p->mcols[s], p->mdesc[s], &bpr, p->row_offset);
+            p->image_roles["scan" + std::to_string(s)] = image_text(sp.cols, p->mcols[s]);
             p->mcfg[s] = mscan_launch_config(p->mcols[s], p->mdesc[s], false, c->num_cus);
             if (p->mcfg[s].variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no multi-aggregate scan kernel variant for this shape");
             std::string jname;
@@ -583,6 +593,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         const size_t m = ns + g;
         int64_t bpr = 0;
         const int64_t n = bind_mscan(c, gp, p->mcols[m], p->mdesc[m], &bpr, p->row_offset);
+        p->image_roles["scan" + std::to_string(m)] = image_text(gp.cols, p->mcols[m]);
         MScanDesc &d = p->mdesc[m];
         d.nkey = (int)gp.key.size();
         for (int k = 0; k < d.nkey; k++) d.key[k] = gp.key[(size_t)k];
@@ -608,9 +619,18 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
 void patch_prelude(const vdl_plan *p, const std::vector<ScanColumn> &sc, MScanCols &cols, MScanDesc &d);
 // The columns of a scan with derived columns (fused front, dimension scans) as kernel arguments; the table's row count.
 // Tables of the prelude are patched in later (patch_prelude); `wanted` collects which ones.
-static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vector<ScanColumn> &sc, MScanCols &cols, MScanDesc &d, std::vector<char> &wanted) {
+// A table column with an image is read from it where the use rules allow (vdl_column_image.h usable_in_vscan), ibase / iscale its
+// decode.  One whose values the select pass needs per row (`per_row`: the sources of lookups and differences, plus what the caller
+// names -- the position of a semi-join) and that is not a pure narrowing is decoded with the tile (MsArgs::decode, one add) and
+// keeps the plan's filters; every other one has its filter and formula tests rewritten into the encoded domain.  (The take side of a
+// front decodes everything it loads: bind_front.)
+static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vector<ScanColumn> &sc, MScanCols &cols, MScanDesc &d, std::vector<char> &wanted,
+                          uint32_t per_row = 0) {
     cols.ncol = (int)sc.size();
     int64_t n = -1;
+    for (const ScanColumn &s : sc)                                    // sources of lookups and differences
+        if (s.kind != VC_DIRECT && s.kind != VC_FORM) for (int src : {s.idx, s.idx2}) if (src >= 0 && src < 32) per_row |= 1u << src;
+    img::Image ims[kMaxVCols];
     for (int k = 0; k < cols.ncol; k++) {
         const ScanColumn &s = sc[(size_t)k];
         cols.kind[k] = s.kind;
@@ -623,6 +643,18 @@ static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vecto
             if (n >= 0 && col.n != n) throw Error(VDL_ERR_SHAPE, "columns of table '" + table + "' have different lengths in the catalog");
             n = col.n;
             cols.ptr[k] = col.dev; cols.width[k] = col.width;
+            if (c->images && col.image_buf && img::usable_in_vscan(col.image, (per_row >> k) & 1u)) {
+                ims[k] = col.image;
+                cols.image |= 1u << k;
+                cols.ptr[k] = col.image_buf->p; cols.width[k] = col.image.width;
+                d.ibase[k] = col.image.base; d.iscale[k] = col.image.scale;
+                if (img::needs_decode(col.image) && ((per_row >> k) & 1u)) {
+                    cols.decode |= 1u << k;
+                } else {
+                    img::map_range(col.image, s.lo, s.hi, &cols.lo[k], &cols.hi[k]);
+                    d.flo[k] = cols.lo[k]; d.fhi[k] = cols.hi[k];
+                }
+            }
         } else if (s.kind == VC_GATHER || s.kind == VC_INRANGE) {
             const Column &col = find_col(c, s.name);
             cols.ptr[k] = col.dev; cols.width[k] = col.width;
@@ -633,6 +665,11 @@ static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vecto
         }
     }
     bind_forms(sc, d);
+    for (int k = 0; k < cols.ncol; k++)                               // a formula's tests of a column read from its image
+        if (cols.kind[k] == VC_FORM)
+            for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dtests[k]; f++)
+                if (d.form[f].col >= 0 && (((cols.image & ~cols.decode) >> d.form[f].col) & 1u))
+                    img::map_range(ims[d.form[f].col], d.form[f].lo, d.form[f].hi, &d.form[f].lo, &d.form[f].hi);
     cols.n = n;
     return n;
 }
@@ -654,7 +691,7 @@ static hipFunction_t front_kernel(vdl_ctx *c, vdl_plan *p, const std::string &ro
     std::vector<char> code;
     std::string why;
     if (jit::compile(jit::scan_source(kind, mscan_args(cols), d, sh), c->arch, code, why)) fk.k = jit::load(code, why, jit::entry_name(kind));
-    if (fk.k) p->jit_note += role + ": " + jit::entry_name(kind) + "<" + std::to_string(sh.nc) + ">, " + std::to_string(code.size()) + " B of code; ";
+    if (fk.k) p->jit_note += role + ": " + jit::entry_name(kind) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + ">, " + std::to_string(code.size()) + " B of code; ";
     else p->jit_note += role + ": not specialised (" + why.substr(0, 400) + "); ";
     return fk.k ? fk.k->fn : nullptr;
 }
@@ -676,7 +713,7 @@ static hipFunction_t front_kernel_one_pass(vdl_ctx *c, vdl_plan *p, const MScanC
     std::vector<char> code;
     std::string why;
     if (jit::compile(jit::front_source(mscan_args(scols), sd, mscan_args(tcols), td, sh, tcols.ncol), c->arch, code, why)) fk.k = jit::load(code, why, jit::entry_name(jit::FRONT));
-    if (fk.k) p->jit_note += role + ": " + jit::entry_name(jit::FRONT) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ">, " + std::to_string(code.size()) + " B of code; ";
+    if (fk.k) p->jit_note += role + ": " + jit::entry_name(jit::FRONT) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ((scols.image | tcols.image) ? ",img" : "") + ">, " + std::to_string(code.size()) + " B of code; ";
     else p->jit_note += role + ": not specialised (" + why.substr(0, 400) + "); ";
     return fk.k ? fk.k->fn : nullptr;
 }
@@ -736,7 +773,9 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         host_descs.push_back(std::make_shared<MScanDesc>());
         MScanDesc *d = host_descs.back().get();
         std::vector<char> unused(F.prelude.size(), 0);
-        const int64_t n = bind_vcols(c, it.table, it.cols, cols, *d, unused);
+        const uint32_t pos = semi && it.index_col >= 0 && it.index_col < 32 ? 1u << it.index_col : 0u;      // (the semi-join's positions)
+        const int64_t n = bind_vcols(c, it.table, it.cols, cols, *d, unused, pos);
+        p->image_roles[(semi ? "semi" : "dim") + std::to_string(k)] = image_text(it.cols, cols);
         patch_prelude(p, it.cols, cols, *d);
         if (semi) {
             // the set of rows of another table that a selected row of this one points at: one scan, atomic ORs
@@ -976,6 +1015,8 @@ static void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b) {
         scols.ptr[j] = cols.ptr[k]; scols.width[j] = cols.width[k]; scols.filtered[j] = cols.filtered[k];
         scols.lo[j] = cols.lo[k]; scols.hi[j] = cols.hi[k]; scols.kind[j] = cols.kind[k];
         sdesc->flo[j] = d.flo[k]; sdesc->fhi[j] = d.fhi[k]; sdesc->dkind[j] = d.dkind[k]; sdesc->dn[j] = d.dn[k]; sdesc->dtests[j] = d.dtests[k];
+        scols.image |= ((cols.image >> k) & 1u) << j; scols.decode |= ((cols.decode >> k) & 1u) << j;
+        sdesc->ibase[j] = d.ibase[k]; sdesc->iscale[j] = d.iscale[k];
         if (d.dkind[k] == VC_FORM) {                          // its steps stay where they are in the pool; the tests' columns are
             sdesc->dsrc[j] = d.dsrc[k]; sdesc->dsrc2[j] = d.dsrc2[k];      // renumbered (monotonic: they stay sorted by column)
             for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dsrc2[k]; f++) {
@@ -988,6 +1029,15 @@ static void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b) {
         sdesc->dsrc2[j] = d.dsrc2[k] >= 0 ? renum[(size_t)d.dsrc2[k]] : -1;
     }
     scols.n = b.n;
+    // the take side decodes what it loads from an image (MsArgs::decode): its own filters and formula tests go back to the columns' values
+    const uint32_t sel_decode = cols.decode;
+    cols.decode = 0;
+    for (int k = 0; k < cols.ncol; k++) {
+        if (!((cols.image >> k) & 1u)) continue;
+        d.flo[k] = J.cols[(size_t)k].lo; d.fhi[k] = J.cols[(size_t)k].hi;
+        if (d.ibase[k] != 0 || d.iscale[k] != 1) cols.decode |= 1u << k;
+    }
+    bind_forms(J.cols, d);
     // the take pass: one packed vector per produced column (statements that are the same column share it), and what those
     // columns are derived from
     // (`distinct` holds output codes: a column, or -2 - e for the row expression e the pass evaluates: ProjPlan::exprs)
@@ -1015,10 +1065,15 @@ static void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b) {
     int taken = 0;
     for (int k = 0; k < cols.ncol && taken < kMaxCarry; k++) {
         if (cols.lazy[k] || cols.kind[k] != VC_DIRECT || !((d.take >> k) & 1u) || renum[(size_t)k] < 0) continue;
+        if (((cols.decode & ~sel_decode) >> k) & 1u) continue;       // the select side holds its encoded values: the take side loads it
         d.carry |= 1u << k;
         sdesc->carry |= 1u << renum[(size_t)k];
         taken++;
     }
+    uint32_t deciding = 0;
+    for (int k = 0; k < cols.ncol; k++) if (renum[(size_t)k] >= 0) deciding |= 1u << k;
+    p->image_roles["front.select"] = image_text(J.cols, cols, deciding);
+    p->image_roles["front.take"] = image_text(J.cols, cols, d.take);
 }
 // the prelude's tables of this run, in both passes' arguments
 static void patch_front(const vdl_plan *p, FrontBound &b) {
@@ -1436,6 +1491,14 @@ int vdl_plan_set_jit(vdl_plan *p, int enabled) {
     return VDL_OK;
 }
 const char *vdl_plan_jit_note(const vdl_plan *p) { return p ? p->jit_note.c_str() : ""; }
+int vdl_plan_image_columns(const vdl_plan *p, const char **list) {
+    if (!p || !list) return VDL_ERR_ARG;
+    p->image_list.clear();
+    for (const auto &r : p->image_roles)
+        if (!r.second.empty()) p->image_list += (p->image_list.empty() ? "" : "; ") + r.first + ": " + r.second;
+    *list = p->image_list.c_str();
+    return VDL_OK;
+}
 // Builds (hiprtc; no GPU needed) the specialised kernel of every multi-aggregate scan of the plan against the columns
 // registered now, without loading or running anything: the note lists each kernel with its code size, or why it failed.
 int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
@@ -1452,17 +1515,23 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
                 std::string log;
                 if (!jit::compile(jit::scan_source(kind, mscan_args(cols), d, sh), c->arch, code, log))
                     throw Error(VDL_ERR_UNSUPPORTED, role + " does not build: " + log.substr(0, 2000));
-                p->jit_note += role + ": " + jit::entry_name(kind) + "<" + std::to_string(sh.nc) + ">, " + std::to_string(code.size()) + " B of code; ";
+                p->jit_note += role + ": " + jit::entry_name(kind) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + ">, " + std::to_string(code.size()) + " B of code; ";
             };
             const FusedPlan &F = p->fused;
             for (size_t k = 0; k < F.prelude.size(); k++) {
-                if (F.prelude[k].kind != PreludeItem::DIM_BITMAP || !F.prelude[k].scan) continue;
+                const PreludeItem &it = F.prelude[k];
+                const bool semi = it.kind == PreludeItem::SEMI_BITMAP;
+                if (!(semi || it.kind == PreludeItem::DIM_BITMAP) || !it.scan) continue;
                 MScanCols cols;
                 auto d = std::make_unique<MScanDesc>();
                 std::vector<char> unused(F.prelude.size(), 0);
-                bind_vcols(c, F.prelude[k].table, F.prelude[k].cols, cols, *d, unused);
-                d->bitmap_only = 1;
-                build("dim" + std::to_string(k), jit::SELECT, cols, *d);
+                const uint32_t pos = semi && it.index_col >= 0 && it.index_col < 32 ? 1u << it.index_col : 0u;
+                bind_vcols(c, it.table, it.cols, cols, *d, unused, pos);
+                const std::string role = (semi ? "semi" : "dim") + std::to_string(k);
+                p->image_roles[role] = image_text(it.cols, cols);
+                d->bitmap_only = semi ? 2 : 1;
+                if (semi) { d->pmin = it.modulus; d->nout = 1; d->out_col[0] = it.index_col; }
+                build(role, jit::SELECT, cols, *d);
             }
             FrontBound fb;
             bind_front(c, p, fb);
@@ -1473,7 +1542,8 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
                 std::string log;
                 if (!jit::compile(jit::front_source(mscan_args(fb.scols), *fb.sdesc, mscan_args(fb.cols), *fb.d, sh, fb.cols.ncol), c->arch, code, log))
                     throw Error(VDL_ERR_UNSUPPORTED, "front does not build: " + log.substr(0, 2000));
-                p->jit_note += std::string("front: ") + jit::entry_name(jit::FRONT) + "<" + std::to_string(sh.nc) + "," + std::to_string(fb.cols.ncol) + ">, " + std::to_string(code.size()) + " B of code; ";
+                p->jit_note += std::string("front: ") + jit::entry_name(jit::FRONT) + "<" + std::to_string(sh.nc) + "," + std::to_string(fb.cols.ncol) +
+                               ((fb.scols.image | fb.cols.image) ? ",img" : "") + ">, " + std::to_string(code.size()) + " B of code; ";
             }
             return;
         }
@@ -1488,11 +1558,13 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
             if (grouped) {
                 const GroupScanPlan &gp = F.gscans[s - ns];
                 bind_mscan(c, gp, cols, *d, &bpr, 0);
+                p->image_roles["scan" + std::to_string(s)] = image_text(gp.cols, cols);
                 d->nkey = (int)gp.key.size();
                 for (int k = 0; k < d->nkey; k++) d->key[k] = gp.key[(size_t)k];
                 d->pmin = gp.pmin; d->pcount = gp.pcount;
             } else {
                 bind_mscan(c, F.scans[s], cols, *d, &bpr, 0);
+                p->image_roles["scan" + std::to_string(s)] = image_text(F.scans[s].cols, cols);
             }
             const ScanLaunch cfg = mscan_launch_config(cols, *d, grouped, c->num_cus);
             if (cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no scan kernel variant for this shape");

@@ -269,6 +269,10 @@ struct vdl_plan {
     std::shared_ptr<void> front_keep;                        // the fused front's bound descriptors of the current run, likewise
     std::vector<char> kscan;                 // [scan] runs on the single-aggregate k_scan (decided when the plan is bound / tuned)
     std::string jit_note;                    // what was specialised, or why not
+    // by scan role ("scan<k>", "front.select", "front.take", "dim<k>", "semi<k>"): the catalog columns the scan bound last read from their
+    // images, "name:width ..." (vdl_plan_image_columns); roles without one hold ""
+    std::map<std::string, std::string> image_roles;
+    mutable std::string image_list;          // what vdl_plan_image_columns handed out last
     std::vector<BufP> prelude_buf;           // fused join scans: dimension bitmaps / LIKE tables of the current run (FusedPlan::prelude)
     std::vector<int64_t> prelude_n;
     std::vector<int64_t> prelude_rows;       // SEMI_BITMAP items: rows of the (local) source table the set was built from

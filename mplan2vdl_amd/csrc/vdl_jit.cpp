@@ -188,12 +188,13 @@ static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, con
     o << "namespace vdl {\n";
     o << "constexpr MsArgs jit_args" << suffix << "() {\n    MsArgs a{};\n";
     o << "    a.ncol = " << C.ncol << "; a.widths = " << C.widths << "ull; a.filtered = " << C.filtered << "u; a.derived = " << C.derived
-      << "u; a.lazy = " << C.lazy << "u; a.stages = " << C.stages << "ull; a.queued = " << C.queued << ";\n    return a;\n}\n";
+      << "u; a.lazy = " << C.lazy << "u; a.stages = " << C.stages << "ull; a.queued = " << C.queued << "; a.decode = " << C.decode << "u;\n    return a;\n}\n";
     o << "constexpr MScanDesc jit_desc" << suffix << "() {\n    MScanDesc d{};\n";
     o << "    d.nagg = " << D.nagg << "; d.nkey = " << D.nkey << "; d.replicas = " << D.replicas << "; d.pmin = " << lit(D.pmin) << "; d.pcount = " << lit(D.pcount) << ";\n";
     int pool = 0;
     for (int k = 0; k < C.ncol; k++) {
         if ((C.filtered >> k) & 1u) o << "    d.flo[" << k << "] = " << lit(D.flo[k]) << "; d.fhi[" << k << "] = " << lit(D.fhi[k]) << ";\n";
+        if ((C.decode >> k) & 1u) o << "    d.ibase[" << k << "] = " << lit(D.ibase[k]) << "; d.iscale[" << k << "] = " << lit(D.iscale[k]) << ";\n";
         if ((C.derived >> k) & 1u) {
             o << "    d.dkind[" << k << "] = " << D.dkind[k] << "; d.dsrc[" << k << "] = " << D.dsrc[k] << "; d.dsrc2[" << k << "] = " << D.dsrc2[k]
               << "; d.dtests[" << k << "] = " << D.dtests[k] << ";\n";

@@ -44,6 +44,10 @@ __device__ __forceinline__ int64_t load_scalar(const void *p, int width, int64_t
     default: return ((const int8_t *)p)[i];
     }
 }
+// a value read from a column image (vdl_column_image.h) as the column holds it: base + scale * e, in wrapping 64-bit arithmetic
+__device__ __forceinline__ int64_t img_decode(int64_t e, int64_t base, int64_t scale) {
+    return (int64_t)((uint64_t)base + (uint64_t)scale * (uint64_t)e);
+}
 template <bool NT, typename V>
 __device__ __forceinline__ V stream_load(const char *p) {
     if (NT) return __builtin_nontemporal_load((const V *)p);
@@ -142,6 +146,22 @@ __device__ __forceinline__ void load_tile(const MsArgs &C, const MsArgs &Cr, int
 #pragma unroll
                 for (int u = 0; u < U; u++) { i8x2 x = stream_load<NT, i8x2>(p + (base + (int64_t)u * (BS * 2))); v[c][2 * u] = x.x; v[c][2 * u + 1] = x.y; }
             }
+        }
+    }
+}
+
+// The select side of a projection scan: the columns of C.decode -- read from an image of scale 1 (vdl_column_image.h usable_in_vscan)
+// because their values are needed per row: the source of a lookup or a difference, a semi-join position, a carried value -- become
+// the column's own values as soon as the tile is in, by one add (their filters were left as the plan has them); every other column
+// read from an image stays in the encoded domain, its filters and formula tests rewritten by the host.
+template <int NC, int RW>
+__device__ __forceinline__ void decode_tile(const MsArgs &C, const MScanDesc &D, int64_t (&v)[NC][RW]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        if ((C.decode >> c) & 1u) {                        // wave-uniform
+            const uint64_t ib = (uint64_t)D.ibase[c];
+#pragma unroll
+            for (int r = 0; r < RW; r++) v[c][r] = (int64_t)((uint64_t)v[c][r] + ib);
         }
     }
 }
@@ -750,6 +770,7 @@ __device__ __forceinline__ void project_select_body(const MsArgs &C, const MsArg
                 }
             }
         }
+        decode_tile<NC, ROWS>(C, D, v);
         bool alive[ROWS];
 #pragma unroll
         for (int r = 0; r < ROWS; r++) alive[r] = base + (int64_t)(r >> 1) * (BS * 2) + (r & 1) < Cr.n;
@@ -878,6 +899,7 @@ __device__ __forceinline__ void project_front_body(const MsArgs &Cs, const MsArg
                     }
                 }
             }
+            decode_tile<NCS, ROWS>(Cs, Ds, v);
             bool alive[ROWS];
 #pragma unroll
             for (int r = 0; r < ROWS; r++) alive[r] = base + (int64_t)(r >> 1) * (BS * 2) + (r & 1) < Csr.n;
@@ -926,6 +948,7 @@ __device__ __forceinline__ void project_front_body(const MsArgs &Cs, const MsArg
             if (Ds.carry) {
                 // the survivors' values of the deciding columns that the outputs want too (the join index of a fact table whose dimension
                 // is filtered): they are in registers here -- kept in survivor order instead of being fetched again line by isolated line
+                // (a column read from an image is carried only when the select side holds its own values: plain or decoded with the tile)
                 int ci = 0;
 #pragma unroll
                 for (int c = 0; c < NCS; c++) {
@@ -971,6 +994,7 @@ __device__ __forceinline__ void project_front_body(const MsArgs &Cs, const MsArg
         }
         // the survivors' rows: what the outputs need of them -- fact columns at the row (carried values from LDS), dimension columns
         // through the index -- and the packed vectors.  (Nothing is written beyond the vectors' capacity: the host may have guessed it.)
+        // Columns read from images are decoded as they are loaded: everything the take side computes is in the columns' own values.
         if (off < Dtr.out_cap) {
             for (int k = tid; k < total; k += BS) {
                 const int64_t row = batch * (kFrontBatch * TILE) + (int64_t)spos[k];
@@ -980,7 +1004,10 @@ __device__ __forceinline__ void project_front_body(const MsArgs &Cs, const MsArg
                     vt[c][0] = 0;
                     if (c < Ct.ncol && ((Dt.take >> c) & 1u) && !((Ct.derived >> c) & 1u)) {
                         if (((Dt.carry >> c) & 1u) && k < kFrontCarry) vt[c][0] = cst[__builtin_popcount(Dt.carry & ((1u << c) - 1u))][k];
-                        else vt[c][0] = load_scalar(Ctr.ptr[c], Ct.width(c), row);
+                        else {
+                            vt[c][0] = load_scalar(Ctr.ptr[c], Ct.width(c), row);
+                            if ((Ct.decode >> c) & 1u) vt[c][0] = img_decode(vt[c][0], Dt.ibase[c], Dt.iscale[c]);
+                        }
                     }
                 }
                 bool on[1] = {true};

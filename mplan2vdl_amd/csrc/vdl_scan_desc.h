@@ -101,6 +101,7 @@ struct MScanCols {                           // host-side description of a scan'
     int kind[kMaxVCols] = {};                // VColKind (vdl_fuse.h); 0 = read from the scanned table
     int lazy[kMaxVCols] = {};                // projection scan: the column decides nothing about a row's survival -- read it for survivors only
     uint32_t image = 0;                      // bit c: column c is read from its frame-of-reference image (vdl_column_image.h; bounds rewritten)
+    uint32_t decode = 0;                     // bit c: ... and decoded by the kernel (MsArgs::decode)
 };
 struct MAggDesc {
     int kind = 0;                            // AGG_SUM / AGG_MIN / AGG_MAX / AGG_FIRST
@@ -120,6 +121,9 @@ struct MScanDesc {                           // lives in device memory, read wit
     int dtests[kMaxVCols] = {};
     FormStep form[kMaxFormPool];
     int64_t dn[kMaxVCols] = {};              // derived columns: entries of the table looked up
+    // projection scans (fronts, dimension and semi-join scans): column c read from its image is ibase[c] + iscale[c] * e (wrapping); read
+    // only for the columns of MsArgs::decode
+    int64_t ibase[kMaxVCols] = {}, iscale[kMaxVCols] = {};
     // projection scan (k_project): what to write for the surviving rows
     int nout = 0, out_col[kMaxProjOuts] = {};     // out_col[o] >= 0: that column; -2 - e: the row expression e (below)
     // row expressions the take pass computes for the survivors instead of handing their operands over (Q3's composite group key
@@ -160,6 +164,9 @@ struct MsArgs {
     uint32_t filtered = 0;                   // bit c: column c has a range filter (MScanDesc::flo / fhi)
     uint32_t derived = 0;                    // bit c: column c is derived from earlier columns (MScanDesc::dkind ...), ptr[c] = its table
     uint32_t lazy = 0;                       // bit c: not read with the tile (projection scan: needed for surviving rows only; staged scans: below)
+    // projection scans, bit c: read from an image that is not a pure narrowing, decoded (MScanDesc::ibase / iscale) -- on the select
+    // side as the tile comes in (scale 1: per-row values, vdl_column_image.h usable_in_vscan), on the take side as a survivor's is loaded
+    uint32_t decode = 0;
     // specialised aggregate scans that read late (vdl_jit.cpp): 4 bits per table column -- 0: read with the tile; 1..3: a filter
     // column read for the rows that passed the earlier stages; 14: a source of derived columns / of the group key, read for
     // the rows that passed every filter on table columns; 15: an aggregate input only, read for the rows that passed everything

@@ -12,6 +12,10 @@
 // table (--shard, default lineitem) and the other tables in full, joins an RCCL communicator (rank 0's id travels through a
 // file in a private temporary directory) and calls vdl_run_sharded.  The parent prints ONE reply: the common answer of a
 // fold plan, or the ranks' slices concatenated in rank order for a plan with a Partition.
+//   ... | vdlrun --encode ...                                                  columns read through their images
+// --encode builds the frame-of-reference image of every column it uploads or generates (vdl_encode_column; each rank of its own
+// rows), so that the scans read the narrow copies; after the run one line "vdlrun: images: <vdl_plan_image_columns>" goes to
+// stderr (rank 0's).  The reply on stdout is the same as without it.
 #include <signal.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -43,7 +47,7 @@ const GenSpec kLineitem[] = {
 struct ColFile { int width; int64_t rows; };
 
 int load_data_dir(vdl_ctx *ctx, const std::string &dir, const std::string &program, const std::string &shard_table = "", int rank = 0, int world = 1,
-                  int64_t *row0_out = nullptr) {
+                  int64_t *row0_out = nullptr, bool encode = false) {
     std::map<std::string, ColFile> listed;
     std::ifstream manifest(dir + "/columns.csv");
     if (!manifest) { std::fprintf(stderr, "vdlrun: cannot read %s/columns.csv\n", dir.c_str()); return 1; }
@@ -79,8 +83,12 @@ int load_data_dir(vdl_ctx *ctx, const std::string &dir, const std::string &progr
             std::fprintf(stderr, "vdlrun: %s/%s.bin is missing or shorter than the %lld rows columns.csv lists\n", dir.c_str(), name.c_str(), (long long)it->second.rows);
             return 1;
         }
-        const int rc = vdl_upload_column(ctx, name.c_str(), buf.data(), it->second.width, hi - lo);
+        int rc = vdl_upload_column(ctx, name.c_str(), buf.data(), it->second.width, hi - lo);
         if (rc) { std::fprintf(stderr, "vdlrun: vdl_upload_column(%s) failed (%d): %s\n", name.c_str(), rc, vdl_last_error(ctx)); return 1; }
+        if (encode && (rc = vdl_encode_column(ctx, name.c_str()))) {
+            std::fprintf(stderr, "vdlrun: vdl_encode_column(%s) failed (%d): %s\n", name.c_str(), rc, vdl_last_error(ctx));
+            return 1;
+        }
         listed.erase(it);                                  // a column loaded twice by the program is uploaded once
         listed[name] = ColFile{0, -1};
     }
@@ -160,7 +168,7 @@ bool read_reply(const std::string &path, Reply &r) {
 struct Options {
     int64_t rows = 60175;           // SF0.01 lineitem, /root/reference/tests/tpchnoorder/bounds.csv:59
     uint64_t seed = 0x5EED0006ULL;
-    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0;
+    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, encode = 0;
     std::string data_dir, shard = "lineitem";
 };
 
@@ -177,12 +185,14 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
     if (o.describe) { std::fputs(vdl_plan_describe(plan), stdout); return 0; }
     int64_t row0 = 0;
     if (!o.data_dir.empty()) {
-        if (load_data_dir(ctx, o.data_dir, text, o.shard, rank, world, &row0)) return 1;
+        if (load_data_dir(ctx, o.data_dir, text, o.shard, rank, world, &row0, o.encode != 0)) return 1;
     } else {
         row0 = o.rows * rank / world;
         const int64_t mine = o.rows * (rank + 1) / world - row0;
         for (const GenSpec &g : kLineitem)
             if ((rc = vdl_generate_column(ctx, g.name, g.width, row0, mine, o.seed, g.lo, g.hi, g.mul, g.add))) return die(ctx, "vdl_generate_column", rc);
+        if (o.encode)
+            for (const GenSpec &g : kLineitem) if ((rc = vdl_encode_column(ctx, g.name))) return die(ctx, "vdl_encode_column", rc);
     }
     if (comm_dir.empty()) {
         if ((rc = vdl_run(ctx, plan))) return die(ctx, "vdl_run", rc);
@@ -214,6 +224,11 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
         if ((rc = vdl_run_sharded(ctx, plan))) return die(ctx, "vdl_run_sharded", rc);
     }
     collect(plan, reply);
+    if (o.encode && rank == 0) {
+        const char *list = "";
+        vdl_plan_image_columns(plan, &list);
+        std::fprintf(stderr, "vdlrun: images: %s\n", list);
+    }
     vdl_plan_free(plan);
     vdl_close(ctx);
     return 0;
@@ -232,11 +247,12 @@ int main(int argc, char **argv) {
         else if (a == "--shard" && i + 1 < argc) o.shard = argv[++i];
         else if (a == "--no-fuse") o.fuse = 0;
         else if (a == "--jit") o.jit = 1;
+        else if (a == "--encode") o.encode = 1;
         else if (a == "--jit-tune") o.jit = 2;
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--encode] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }

@@ -120,6 +120,7 @@ def register_q3_columns(engine, n_orders, li_rows=None, device="cuda", seed=SEED
     copartition=True keeps only the orders rows the lineitem shard references (lineitem is clustered by order, so
     that is one contiguous range) and rebases the join index to it: the co-located placement of a sharded star
     schema, under which no rank repeats the orders-side work of another.
+    The registered join index and l_orderkey are encoded (Engine.encode) like the generated columns.
     Returns the tensors that back the registered columns (keep them alive while the engine uses them)."""
     import torch
 
@@ -145,6 +146,10 @@ def register_q3_columns(engine, n_orders, li_rows=None, device="cuda", seed=SEED
     reg("lineitem.lineitem_orders", lo - o0)
     reg("lineitem.l_orderkey", (1 + (lo // 8) * 32 + (lo % 8)).to(torch.int32))
     torch.cuda.synchronize()
+    # the registered lineitem columns get their frame-of-reference images too (the generated ones have them already), so the
+    # front reads the join index narrow; the tensors are not written again
+    engine.encode("lineitem.lineitem_orders")
+    engine.encode("lineitem.l_orderkey")
     return keep
 
 

@@ -77,6 +77,13 @@ class Plan:
         self._e._check(self._e._L.vdl_plan_jit_check(self._e._c, self._h))
         return self.jit_note()
 
+    def image_columns(self):
+        """{role: {catalog column: image width}} of the scans as bound at the last run or jit_check (vdl.h:
+        vdl_plan_image_columns): roles "scan<k>", "front.select", "front.take", "dim<k>", "semi<k>"; roles that read no image are left out."""
+        text = ctypes.c_char_p()
+        self._e._check(self._e._L.vdl_plan_image_columns(self._h, ctypes.byref(text)))
+        return _lib.parse_image_columns((text.value or b"").decode())
+
     def set_trace(self, enabled):
         """Keep a host copy of every statement's vector (statement-by-statement runs only): see `traced()`."""
         self._e._check(self._e._L.vdl_plan_set_trace(self._h, int(bool(enabled))))
