@@ -295,28 +295,35 @@ static uint64_t staged_columns(vdl_ctx *c, const MScanCols &cols, const MScanDes
     *lazy_mask = lazy;
     return stages;
 }
+// The arguments of a scan's specialised form `lazy` (0: every column with the tile; 1, 2, 4: staged; 3: the queue form), or false
+// and why the form does not exist for this scan.  The tuner (build_specialised) and vdl_plan_jit_check refuse the same forms for
+// the same reasons.
+static bool specialised_args(vdl_ctx *c, const MScanCols &cols, const MScanDesc &d, bool grouped, int lazy, MsArgs &args, std::string &why) {
+    args = mscan_args(cols);
+    if (!lazy) return true;
+    args.stages = staged_columns(c, cols, d, grouped, &args.lazy, eager_filters_of(lazy));
+    if (!args.lazy) { why = "no column to read late"; return false; }
+    if (lazy == 3) {
+        // the queue form: the most selective filter column with the tile, EVERY other table column for the queued rows
+        int eager = 0;
+        for (int k = 0; k < cols.ncol; k++) {
+            if (cols.kind[k] != VC_DIRECT) continue;
+            if (!((args.lazy >> k) & 1u)) { eager++; if (!cols.filtered[k]) { why = "a column that is no filter would come with the tile"; return false; } }
+        }
+        if (eager != 1) { why = "the queue form wants exactly one filter column with the tile"; return false; }
+        args.queued = 1;
+        args.stages = 0;
+    }
+    return true;
+}
 static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, int u, int lazy /* 0 | eager filter columns of the staged form */, Specialised &out, std::string &why,
                               bool census = false) {
     jit::Shape sh = jit_shape(p->mcols[s], p->mcfg[s]);
     if (u > 0) sh.u = u;
     sh.census = census;
     std::vector<char> code;
-    MsArgs args = mscan_args(p->mcols[s]);
-    if (lazy) {
-        args.stages = staged_columns(c, p->mcols[s], p->mdesc[s], grouped, &args.lazy, eager_filters_of(lazy));
-        if (!args.lazy) { why = "no column to read late"; return false; }
-        if (lazy == 3) {
-            // the queue form: the most selective filter column with the tile, EVERY other table column for the queued rows
-            int eager = 0;
-            for (int k = 0; k < p->mcols[s].ncol; k++) {
-                if (p->mcols[s].kind[k] != VC_DIRECT) continue;
-                if (!((args.lazy >> k) & 1u)) { eager++; if (!p->mcols[s].filtered[k]) { why = "a column that is no filter would come with the tile"; return false; } }
-            }
-            if (eager != 1) { why = "the queue form wants exactly one filter column with the tile"; return false; }
-            args.queued = 1;
-            args.stages = 0;
-        }
-    }
+    MsArgs args;
+    if (!specialised_args(c, p->mcols[s], p->mdesc[s], grouped, lazy, args, why)) return false;
     if (!jit::compile(jit::mscan_source(args, p->mdesc[s], sh), c->arch, code, why)) { why = why.substr(0, 400); return false; }
     // a specialised scan is 10-25 KB of code; ten times that means the compiler did not fold the descriptor (it then sits in
     // scratch memory and every descriptor-driven loop stays): such a build is slower than the precompiled kernel
@@ -1572,9 +1579,13 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
             if (getenv("VDL_JIT_CENSUS")) sh.census = true;              // (tests: the measurement build of a staged scan compiles too)
             std::vector<char> code;
             std::string log;
-            MsArgs args = mscan_args(cols);
-            if (getenv("VDL_JIT_LATE")) args.stages = staged_columns(c, cols, *d, grouped, &args.lazy, eager_filters_of(std::max(1, atoi(getenv("VDL_JIT_LATE")))));      // the staged form of the same scan
-            if (getenv("VDL_JIT_LATE") && atoi(getenv("VDL_JIT_LATE")) == 3 && args.lazy) { args.queued = 1; args.stages = 0; }   // ... or its queue form
+            // the staged or queue form of the same scan (VDL_JIT_LATE as in specialise_scan), refused where the tuner refuses it
+            const int late = getenv("VDL_JIT_LATE") ? std::max(1, atoi(getenv("VDL_JIT_LATE"))) : 0;
+            MsArgs args;
+            if (!specialised_args(c, cols, *d, grouped, late, args, log)) {
+                p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + log + "); ";
+                continue;
+            }
             if (!jit::compile(jit::mscan_source(args, *d, sh), c->arch, code, log))
                 throw Error(VDL_ERR_UNSUPPORTED, "scan " + std::to_string(s) + " does not build: " + log.substr(0, 2000));
             p->jit_note += "scan " + std::to_string(s) + ": " + jit_name(sh, cols.image != 0) + (args.queued ? " (queue)" : args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";

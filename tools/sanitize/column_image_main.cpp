@@ -68,6 +68,21 @@ int main() {
         {8, -1000000000000000000ll, 1000000000000000000ll, 18, 1, -1000000000000000000ll, 1000000000000000000ll},
         {8, 5, 5 + 127 * 1000, 3, 1, 5, 1000},
         {8, 5, 5 + 128 * 1000, 3, 2, 5, 1000},                    // one past the int8 range
+        // the width limits exactly, at both ends of int64
+        {4, -32768, 32767, 0, 2, 0, 1},                           // int16's range stored in 4 bytes: a pure narrowing
+        {8, -32769, 32767, 0, 4, 0, 1},                           // one below it
+        {8, -128, 127, 0, 1, 0, 1},
+        {8, -128, 128, 0, 2, 0, 1},
+        {8, INT64_MAX - 3 - 2147483647ll, INT64_MAX - 3, 0, 4, INT64_MAX - 3 - 2147483647ll, 1},   // span 2^31 - 1 near INT64_MAX
+        {8, INT64_MAX - 2147483647ll, INT64_MAX, 0, 4, INT64_MAX - 2147483647ll, 1},               // ... ending on it
+        {8, 1ll << 40, (1ll << 40) + 2147483648ll, 0, 0, 0, 1},   // span 2^31: none
+        {8, INT64_MIN, INT64_MIN + 2147483647ll, 0, 4, INT64_MIN, 1},
+        {8, INT64_MIN, INT64_MIN + 2147483648ll, 0, 0, 0, 1},
+        {8, INT64_MIN, INT64_MIN + 127 * 1000, 3, 1, INT64_MIN, 1000},
+        {8, INT64_MIN, INT64_MIN + 128 * 1000, 3, 2, INT64_MIN, 1000},
+        {8, INT64_MIN, INT64_MIN + 30000ll * 1000, 3, 2, INT64_MIN, 1000},
+        {8, -(1ll << 62) + 7, -(1ll << 62) + 7 + 127 * 1000, 3, 1, -(1ll << 62) + 7, 1000},
+        {8, -(1ll << 62) + 7, -(1ll << 62) + 7 + 128 * 1000, 3, 2, -(1ll << 62) + 7, 1000},
     };
     for (const C &t : cases) {
         const img::Image im = img::choose(t.stored, t.mn, t.mx, t.p);
@@ -107,8 +122,19 @@ int main() {
                 if ((__int128)base + (__int128)im.scale * img::width_min(w) < INT64_MIN) continue;
                 ims.push_back(im);
             }
+    // images that start at INT64_MIN or end at INT64_MAX (their encoded values are >= 0: the negative half of the width lies
+    // outside int64 and is never stored)
+    for (int w : {1, 2, 4})
+        for (int p : {0, 3}) {
+            img::Image lo; lo.width = w; lo.base = INT64_MIN; lo.scale = img::pow10(p);
+            ims.push_back(lo);
+            img::Image hi; hi.width = w; hi.scale = img::pow10(p); hi.base = (int64_t)((__int128)INT64_MAX - (__int128)hi.scale * img::width_max(w));
+            ims.push_back(hi);
+        }
     for (const img::Image &im : ims) {
-        std::vector<int64_t> ends = {INT64_MIN, INT64_MAX, INT64_MIN + 1, INT64_MAX - 1, 0, -1, 1, im.base, im.base - 1, im.base + 1};
+        std::vector<int64_t> ends = {INT64_MIN, INT64_MAX, INT64_MIN + 1, INT64_MAX - 1, 0, -1, 1, im.base};
+        if (im.base > INT64_MIN) ends.push_back(im.base - 1);
+        if (im.base < INT64_MAX) ends.push_back(im.base + 1);
         for (int64_t e : {img::width_min(im.width), img::width_max(im.width), (int64_t)0, (int64_t)-1, (int64_t)1, (int64_t)22, (int64_t)-23}) {
             const __int128 v = value(im, e);
             for (int d : {-1, 0, 1}) { const __int128 x = v + d; if (x >= INT64_MIN && x <= INT64_MAX) ends.push_back((int64_t)x); }
