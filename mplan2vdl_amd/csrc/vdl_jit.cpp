@@ -180,6 +180,12 @@ void cache_write(const std::string &path, const std::string &src, const std::vec
     if (!ok) unlink(tmp.c_str());
 }
 
+// VDL_JIT_BRANCHY_LATE=1 (A/B profiles): the staged forms' masked late loads as branches around plain loads, as before buffer loads
+bool branchy_late() {
+    const char *e = getenv("VDL_JIT_BRANCHY_LATE");
+    return e && atoi(e) != 0;
+}
+
 }  // namespace
 
 // the descriptor as constexpr functions: only what differs from the defaults is written
@@ -257,10 +263,22 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
               << " const uint64_t f_ = __ballot(first_); if (ln_ == 0) census_cnt[" << c << "] += (unsigned long long)__popcll(f_); }";
             return l.str();
         };
+        // (VDL_JIT_BRANCHY_LATE=1: the masked loads as branches, the form before buffer loads -- for profiles that compare the two)
+        const bool branchy = branchy_late();
         auto load = [&](int c, const char *mask) {
             std::ostringstream l;
             const int w = C.width(c);
-            if (pairs) {
+            if (pairs && !branchy) {
+                // one buffer resource per column over the rows of the lane's tile (built from wave-uniform values: tile0, tile_rows);
+                // a pair of which no row is in passes an offset past it and asks memory for nothing -- no branch, so a row slice's
+                // late loads go out together (vdl_mscan_body.h buf_load_pair).  The partial tile's last row has no partner: the
+                // scalar form reads it (rows_left is a constant in full tiles, where that code folds away).
+                l << " if (RW % 2 == 0) { const __amdgpu_buffer_rsrc_t rs_ = buf_rsrc((const char *)Cr.ptr[" << c << "] + tile0 * " << w << ", (uint32_t)(tile_rows * " << w
+                  << ")); _Pragma(\"unroll\") for (int r = 0; r < RW; r += 2) { const int r1 = r + 1 < RW ? r + 1 : r;" << census(c, w, (std::string(mask) + "[r] | " + mask + "[r1]").c_str())
+                  << " const bool two_ = (int64_t)((r >> 1) * (kMsBlock * 2)) + 1 < rows_left; buf_load_pair<" << w << ">(rs_, (" << mask << "[r] | " << mask
+                  << "[r1]) & two_, (uint32_t)(rowid[r] - Cr.row0 - tile0) * " << w << "u, v[" << c << "][r], v[" << c << "][r1]); if (!two_ && " << mask << "[r]) v[" << c
+                  << "][r] = load_scalar(Cr.ptr[" << c << "], " << w << ", rowid[r] - Cr.row0); } } else {";
+            } else if (pairs) {
                 const char *vt = w == 8 ? "ll2" : w == 4 ? "i32x2" : w == 2 ? "i16x2" : "i8x2";
                 l << " if (RW % 2 == 0) { _Pragma(\"unroll\") for (int r = 0; r < RW; r += 2) { const int r1 = r + 1 < RW ? r + 1 : r; v[" << c << "][r] = 0; v[" << c
                   << "][r1] = 0;" << census(c, w, (std::string(mask) + "[r] | " + mask + "[r1]").c_str()) << " if (" << mask << "[r] | " << mask << "[r1]) { const int64_t i0 = rowid[r] - Cr.row0; if (i0 + 1 < Cr.n) { const " << vt << " x = *(const " << vt

@@ -44,6 +44,34 @@ __device__ __forceinline__ int64_t load_scalar(const void *p, int width, int64_t
     default: return ((const int8_t *)p)[i];
     }
 }
+// Masked loads without branches.  `if (on) v = *p` makes the compiler branch around the load and wait for it inside the branch
+// (vmcnt(0): every load in flight, the tile's included), so a row slice's late loads became serial round trips.  A buffer
+// load through a resource of `bytes` bytes from `p` asks memory for nothing and returns 0 where its offset lies past the
+// resource: a lane whose row is out passes kBufOut, and every lane's load issues in one straight line.  `p` and `bytes` must be
+// wave-uniform (the resource lives in scalar registers); offsets are 32 bits, so a resource spans one tile of a column,
+// whatever the size of the column.
+constexpr uint32_t kBufOut = 0x80000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void *p, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), (short)0, (int)bytes, 0x00020000);
+}
+// an adjacent row pair of width W at byte offset `off` in one load, both 0 where !on
+template <int W>
+__device__ __forceinline__ void buf_load_pair(__amdgpu_buffer_rsrc_t rs, bool on, uint32_t off, int64_t &a, int64_t &b) {
+    const int o = (int)(on ? off : kBufOut);
+    if (W == 8) {
+        const auto x = __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 0);
+        a = (int64_t)(((uint64_t)x[1] << 32) | x[0]); b = (int64_t)(((uint64_t)x[3] << 32) | x[2]);
+    } else if (W == 4) {
+        const auto x = __builtin_amdgcn_raw_buffer_load_b64(rs, o, 0, 0);
+        a = (int32_t)x[0]; b = (int32_t)x[1];
+    } else if (W == 2) {
+        const uint32_t x = __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0);
+        a = (int16_t)(x & 0xffffu); b = (int16_t)(x >> 16);
+    } else {
+        const uint32_t x = __builtin_amdgcn_raw_buffer_load_b16(rs, o, 0, 0);
+        a = (int8_t)(x & 0xffu); b = (int8_t)(x >> 8);
+    }
+}
 // a value read from a column image (vdl_column_image.h) as the column holds it: base + scale * e, in wrapping 64-bit arithmetic
 __device__ __forceinline__ int64_t img_decode(int64_t e, int64_t base, int64_t scale) {
     return (int64_t)((uint64_t)base + (uint64_t)scale * (uint64_t)e);
@@ -426,7 +454,10 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
     }
     __syncthreads();
 
-    auto process = [&](auto rows_tag, int64_t (&v)[NC][decltype(rows_tag)::value], const int64_t (&rowid)[decltype(rows_tag)::value], int64_t rows_left, auto staged_tag) {
+    // tile0, tile_rows: the first row (an index into the columns) and the rows of the tile the lane's rows lie in -- wave-uniform, the
+    // generated late loads build their buffer resources from them
+    auto process = [&](auto rows_tag, int64_t (&v)[NC][decltype(rows_tag)::value], const int64_t (&rowid)[decltype(rows_tag)::value], int64_t rows_left, auto staged_tag,
+                       int64_t tile0, int64_t tile_rows) {
         constexpr int RW = decltype(rows_tag)::value;
         bool pass[RW];
         // Staged reads (STAGED: specialised builds, when the tuner found them quicker): only the most selective filter column comes
@@ -646,7 +677,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
                         v1[c][0] = 0;
                         if (c < C.ncol && !((C.derived >> c) & 1u)) v1[c][0] = load_scalar(Cr.ptr[c], C.width(c), rid[0] - Cr.row0);
                     }
-                    process(IntTag<1>{}, v1, rid, 1, IntTag<0>{});
+                    process(IntTag<1>{}, v1, rid, 1, IntTag<0>{}, 0, 0);
                 }
                 head = (head + k) & (QCAP - 1);
                 held -= k;
@@ -662,7 +693,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
 #pragma unroll
         for (int u = 0; u < U; u++) { rowid[2 * u] = Cr.row0 + base + (int64_t)u * (BS * 2); rowid[2 * u + 1] = rowid[2 * u] + 1; }
         load_tile<NC, U, VEC, NT>(C, Cr, base, v, STAGED ? C.lazy : 0u);
-        process(IntTag<ROWS>{}, v, rowid, (int64_t)1 << 40, IntTag<1>{});
+        process(IntTag<ROWS>{}, v, rowid, (int64_t)1 << 40, IntTag<1>{}, tile * TILE, (int64_t)TILE);
     }
     if (blockIdx.x == gridDim.x - 1 && ntiles * TILE < Cr.n) {
         if (DER) {
@@ -681,7 +712,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
                     }
                 }
             }
-            process(IntTag<ROWS>{}, v, rowid, Cr.n - base, IntTag<1>{});
+            process(IntTag<ROWS>{}, v, rowid, Cr.n - base, IntTag<1>{}, ntiles * TILE, Cr.n - ntiles * TILE);
         } else {
             for (int64_t i = ntiles * TILE + tid; i < Cr.n; i += BS) {      // tail rows, one per lane
                 int64_t v1[NC][1], rid[1];
@@ -689,7 +720,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
 #pragma unroll
                 for (int c = 0; c < NC; c++)
                     if (c < C.ncol) v1[c][0] = load_scalar(Cr.ptr[c], C.width(c), i);
-                process(IntTag<1>{}, v1, rid, 1, IntTag<1>{});
+                process(IntTag<1>{}, v1, rid, 1, IntTag<1>{}, i, 1);
             }
         }
     }
