@@ -164,11 +164,42 @@ int  vdl_output(const vdl_plan *plan, int k, const char **name, const char **tmp
  * host: vdl_output reports its length with *vals == NULL and vdl_output_device hands out the device pointer (int64
  * values, owned by the plan until it is run again or freed; the run has completed on the context's stream when
  * vdl_run returns).  Smaller outputs stay host-side (*dev_vals == NULL).  Q3 at SF100 returns 4 x 13.9M values:
- * 445 MB over PCIe is a quarter of the run. */
+ * 445 MB over PCIe is a quarter of the run (vdl_plan_set_order with the query's own LIMIT is the way not to make that copy). */
 int  vdl_plan_set_device_outputs(vdl_plan *plan, int enabled);
 int  vdl_output_device(const vdl_plan *plan, int k, const int64_t **dev_vals, size_t *n);
 int  vdl_n_timings(const vdl_plan *plan);
 int  vdl_timing(const vdl_plan *plan, int k, const char **label, double *usec);
+
+/* ---- ordered and top-N results: ORDER BY / LIMIT -------------------------------------------------------------------
+ * The plans this engine runs were compiled with the ORDER BY and LIMIT of their SQL cut off (the reference compiler stops
+ * at an ORDER BY list and never lowers `top N`), so a run hands back every result row in program order.  An order set on
+ * the plan makes vdl_run deliver the same outputs, all of them permuted by ONE permutation and cut to the limit, computed
+ * where the rows are: on the device for everything a MaterializeCompact produces there (Q3's 4 x 13.9M values at SF100 never
+ * leave HBM: 4 x 10 do), on the host for the handful of rows a fused plan assembles there.
+ *   - keys are compared as signed int64, key by key in the order given, each ascending (descending[k] = 0) or descending;
+ *   - rows equal on every key stay in the order of the unordered result (ties are broken by the row's position, ascending):
+ *     the order is total and equals numpy's lexsort with the position as the last key;
+ *   - a key is ordered by the int64 the engine holds for it.  For decimals and dates that is the SQL order.  A string field
+ *     is its dictionary code (a heap offset, dictionary.csv): ordering by one groups equal strings but is NOT alphabetical --
+ *     ordering by the text belongs to the decoding side (resolve.py);
+ *   - limit 0 = all rows; limit L > 0 = the first min(L, m) rows of that order.  No keys and L > 0 = the first L rows in program
+ *     order.  No keys and limit 0 clears the order: the plan runs as if none had ever been set.
+ * A key names an output by its full field name (the `name` of vdl_output, e.g. "o_orderdate__orders__o_orderdate") or by its
+ * "tmpN" key.  An unknown name, a name given twice, more than 8 keys or a negative limit: VDL_ERR_ARG (no device, no run needed:
+ * the outputs are known from the program text).  At run time all outputs must have one length m (they are the columns of one
+ * result), VDL_ERR_SHAPE names outputs and lengths otherwise; m = 0 is fine.  With vdl_plan_set_device_outputs the 65536 rule
+ * applies to the ordered, cut outputs.  Sharded runs (vdl_run_sharded*, vdl_run_local, vdl_exchange_begin) refuse a plan with an
+ * order set, VDL_ERR_UNSUPPORTED: the ranks hold disjoint result rows and the merge of per-rank top-N is not built.
+ * With an order set the timings carry one more entry, "timeInMicrosecondsForOrder": device events around the order step (the
+ * host's own time where the step ran on the host). */
+int  vdl_plan_set_order(vdl_plan *plan, int n_keys, const char *const *fields, const int *descending, int64_t limit);
+/* After a run, what the order step did: "host m=.. rows=..", "topn m=.. rows=.. rounds=.. candidates=.. digits_used_up=0|1"
+ * (selection rounds run, candidate rows the final step ordered) or "sort m=.. rows=.. partitions=..".  "" when no order is set. */
+const char *vdl_plan_order_note(const vdl_plan *plan);
+/* The host formulation of exactly that order, device-free: index_out[r] = position of the row of rank r, for r < min(limit or m, m).
+ * keys[k] points to m int64.  What the engine itself uses for results that lie on the host. */
+int  vdl_order_host(int n_keys, const int64_t *const *keys, const int *descending, int64_t m, int64_t limit, int64_t *index_out);
+
 
 /* Debugging aid for parity work.  With tracing on, a vdl_run that goes statement by statement (plan not fused, or
  * vdl_plan_set_fusion(plan, 0)) keeps a host copy of every statement's vector as it stood right after the statement:

@@ -925,6 +925,7 @@ int vdl_plan_sharded_route(vdl_ctx *c, vdl_plan *p, const char **route, int *rep
 int vdl_run_sharded_begin(vdl_ctx *c, vdl_plan *p, int slot) {
     if (!c || !p) return VDL_ERR_ARG;
     return guard(c, [&] {
+        refuse_order_sharded(p);
         if (!fold_route(c, p)) throw Error(VDL_ERR_UNSUPPORTED, "vdl_run_sharded_begin serves plans whose outputs are folds (partial words); plans with a "
                                                                "Partition exchange rows and run through vdl_run_sharded");
         sharded_begin(c, p, slot);
@@ -940,6 +941,7 @@ int vdl_run_sharded_end(vdl_ctx *c, vdl_plan *p, int slot) {
 
 int vdl_run_sharded(vdl_ctx *c, vdl_plan *p) {
     if (!c || !p) return VDL_ERR_ARG;
+    if (const int rc = guard(c, [&] { refuse_order_sharded(p); })) return rc;
     if (p->use_fusion && p->fused.ok) {                       // a fused plan with a semi-join set: the sets are merged across the ranks
         bool semi = false;
         for (const PreludeItem &it : p->fused.prelude) semi |= it.kind == PreludeItem::SEMI_BITMAP;

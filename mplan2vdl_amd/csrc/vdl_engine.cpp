@@ -5,6 +5,8 @@
 //               per table (vdl_fuse.cpp decides, k_scan executes);
 //   * general : any other program runs statement by statement with one kernel per operator;
 //               RangeV/RangeC, Project, Shuffle and identity Gathers never touch memory.
+#include <chrono>
+
 #include "vdl_genexec.h"
 
 namespace {
@@ -967,6 +969,48 @@ void finalize_end(vdl_ctx *c, vdl_plan *p, int slot) {
 namespace vdl {
 namespace eng {
 
+// ---- the order step on the host ----------------------------------------------------------------------------------------------
+int64_t order_resolve(const vdl_plan *p, std::vector<size_t> &keys) {
+    int64_t m = p->outs.empty() ? 0 : (int64_t)p->outs[0].count();
+    bool same = true;
+    for (const Output &o : p->outs) same = same && (int64_t)o.count() == m;
+    if (!same) {
+        std::string all;
+        for (const Output &o : p->outs) all += (all.empty() ? "" : ", ") + o.name + " (" + o.tmp + "): " + std::to_string(o.count());
+        throw Error(VDL_ERR_SHAPE, "an order is set, but the outputs are not the columns of one result; their lengths: " + all);
+    }
+    keys.clear();
+    for (int node : p->order.nodes) {
+        size_t at = p->outs.size();
+        for (size_t k = 0; k < p->outs.size(); k++) if (p->outs[k].node == node) { at = k; break; }
+        if (at == p->outs.size()) throw Error(VDL_ERR_SHAPE, "an order is set, but its key tmp" + std::to_string(node) + " is not among the outputs of this run");
+        keys.push_back(at);
+    }
+    return m;
+}
+void order_outputs_on_host(vdl_plan *p) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<size_t> keys;
+    const int64_t m = order_resolve(p, keys);
+    const int64_t L = p->order.limit > 0 ? std::min<int64_t>(p->order.limit, m) : m;
+    std::vector<const int64_t *> kp;
+    for (size_t k : keys) kp.push_back(p->outs[k].ptr());
+    std::vector<int64_t> index((size_t)L);
+    const int rc = vdl_order_host((int)kp.size(), kp.data(), p->order.desc.data(), m, p->order.limit, index.data());
+    if (rc != VDL_OK) throw Error(rc, "vdl_order_host failed");
+    for (Output &o : p->outs) {
+        const int64_t *src = o.ptr();
+        std::vector<int64_t> cut((size_t)L);
+        for (int64_t i = 0; i < L; i++) cut[(size_t)i] = src[index[(size_t)i]];
+        o.vals.swap(cut);
+        o.big = nullptr; o.big_n = 0;
+    }
+    p->order_note = "host m=" + std::to_string(m) + " rows=" + std::to_string(L);
+    // (no device work: the entry is the host's own time for the step)
+    p->timings.push_back({"timeInMicrosecondsForOrder", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count()});
+}
+
+
 // The fused front of a plan that does not fuse as a whole (ProjPlan, vdl_fuse.h): one scan over the fact table -- two
 // passes: count per tile, then write -- produces the statements of `proj.nodes` as SPARSE vectors on one shared selection;
 // the per-operator executor starts from them (`over`).  false: the plan has no such front (or it is switched off).
@@ -1592,6 +1636,58 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
         }
     });
 }
+// ---- ORDER BY / LIMIT (vdl_plan_set_order) -----------------------------------------------------------------------------------
+int vdl_order_host(int n_keys, const int64_t *const *keys, const int *descending, int64_t m, int64_t limit, int64_t *index_out) {
+    if (n_keys < 0 || n_keys > kOrdMaxKeys || m < 0 || limit < 0 || (n_keys > 0 && (!keys || !descending)) || (m > 0 && !index_out)) return VDL_ERR_ARG;
+    for (int k = 0; k < n_keys; k++) if (!keys[k] && m > 0) return VDL_ERR_ARG;
+    const int64_t L = limit > 0 ? std::min(limit, m) : m;
+    try {
+        // u = key ^ flip: signed order as unsigned order, complemented when descending (no negation: INT64_MIN has none)
+        uint64_t flip[kOrdMaxKeys];
+        for (int k = 0; k < n_keys; k++) flip[k] = descending[k] ? kOrdFlipDesc : kOrdFlipAsc;
+        auto before = [&](int64_t a, int64_t b) {
+            for (int k = 0; k < n_keys; k++) {
+                const uint64_t ua = (uint64_t)keys[k][a] ^ flip[k], ub = (uint64_t)keys[k][b] ^ flip[k];
+                if (ua != ub) return ua < ub;
+            }
+            return a < b;                                 // ties: the position decides, so the order is total
+        };
+        if (n_keys == 0) { for (int64_t i = 0; i < L; i++) index_out[i] = i; return VDL_OK; }
+        std::vector<int64_t> idx((size_t)m);
+        for (int64_t i = 0; i < m; i++) idx[(size_t)i] = i;
+        if (L < m) std::partial_sort(idx.begin(), idx.begin() + L, idx.end(), before);
+        else std::sort(idx.begin(), idx.end(), before);
+        std::copy(idx.begin(), idx.begin() + L, index_out);
+    } catch (const std::bad_alloc &) { return VDL_ERR_NOMEM; }
+    return VDL_OK;
+}
+
+int vdl_plan_set_order(vdl_plan *p, int n_keys, const char *const *fields, const int *descending, int64_t limit) {
+    if (!p) return VDL_ERR_ARG;
+    auto fail = [&](const std::string &why) { if (p->ctx) p->ctx->err = "vdl_plan_set_order: " + why; return (int)VDL_ERR_ARG; };
+    if (n_keys < 0) return fail("negative number of keys");
+    if (n_keys > kOrdMaxKeys) return fail(std::to_string(n_keys) + " keys given, at most " + std::to_string(kOrdMaxKeys) + " are supported");
+    if (limit < 0) return fail("negative limit " + std::to_string(limit));
+    if (n_keys > 0 && (!fields || !descending)) return fail("keys without fields / directions");
+    vdl_plan::OrderSpec spec;
+    for (int k = 0; k < n_keys; k++) {
+        const std::string f = fields[k] ? fields[k] : "";
+        int node = -1;
+        for (int id : p->prog.outputs)
+            if (p->prog.at(id).field == f || "tmp" + std::to_string(id) == f) { node = id; break; }
+        if (node < 0) return fail("'" + f + "' is not an output of this plan (outputs are named by their full field name or their tmpN key)");
+        if (std::find(spec.nodes.begin(), spec.nodes.end(), node) != spec.nodes.end()) return fail("'" + f + "' is given twice");
+        spec.nodes.push_back(node);
+        spec.desc.push_back(descending[k] != 0);
+    }
+    spec.limit = limit;
+    spec.set = n_keys > 0 || limit > 0;
+    p->order = spec;
+    p->order_note.clear();
+    return VDL_OK;
+}
+const char *vdl_plan_order_note(const vdl_plan *p) { return p ? p->order_note.c_str() : ""; }
+
 int vdl_plan_set_device_outputs(vdl_plan *p, int enabled) {
     if (!p) return VDL_ERR_ARG;
     p->device_outputs = enabled != 0;
@@ -1631,6 +1727,7 @@ int vdl_run(vdl_ctx *c, vdl_plan *p) {
     if (!c || !p) return VDL_ERR_ARG;
     return guard(c, [&] {
         need_device(c);
+        p->order_note.clear();
         if (p->use_fusion && p->fused.ok) {
             const int64_t nw = plan_words(p, nullptr, nullptr);
             if (!p->words || p->words_cap < nw) { p->words = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(nw, 1)); p->words_cap = nw; }
@@ -1638,6 +1735,7 @@ int vdl_run(vdl_ctx *c, vdl_plan *p) {
                 run_fused_local(c, p, (int64_t *)p->words->p, true);
                 finalize_begin(c, p, (const int64_t *)p->words->p, 0);
                 finalize_end(c, p, 0);
+                if (p->order.set) order_outputs_on_host(p);     // a fused plan's outputs are assembled on the host: a handful of rows
                 return;
             } catch (const NeedGeneralPath &e) {
                 p->fallback_note = e.what();          // exact for any data: rerun statement by statement
@@ -1652,6 +1750,7 @@ int vdl_run(vdl_ctx *c, vdl_plan *p) {
             p->after_front(c, p, over, front, failure);
         } else front = run_projection(c, p, over);
         GenExec g(c, p);
+        g.ordering = p->order.set;
         g.run_nodes(p->prog.outputs, front ? &over : nullptr);
         if (front) p->timings.push_back({p->front_note, p->front_usec});
         if (!p->fallback_note.empty()) { p->timings.push_back({"fusedPlanAbandoned: " + p->fallback_note, 0.0}); p->fallback_note.clear(); }
@@ -1725,6 +1824,7 @@ int vdl_plan_partial_spec(const vdl_plan *p, int64_t *n_words, const int32_t **r
 int vdl_run_local(vdl_ctx *c, vdl_plan *p, void *dev_partials) {
     if (!c || !p || !dev_partials) return VDL_ERR_ARG;
     return guard(c, [&] {
+        refuse_order_sharded(p);
         need_device(c);
         if (!(p->use_fusion && p->fused.ok)) { general_run_local(c, p, (int64_t *)dev_partials); return; }
         bool shardable = true;

@@ -245,6 +245,15 @@ struct vdl_plan {
     std::vector<Traced> traced;
     hipEvent_t stmt_ev[2] = {nullptr, nullptr};   // per-statement profiling of the per-operator executor (created on first use)
     bool device_outputs = false;
+    // vdl_plan_set_order: the outputs of vdl_run come back permuted by one order and cut to the limit (vdl_genexec.h "order step")
+    struct OrderSpec {
+        bool set = false;
+        std::vector<int> nodes;          // the key outputs: ids of their MaterializeCompact statements
+        std::vector<int> desc;
+        int64_t limit = 0;
+    } order;
+    std::string order_note;              // what the order step of the last run did
+    hipEvent_t order_ev[2] = {nullptr, nullptr};
     std::string description;
     std::vector<Output> outs;
     std::vector<Timing> timings;
@@ -368,6 +377,7 @@ struct vdl_plan {
     ~vdl_plan() {
         for (auto &b : out_pinned) if (b.first) (void)hipHostFree(b.first);
         for (hipEvent_t e : stmt_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : order_ev) if (e) (void)hipEventDestroy(e);
         for (int k = 0; k < 2; k++) {
             if (ev0[k]) (void)hipEventDestroy(ev0[k]);
             if (ev1[k]) (void)hipEventDestroy(ev1[k]);
@@ -432,6 +442,16 @@ inline const Column &find_col(vdl_ctx *c, const std::string &name) {
 }
 
 std::string describe_plan(const vdl_plan *p);
+// sharded entry points refuse a plan with an order set
+inline void refuse_order_sharded(const vdl_plan *p) {
+    if (p->order.set)
+        throw Error(VDL_ERR_UNSUPPORTED, "an order is set on this plan (vdl_plan_set_order): in a sharded run the ranks hold disjoint result rows, and the merge of "
+                                         "per-rank top-N results is not built; run it on one GPU with vdl_run, or clear the order");
+}
+// the order step for results that lie on the host (vdl_engine.cpp): checks the outputs' lengths, vdl_order_host + a permute of every output
+void order_outputs_on_host(vdl_plan *p);
+// the outputs' common length and the key outputs' ordinals, checked (VDL_ERR_SHAPE naming outputs and lengths)
+int64_t order_resolve(const vdl_plan *p, std::vector<size_t> &keys);
 size_t exchange_fold_count(const vdl_plan *p, const std::string &table);      // vdl_exchange.cpp: global folds beside the Partition (sharded runs)
 int exchange_fold_kind(const vdl_plan *p, size_t k);                          // ... 0 sum / count, 1 min, 2 max of the k-th one (after vdl_exchange_begin)
 bool run_projection(vdl_ctx *c, vdl_plan *p, std::map<int, DVec> &over);     // vdl_engine.cpp: the fused front of a plan that does not fuse as a whole

@@ -246,6 +246,7 @@ extern "C" {
 int vdl_exchange_begin(vdl_ctx *c, vdl_plan *p, int world, int64_t *counts_host) {
     if (!c || !p || !counts_host || world < 1 || world > kMaxExWorld) return VDL_ERR_ARG;
     return guard(c, [&] {
+        refuse_order_sharded(p);
         exchange_local(c, p, world);
         exchange_route(c, p, nullptr, counts_host);
     });

@@ -575,7 +575,16 @@ struct GenExec {
     // Result transfers of pinned outputs are queued on the context's copy stream behind the kernels that produced them
     // and overlap the statements that follow; the run waits for them at its end.
     std::vector<BufP> copies_in_flight;
+    bool ordering = false;                  // vdl_run of a plan with an order set: outputs stay where they are until order_outputs()
+    std::vector<BufP> kept;                 // ... their device buffers, by output ordinal
+    size_t out_override = SIZE_MAX;         // order_outputs() copies output `out_override` out after the fact
+    size_t out_ordinal() const { return out_override != SIZE_MAX ? out_override : p->outs.size(); }
     void copy_out(Output &o, const BufP &dev, size_t count) {
+        if (ordering) {
+            kept.resize(out_ordinal() + 1);
+            kept[out_ordinal()] = dev; o.dev = (const int64_t *)dev->p; o.big_n = count;
+            return;
+        }
         if (p->device_outputs && count >= kBigOutput) {  // the caller reads it where it is
             o.dev_keep = dev; o.dev = (const int64_t *)dev->p; o.big_n = count;
             return;
@@ -589,7 +598,7 @@ struct GenExec {
             if (stage && count <= vdl_ctx::kSmallStageWords) {
                 if (stage_used + count > vdl_ctx::kSmallStageWords) flush_small();
                 HIP_CHECK(hipMemcpyAsync(stage + stage_used, dev->p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, s));
-                small_copies.push_back({p->outs.size(), stage_used, count});
+                small_copies.push_back({out_ordinal(), stage_used, count});
                 stage_used += count;
                 return;
             }
@@ -627,7 +636,7 @@ struct GenExec {
     // where the values of an output go on the host: a pinned buffer of the plan when large
     int64_t *host_out(Output &o, size_t count) {
         if (count >= kBigOutput) {
-            int64_t *pin = p->pinned_out(p->outs.size(), count);
+            int64_t *pin = p->pinned_out(out_ordinal(), count);
             if (pin) { o.big = pin; o.big_n = count; return pin; }
         }
         o.vals.resize(count);
@@ -1632,8 +1641,186 @@ struct GenExec {
             for (int opnd : {n.a, n.b, n.c})
                 if (opnd > 0 && last_use[(size_t)opnd] == (int)k) vec[(size_t)opnd] = DVec{};
         }
+        if (ordering) order_outputs();
         HIP_CHECK(hipStreamSynchronize(s));
         finish_copies();
+        if (order_timed) {
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, p->order_ev[0], p->order_ev[1]));
+            p->timings.push_back({"timeInMicrosecondsForOrder", (double)ms * 1e3});
+        }
+    }
+
+    // ---- the order step (vdl_plan_set_order): every output permuted by ONE order over the key outputs and cut to the limit --------
+    // Outputs reach this point where they were produced: in HBM (copy_out kept the buffers) or, for the few a statement assembles on
+    // the host, in Output::vals.  All on the host: vdl_order_host.  Otherwise the index list is computed on the device -- selection
+    // for limits up to kOrdTopMax, a key-by-key sort through the Partition otherwise -- ONE gather writes every output's rows, and
+    // the short buffers take the usual way out (copy_out).  Round trips go through the pinned words (fetch_words).
+    bool order_timed = false;
+    static uint64_t order_flip(int descending) { return descending ? kOrdFlipDesc : kOrdFlipAsc; }
+
+    // the first L rows of the order, L <= kOrdTopMax: an index list of L row numbers
+    BufP order_select(const OrdKeys &K, int64_t m, int64_t L, std::string &note) {
+        const size_t nw = (size_t)std::max<int64_t>(nwords(m), 1);
+        BufP st = dev_alloc(c, sizeof(uint64_t) * kOrdStateWords);
+        HIP_CHECK(hipMemsetAsync(st->p, 0, sizeof(uint64_t) * kOrdStateWords, s));
+        uint64_t *stw = (uint64_t *)st->p;
+        BufP active, below;                                   // rows that match what was chosen so far (null = all) / rows strictly below it
+        int64_t need = L, n_below = 0, boundary = m;
+        int rounds = 0, k = 0;
+        bool used_up = false;
+        while (boundary > kOrdBoundary) {
+            if (k == K.n) { used_up = true; break; }          // every digit of every key chosen: the boundary rows are equal on all keys
+            if (k > 0) HIP_CHECK(hipMemsetAsync(stw, 0, 2 * sizeof(uint64_t), s));
+            HIP_CHECK(launch_order_minmax(K.key[k], K.flip[k], active ? (const uint64_t *)active->p : nullptr, m, stw, s));
+            int64_t mm[2];
+            fetch_words(stw, 2, mm);
+            const uint64_t umin = ~(uint64_t)mm[0], umax = (uint64_t)mm[1];
+            if (umin == umax) { k++; continue; }              // constant over the rows still in: no digit of it decides anything
+            int nbits = 64 - __builtin_clzll(umin ^ umax);    // the bits above are shared: they are the prefix to start from
+            int hi_shift = nbits;
+            uint64_t prefix = nbits < 64 ? umin >> nbits : 0;
+            while (boundary > kOrdBoundary && nbits > 0) {
+                const int shift = std::max(nbits - kOrdDigitBits, 0), width = nbits - shift;
+                HIP_CHECK(launch_order_round(K.key[k], K.flip[k], active ? (const uint64_t *)active->p : nullptr, m, hi_shift, prefix, shift, width, need, stw, s));
+                int64_t r[3];
+                fetch_words(stw + 2, 3, r);
+                if (r[1] < 0 || r[1] >= need || r[2] < need - r[1] || r[2] > boundary) throw Error(VDL_ERR_DEVICE, "internal: order selection round lost count");
+                prefix = (prefix << width) | (uint64_t)r[0];
+                n_below += r[1]; need -= r[1]; boundary = r[2];
+                hi_shift = nbits = shift;
+                rounds++;
+            }
+            if (!below) below = zero_bitmap(m);
+            BufP next = dev_alloc(c, sizeof(uint64_t) * nw);
+            HIP_CHECK(launch_order_close(K.key[k], K.flip[k], active ? (const uint64_t *)active->p : nullptr, m, hi_shift, prefix, (uint64_t *)next->p,
+                                         (uint64_t *)below->p, s));
+            active = next;
+            k++;
+        }
+        // the candidates' row numbers, ascending within each part: the rows strictly below, then the boundary rows (all of them, or --
+        // digits used up -- the first `need` by position, which ARE the answer's tail)
+        const int64_t take = used_up ? need : boundary, nc = n_below + take;
+        BufP cand = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(nc, 1));
+        // (the bitmaps' populations are counted once more by the compaction: they must be what the rounds reported before anything
+        // is written by them)
+        if (n_below > 0) {
+            BufP counts;
+            if (popcount(below, m, &counts) != n_below) throw Error(VDL_ERR_DEVICE, "internal: order selection lost rows below the boundary");
+            HIP_CHECK(launch_compact_write(iota_src(), (const uint64_t *)below->p, m, (const int64_t *)counts->p, (int64_t *)cand->p, s));
+        }
+        {
+            const uint64_t *bits = active ? (const uint64_t *)active->p : nullptr;
+            BufP counts;
+            if (popcount(active, m, &counts) != boundary) throw Error(VDL_ERR_DEVICE, "internal: order selection lost boundary rows");
+            if (take == boundary) HIP_CHECK(launch_compact_write(iota_src(), bits, m, (const int64_t *)counts->p, (int64_t *)cand->p + n_below, s));
+            else {
+                BufP all = dev_alloc(c, sizeof(int64_t) * (size_t)boundary);
+                HIP_CHECK(launch_compact_write(iota_src(), bits, m, (const int64_t *)counts->p, (int64_t *)all->p, s));
+                HIP_CHECK(hipMemcpyAsync((int64_t *)cand->p + n_below, all->p, sizeof(int64_t) * (size_t)take, hipMemcpyDeviceToDevice, s));
+            }
+        }
+        BufP staged = dev_alloc(c, sizeof(uint64_t) * (size_t)std::max<int64_t>(nc * K.n, 1));
+        BufP index = dev_alloc(c, sizeof(int64_t) * (size_t)L);
+        HIP_CHECK(hipMemsetAsync(index->p, 0, sizeof(int64_t) * (size_t)L, s));
+        HIP_CHECK(launch_order_rank(K, (const int64_t *)cand->p, nc, L, (uint64_t *)staged->p, (int64_t *)index->p, s));
+        note = "topn m=" + std::to_string(m) + " rows=" + std::to_string(L) + " rounds=" + std::to_string(rounds) + " candidates=" + std::to_string(nc) +
+               " digits_used_up=" + (used_up ? "1" : "0");
+        return index;
+    }
+
+    // the whole order: stable sorts key by key, last key first, each through the one-sweep Partition on u - min(u); null = the rows are in order as they stand
+    BufP order_sort(const OrdKeys &K, int64_t m, std::string &note) {
+        BufP st = dev_alloc(c, sizeof(uint64_t) * kOrdStateHead);
+        uint64_t *stw = (uint64_t *)st->p;
+        BufP perm;
+        int sorts = 0;
+        for (int k = K.n - 1; k >= 0; k--) {
+            HIP_CHECK(hipMemsetAsync(stw, 0, 2 * sizeof(uint64_t), s));
+            HIP_CHECK(launch_order_minmax(K.key[k], K.flip[k], nullptr, m, stw, s));
+            int64_t mm[2];
+            fetch_words(stw, 2, mm);
+            const uint64_t umin = ~(uint64_t)mm[0], range = (uint64_t)mm[1] - umin;
+            if (range == 0) continue;
+            // the Partition's domain is 63 bits: a wider range is sorted as two 32-bit halves, low half first
+            const bool split = range >= ((uint64_t)1 << 62);
+            for (int half = split ? 1 : 0; half <= (split ? 2 : 0); half++) {
+                const uint64_t top = half == 0 ? range : half == 1 ? 0xffffffffull : range >> 32;
+                BufP t = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+                HIP_CHECK(launch_order_sortkey(K.key[k], K.flip[k], perm ? (const int64_t *)perm->p : nullptr, m, umin, half, (int64_t *)t->p, s));
+                // (at least two radix passes, so that the slots come out in rank order the way every GROUP BY's Partition leaves them)
+                const int64_t pcount = (int64_t)std::max<uint64_t>(top + 1, 512), max_bucket = top + 1 >= 512 ? (int64_t)top : -1;
+                BufP scr = dev_alloc(c, partition_scratch_bytes(m, pcount));
+                BufP nvalid = dev_alloc(c, sizeof(int64_t));
+                BufP ka = dev_alloc(c, sizeof(int64_t) * (size_t)m), sa = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+                BufP kb = dev_alloc(c, sizeof(int64_t) * (size_t)m), sb = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+                BufP order = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+                HIP_CHECK(launch_partition(i64_src(t), nullptr, m, 0, pcount, scr->p, (uint64_t *)ka->p, (int64_t *)sa->p, (uint64_t *)kb->p, (int64_t *)sb->p,
+                                           (int64_t *)nvalid->p, nullptr, s, max_bucket, (int64_t *)order->p, nullptr));
+                if (perm) {
+                    BufP both = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+                    HIP_CHECK(launch_order_compose((const int64_t *)perm->p, (const int64_t *)order->p, m, (int64_t *)both->p, s));
+                    perm = both;
+                } else perm = order;
+                sorts++;
+            }
+        }
+        note = "sort m=" + std::to_string(m) + " rows=@ partitions=" + std::to_string(sorts);
+        return perm;
+    }
+
+    void order_outputs() {
+        ordering = false;
+        std::vector<size_t> keys;
+        const int64_t m = order_resolve(p, keys);
+        const int64_t L = p->order.limit > 0 ? std::min<int64_t>(p->order.limit, m) : m;
+        bool on_device = false;
+        for (const Output &o : p->outs) on_device |= o.dev != nullptr;
+        if (!on_device) { order_outputs_on_host(p); return; }          // (m = 0 included: nothing was kept)
+        kept.resize(p->outs.size());
+        for (size_t k = 0; k < p->outs.size(); k++) {                  // a result a statement assembled on the host joins the others
+            Output &o = p->outs[k];
+            if (o.dev) continue;
+            kept[k] = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+            HIP_CHECK(hipMemcpyAsync(kept[k]->p, o.vals.data(), sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s));                        // (pageable source)
+            o.dev = (const int64_t *)kept[k]->p;
+        }
+        if (!p->order_ev[1]) { HIP_CHECK(hipEventCreate(&p->order_ev[0])); HIP_CHECK(hipEventCreate(&p->order_ev[1])); }
+        HIP_CHECK(hipEventRecord(p->order_ev[0], s));
+        OrdKeys K;
+        K.n = (int)keys.size();
+        for (int k = 0; k < K.n; k++) { K.key[k] = p->outs[keys[(size_t)k]].dev; K.flip[k] = order_flip(p->order.desc[(size_t)k]); }
+        BufP index;                                                    // null: the rows stay in place
+        std::string note = "sort m=" + std::to_string(m) + " rows=@ partitions=0";
+        if (K.n > 0 && m > 1) {
+            if (p->order.limit > 0 && p->order.limit <= kOrdTopMax) index = order_select(K, m, L, note);
+            else index = order_sort(K, m, note);
+        }
+        const size_t at = note.find('@');
+        if (at != std::string::npos) note.replace(at, 1, std::to_string(L));
+        p->order_note = note;
+        std::vector<BufP> cut(p->outs.size());
+        if (index) {
+            for (size_t k0 = 0; k0 < p->outs.size(); k0 += kOrdGatherMax) {       // ONE launch for every plan with at most kOrdGatherMax outputs
+                OrdGather G;
+                for (size_t k = k0; k < p->outs.size() && G.n < kOrdGatherMax; k++, G.n++) {
+                    cut[k] = dev_alloc(c, sizeof(int64_t) * (size_t)L);
+                    G.src[G.n] = p->outs[k].dev; G.dst[G.n] = (int64_t *)cut[k]->p;
+                }
+                HIP_CHECK(launch_order_gather(G, (const int64_t *)index->p, L, s));
+            }
+        } else cut = kept;                                             // the first L rows as they stand
+        HIP_CHECK(hipEventRecord(p->order_ev[1], s));
+        order_timed = true;
+        for (size_t k = 0; k < p->outs.size(); k++) {
+            Output &o = p->outs[k];
+            o.dev = nullptr; o.dev_keep = nullptr; o.big = nullptr; o.big_n = 0; o.vals.clear();
+            out_override = k;
+            copy_out(o, cut[k], (size_t)L);
+        }
+        out_override = SIZE_MAX;
+        kept.clear();
     }
 };
 

@@ -291,4 +291,31 @@ hipError_t launch_ex_route(const ExRoute &R, int64_t *tileoff /* world x ex_rout
 hipError_t launch_ex_pack_all(const ExRoute &R, const ExCols &C, const int64_t *tileoff, const int64_t *counts /* as launch_ex_route left them */, int64_t n_send, int64_t *out, hipStream_t s);
 hipError_t launch_ex_unmask(const int64_t *mask, int64_t n, int j, uint64_t *valid, hipStream_t s);
 
+// ---- ORDER BY / LIMIT over result columns in HBM (vdl_order.hip) ---------------
+// A key's order word is u = key ^ flip: kOrdFlipAsc makes signed ascending = unsigned ascending, kOrdFlipDesc also complements.
+constexpr uint64_t kOrdFlipAsc = 0x8000000000000000ull, kOrdFlipDesc = 0x7fffffffffffffffull;
+constexpr int kOrdMaxKeys = 8;
+constexpr int kOrdDigitBits = 11, kOrdBins = 1 << kOrdDigitBits;      // digit of a selection round
+constexpr int kOrdTopMax = 4096;                                       // limits up to here take the selection, larger ones (and 0) the full sort
+constexpr int kOrdBoundary = 4096;                                     // C: the selection stops once the boundary bin holds at most this many rows
+constexpr int kOrdStateHead = 8, kOrdStateWords = kOrdStateHead + kOrdBins;   // state: [0] max(~u) [1] max(u) [2] bin [3] rows below it [4] rows in it | histogram
+constexpr int kOrdGatherMax = 24;                                      // outputs one gather launch writes
+struct OrdKeys { int n = 0; const int64_t *key[kOrdMaxKeys] = {}; uint64_t flip[kOrdMaxKeys] = {}; };
+struct OrdGather { int n = 0; const int64_t *src[kOrdGatherMax] = {}; int64_t *dst[kOrdGatherMax] = {}; };
+// min / max of u over the rows of `active` (null = all m): state[0] = max(~u), state[1] = max(u); both words zero before the launch
+hipError_t launch_order_minmax(const int64_t *key, uint64_t flip, const uint64_t *active, int64_t m, uint64_t *state, hipStream_t s);
+// one selection round over the rows of `active` whose bits [hi_shift, 64) equal prefix (hi_shift = 64: every row): histogram of bits
+// [shift, shift + width), then state[2..4] = {bin holding the need-th such row, rows in the bins below it, rows in it}; histogram (zero before) zero after
+hipError_t launch_order_round(const int64_t *key, uint64_t flip, const uint64_t *active, int64_t m, int hi_shift, uint64_t prefix, int shift, int width,
+                              int64_t need, uint64_t *state, hipStream_t s);
+// rows of active_in (null = all) with bits [hi_shift, 64) == prefix -> active_out, < prefix -> OR-ed into below ((m + 63) / 64 words each)
+hipError_t launch_order_close(const int64_t *key, uint64_t flip, const uint64_t *active_in, int64_t m, int hi_shift, uint64_t prefix, uint64_t *active_out,
+                              uint64_t *below, hipStream_t s);
+// n <= kOrdTopMax + kOrdBoundary candidate rows `pos`: index_out[r] = the candidate of rank r < keep under (keys, position); staged: K.n * n words
+hipError_t launch_order_rank(const OrdKeys &K, const int64_t *pos, int64_t n, int64_t keep, uint64_t *staged, int64_t *index_out, hipStream_t s);
+hipError_t launch_order_gather(const OrdGather &G, const int64_t *index, int64_t n, hipStream_t s);      // dst[o][i] = src[o][index[i]], i < n
+// full order: out[i] = u(key[perm[i]]) - umin (perm null = identity) whole (half 0) / low 32 bits (1) / high 32 bits (2); out[i] = perm[order[i]]
+hipError_t launch_order_sortkey(const int64_t *key, uint64_t flip, const int64_t *perm, int64_t m, uint64_t umin, int half, int64_t *out, hipStream_t s);
+hipError_t launch_order_compose(const int64_t *perm, const int64_t *order, int64_t m, int64_t *out, hipStream_t s);
+
 }  // namespace vdl

@@ -16,6 +16,10 @@
 // --encode builds the frame-of-reference image of every column it uploads or generates (vdl_encode_column; each rank of its own
 // rows), so that the scans read the narrow copies; after the run one line "vdlrun: images: <vdl_plan_image_columns>" goes to
 // stderr (rank 0's).  The reply on stdout is the same as without it.
+//   ... | vdlrun --order-by revenue:desc,o_orderdate__orders__o_orderdate --limit 10 ...      ORDER BY / LIMIT on the device
+// --order-by FIELD[:asc|:desc],... names outputs by their full field name or their tmpN key, --limit N keeps the first N rows
+// (vdl_plan_set_order): the reply has the same shape with shorter, ordered lists, so resolve.py decodes it untouched.  Not with
+// --gpus: the ranks hold disjoint result rows and the merge of per-rank top-N results is not built.
 #include <signal.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -170,7 +174,33 @@ struct Options {
     uint64_t seed = 0x5EED0006ULL;
     int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, encode = 0;
     std::string data_dir, shard = "lineitem";
+    std::vector<std::string> order_fields;
+    std::vector<int> order_desc;
+    long long limit = 0;
 };
+
+// "a:desc,b,c:asc" -> fields and directions; false = malformed (empty list or field, unknown direction)
+bool parse_order_by(const std::string &list, Options &o) {
+    size_t at = 0;
+    if (list.empty()) return false;
+    for (;;) {
+        const size_t comma = list.find(',', at);
+        std::string item = list.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+        int desc = 0;
+        const size_t colon = item.find(':');
+        if (colon != std::string::npos) {
+            const std::string dir = item.substr(colon + 1);
+            if (dir == "desc") desc = 1;
+            else if (dir != "asc") return false;
+            item.resize(colon);
+        }
+        if (item.empty()) return false;
+        o.order_fields.push_back(item);
+        o.order_desc.push_back(desc);
+        if (comma == std::string::npos) return true;
+        at = comma + 1;
+    }
+}
 
 // one rank of `world` (world = 1 without --gpus: plain vdl_run); comm_dir = where rank 0 leaves the communicator id
 int run_rank(const Options &o, const std::string &text, int rank, int world, const std::string &comm_dir, Reply &reply) {
@@ -182,6 +212,11 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
     vdl_plan_set_fusion(plan, o.fuse);
     vdl_plan_set_profiling(plan, o.profile);
     if (o.jit) vdl_plan_set_jit(plan, o.jit);
+    if (!o.order_fields.empty() || o.limit > 0) {
+        std::vector<const char *> fields;
+        for (const std::string &f : o.order_fields) fields.push_back(f.c_str());
+        if ((rc = vdl_plan_set_order(plan, (int)fields.size(), fields.data(), o.order_desc.data(), o.limit))) return die(ctx, "vdl_plan_set_order", rc);
+    }
     if (o.describe) { std::fputs(vdl_plan_describe(plan), stdout); return 0; }
     int64_t row0 = 0;
     if (!o.data_dir.empty()) {
@@ -245,6 +280,9 @@ int main(int argc, char **argv) {
         else if (a == "--device" && i + 1 < argc) o.device = std::atoi(argv[++i]);
         else if (a == "--gpus" && i + 1 < argc) o.gpus = std::atoi(argv[++i]);
         else if (a == "--shard" && i + 1 < argc) o.shard = argv[++i];
+        else if (a == "--order-by" && i + 1 < argc && parse_order_by(argv[i + 1], o)) i++;
+        else if (a == "--limit" && i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]) &&
+                 std::strlen(argv[i + 1]) <= 18) o.limit = std::atoll(argv[++i]);
         else if (a == "--no-fuse") o.fuse = 0;
         else if (a == "--jit") o.jit = 1;
         else if (a == "--encode") o.encode = 1;
@@ -252,7 +290,7 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--encode] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc],... ] [--limit N] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--encode] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }
@@ -260,6 +298,11 @@ int main(int argc, char **argv) {
     std::string text((std::istreambuf_iterator<char>(std::cin)), std::istreambuf_iterator<char>());
     bool sharded = false;
     for (int i = 1; i < argc; i++) sharded = sharded || std::string(argv[i]) == "--gpus";
+    if (sharded && !o.describe && (!o.order_fields.empty() || o.limit > 0)) {
+        std::fprintf(stderr, "vdlrun: --order-by / --limit are not served with --gpus: the ranks hold disjoint result rows and the merge of per-rank "
+                             "top-N results is not built; run the ordered query on one GPU\n");
+        return 3;
+    }
     if (!sharded || o.describe) {
         Reply r;
         const int rc = run_rank(o, text, 0, 1, "", r);

@@ -109,6 +109,21 @@ class Plan:
         to the plan until its next run."""
         self._e._check(self._e._L.vdl_plan_set_device_outputs(self._h, int(bool(enabled))))
 
+    def set_order(self, keys, limit=0):
+        """ORDER BY / LIMIT on the device: `keys` is a list of (field, descending) pairs (a bare string = ascending), a field
+        being an output's full name or its "tmpN" key; `limit` 0 = all rows.  Every output of `run()` then comes back permuted
+        by that one order (signed int64 keys, ties in the order of the unordered result) and cut to the limit.  No keys and
+        limit 0 clears it.  String fields order by their dictionary code, not alphabetically (include/vdl.h)."""
+        pairs = [(k, False) if isinstance(k, (str, bytes)) else (k[0], bool(k[1])) for k in keys]
+        n = len(pairs)
+        fields = (ctypes.c_char_p * max(n, 1))(*[f.encode() if isinstance(f, str) else f for f, _ in pairs])
+        desc = (ctypes.c_int * max(n, 1))(*[int(d) for _, d in pairs])
+        self._e._check(self._e._L.vdl_plan_set_order(self._h, n, fields, desc, int(limit)))
+
+    def order_note(self):
+        """What the order step of the last run did ("host ...", "topn ...", "sort ..."); "" when no order is set."""
+        return (self._e._L.vdl_plan_order_note(self._h) or b"").decode()
+
     def _collect(self, as_numpy=False):
         L = self._e._L
         results = {}
@@ -232,6 +247,28 @@ class Plan:
         b, detail = ctypes.c_int64(), ctypes.c_char_p()
         self._e._check(self._e._L.vdl_plan_scan_traffic(self._e._c, self._h, ctypes.byref(b), ctypes.byref(detail)))
         return b.value, (detail.value or b"").decode()
+
+
+def order_host(keys, descending, limit=0):
+    """vdl_order_host: the positions of the first `limit` (0 = all) rows under the engine's order -- `keys` a list of equally
+    long int64 arrays compared key by key, `descending` one flag each, ties by position -- as an int64 array.  Needs no GPU."""
+    L = _lib.load()
+    cols = [np.ascontiguousarray(k, dtype=np.int64) for k in keys]
+    if len(cols) != len(list(descending)):
+        raise ValueError("one direction per key")
+    m = len(cols[0]) if cols else 0
+    if any(len(c) != m for c in cols):
+        raise ValueError("keys of different lengths")
+    if not cols and limit > 0:
+        raise ValueError("no keys: the number of rows is unknown")
+    n = len(cols)
+    ptrs = (ctypes.POINTER(ctypes.c_int64) * max(n, 1))(*[c.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) for c in cols])
+    desc = (ctypes.c_int * max(n, 1))(*[int(bool(d)) for d in descending])
+    out = np.empty(min(limit, m) if limit > 0 else m, np.int64)
+    rc = L.vdl_order_host(n, ptrs, desc, m, int(limit), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+    if rc != _lib.VDL_OK:
+        raise VdlError(rc, "vdl_order_host: bad argument")
+    return out
 
 
 class Engine:
