@@ -107,6 +107,14 @@ int  vdl_download_column(vdl_ctx *ctx, const char *name, void *host_ptr, size_t 
 int  vdl_encode_column(vdl_ctx *ctx, const char *name);
 /* width 0: the column has no image; otherwise its width in bytes and v = base + scale * e */
 int  vdl_column_image_info(const vdl_ctx *ctx, const char *name, int *width, int64_t *base, int64_t *scale);
+/* The bit-packed image built beside a byte image: v = base + scale * e' with e' in `bits` bits (1..32) per row, in lane-transposed
+ * stripes of 2048 rows (row 2048 s + 64 j + l is value j of lane l; lane l's values are a bit stream of `bits` dwords, dword k at
+ * dword index (s * bits + k) * 64 + l; zero-padded to whole stripes).  bits 0: the column has none. */
+int  vdl_column_packed_info(const vdl_ctx *ctx, const char *name, int *bits, int64_t *base, int64_t *scale);
+/* its bytes: ceil(nrows / 2048) * bits * 256 */
+int  vdl_download_packed_image(vdl_ctx *ctx, const char *name, void *host_ptr, size_t bytes);
+/* contexts without a device (vdl_plan_jit_check): declare a registered column's packed image (no bytes behind it) */
+int  vdl_declare_packed_image(vdl_ctx *ctx, const char *name, int bits, int64_t base, int64_t scale);
 /* on = 0: scans bind the catalog columns and ignore the images (tests, A/B comparisons in one process); default 1 */
 int  vdl_set_column_images(vdl_ctx *ctx, int on);
 

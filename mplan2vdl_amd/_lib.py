@@ -52,6 +52,9 @@ def load():
         "vdl_download_column": (i32, [vp, cp, vp, ctypes.c_size_t]),
         "vdl_encode_column": (i32, [vp, cp]),
         "vdl_column_image_info": (i32, [vp, cp, P(i32), P(i64), P(i64)]),
+        "vdl_column_packed_info": (i32, [vp, cp, P(i32), P(i64), P(i64)]),
+        "vdl_download_packed_image": (i32, [vp, cp, vp, ctypes.c_size_t]),
+        "vdl_declare_packed_image": (i32, [vp, cp, i32, i64, i64]),
         "vdl_set_column_images": (i32, [vp, i32]),
         "vdl_parse": (i32, [vp, cp, ctypes.c_size_t, P(vp)]),
         "vdl_plan_free": (None, [vp]),
@@ -114,7 +117,8 @@ def load():
 ABI_SYMBOLS = [
     "vdl_open", "vdl_close", "vdl_last_error", "vdl_version", "vdl_set_stream", "vdl_use_own_stream", "vdl_register_column",
     "vdl_upload_column", "vdl_generate_column", "vdl_drop_column", "vdl_column_info", "vdl_download_column",
-    "vdl_encode_column", "vdl_column_image_info", "vdl_set_column_images",
+    "vdl_encode_column", "vdl_column_image_info", "vdl_column_packed_info", "vdl_download_packed_image", "vdl_declare_packed_image",
+    "vdl_set_column_images",
     "vdl_parse", "vdl_plan_free", "vdl_plan_describe", "vdl_plan_is_fused", "vdl_plan_set_fusion",
     "vdl_plan_set_profiling", "vdl_plan_set_jit", "vdl_plan_jit_note", "vdl_plan_jit_check", "vdl_plan_image_columns", "vdl_plan_set_trace", "vdl_n_traced", "vdl_traced", "vdl_run", "vdl_n_outputs", "vdl_output", "vdl_plan_set_device_outputs", "vdl_output_device", "vdl_n_timings", "vdl_timing",
     "vdl_plan_set_order", "vdl_plan_order_note", "vdl_order_host",

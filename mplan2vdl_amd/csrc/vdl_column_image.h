@@ -96,5 +96,66 @@ inline bool usable_in_vscan(const Image &im, bool per_row_value) { return im.wid
 // the kernels must decode the column's values (MsArgs::decode)
 inline bool needs_decode(const Image &im) { return im.width > 0 && !im.pure(); }
 
+// ---- bit-packed images ---------------------------------------------------------------------------------------------------
+// A column's byte image (base, scale, e) is kept a third time with e' = e - emin in exactly `bits` bits per row, bits = the bit
+// length of emax - emin (1 for a constant column): v = base' + scale * e' with base' = base + scale * emin (wrapping).  Built only
+// when it is narrower than the byte image.  Layout: lane-transposed stripes of 2048 rows (64 lanes x 32 values): row
+// 2048 s + 64 j + l is value j of lane l in stripe s; lane l's 32 values are a bit stream of `bits` dwords (value j in bits
+// [j bits, (j + 1) bits), possibly across two dwords), and dword k of lane l in stripe s lies at dword (s bits + k) 64 + l.  The
+// image is padded with zeros to whole stripes.  A wave that reads dword k of a stripe reads 256 contiguous bytes.
+constexpr int kStripeLanes = 64, kStripeValues = 32, kStripeRows = kStripeLanes * kStripeValues;
+struct Packed {
+    int bits = 0;                  // 1..32; 0 = no packed image
+    int64_t base = 0, scale = 1;   // v = base + scale * e'
+};
+
+// bit length of x; 1 for 0
+inline int bit_length(uint64_t x) {
+    int b = 1;
+    while (b < 64 && (x >> b) != 0) b++;
+    return b;
+}
+
+// the packed image of a byte image `im` whose encoded values lie in [emin, emax]; bits 0 when it would not be narrower
+inline Packed pack(const Image &im, int64_t emin, int64_t emax) {
+    Packed pk;
+    if (im.width <= 0 || emin > emax) return pk;
+    const int bits = bit_length((uint64_t)emax - (uint64_t)emin);
+    if (bits > 32 || bits >= 8 * im.width) return pk;
+    pk.bits = bits;
+    pk.base = (int64_t)((uint64_t)im.base + (uint64_t)im.scale * (uint64_t)emin);
+    pk.scale = im.scale;
+    return pk;
+}
+
+inline int64_t stripes(int64_t n) { return (n + kStripeRows - 1) / kStripeRows; }
+// dwords of a packed image of n rows (padded to whole stripes)
+inline int64_t packed_dwords(int64_t n, int bits) { return stripes(n) * bits * kStripeLanes; }
+// where row i's value starts: the dword index of its first bit and the bit inside it
+inline void packed_at(int64_t i, int bits, int64_t *dword, int *bit) {
+    const int64_t s = i / kStripeRows, j = (i % kStripeRows) / kStripeLanes, l = i % kStripeLanes;
+    const int64_t o = j * bits;
+    *dword = (s * bits + o / 32) * kStripeLanes + l;
+    *bit = (int)(o % 32);
+}
+
+// The filter lo <= v <= hi as a filter on e' in [0, 2^bits - 1]: the unfiltered sentinels stay, every other range is clamped to
+// that domain, and a range that holds no stored value becomes [1, 0] (as map_range).
+inline void map_range_packed(const Packed &pk, int64_t lo, int64_t hi, int64_t *plo, int64_t *phi) {
+    if (lo == INT64_MIN && hi == INT64_MAX) { *plo = lo; *phi = hi; return; }
+    const __int128 top = ((__int128)1 << pk.bits) - 1;
+    __int128 a = ceil_div((__int128)lo - pk.base, pk.scale), b = floor_div((__int128)hi - pk.base, pk.scale);
+    if (a < 0) a = 0;
+    if (b > top) b = top;
+    if (a > b) { *plo = 1; *phi = 0; return; }
+    *plo = (int64_t)a; *phi = (int64_t)b;
+}
+// the factor a + s * v over the packed image, as compose
+inline void compose_packed(const Packed &pk, int64_t a, int64_t s, int64_t *a2, int64_t *s2) {
+    Image im;
+    im.width = 4; im.base = pk.base; im.scale = pk.scale;
+    compose(im, a, s, a2, s2);
+}
+
 }  // namespace img
 }  // namespace vdl

@@ -135,7 +135,8 @@ static std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols
 }
 
 template <typename PlanT>
-int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0) {
+// packed: 0 = byte images only; 1 = the filter columns from their bit-packed images (the packed form), 2 = every table column that has one
+int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0, int packed = 0) {
     cols = MScanCols{};
     d = MScanDesc{};
     cols.ncol = (int)sp.cols.size();
@@ -162,6 +163,17 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
                 cols.image |= 1u << k;
                 cols.ptr[k] = col.image_buf->p; cols.width[k] = col.image.width;
                 img::map_range(col.image, sc.lo, sc.hi, &cols.lo[k], &cols.hi[k]);
+            }
+            img::Image pim;                                           // the packed image as an image: for the rules and compose
+            pim.width = 4; pim.base = col.packed.base; pim.scale = col.packed.scale;
+            if (packed && c->images && col.packed.bits && (packed == 2 || cols.filtered[k]) && img::usable(pim, (raw >> k) & 1u)) {
+                // the packed image: bounds on e' in [0, 2^bits - 1], factors composed with (base', scale)
+                ims[k] = pim;
+                cols.image |= 1u << k;
+                cols.packed |= 1u << k;
+                cols.pbits[k] = col.packed.bits;
+                cols.ptr[k] = col.packed_buf ? col.packed_buf->p : nullptr; cols.width[k] = 4;
+                img::map_range_packed(col.packed, sc.lo, sc.hi, &cols.lo[k], &cols.hi[k]);
             }
             *bytes_per_row += cols.width[k];
         } else if (sc.kind == VC_GATHER || sc.kind == VC_INRANGE) {      // a column of another table, looked up / its length
@@ -224,8 +236,20 @@ static std::string mscan_label(const ScanLaunch &cfg, const MScanCols &cols) {
 // filter columns a staged form reads with the tile: 1, 2; 3 = the queue form (one); 4 = all of them (only aggregate inputs and the
 // sources of derived columns read late)
 static int eager_filters_of(int lazy) { return lazy == 3 ? 1 : lazy == 4 ? kMaxVCols : lazy; }
-static const char *late_suffix(int lazy) { return lazy == 3 ? ",queue" : lazy == 4 ? ",lateall" : lazy > 1 ? ",late2" : ",late"; }
-struct Specialised { std::shared_ptr<jit::Kernel> k; int grid = 0, per_cu = 0, u = 0, lazy = 0; size_t code_bytes = 0; std::string name, stages; };
+// (5, 6: the packed form -- the filter columns from their bit-packed images and the aggregate inputs late from their byte images, or
+// every column from its packed image: packed_args)
+static const char *late_suffix(int lazy) {
+    return lazy == 6 ? ",packed" : lazy == 5 ? ",packed,late" : lazy == 3 ? ",queue" : lazy == 4 ? ",lateall" : lazy > 1 ? ",late2" : ",late";
+}
+struct Specialised {
+    std::shared_ptr<jit::Kernel> k;
+    int grid = 0, per_cu = 0, u = 0, lazy = 0;
+    size_t code_bytes = 0;
+    std::string name, stages, packed;
+    std::shared_ptr<MScanCols> cols;      // the packed form: its binding (packed_args), else null (the plan's)
+    std::shared_ptr<MScanDesc> desc;
+    uint32_t late = 0;                    // the packed form: columns read late (MsArgs::lazy)
+};
 // "l_discount@1 l_quantity@2 l_extendedprice@last": which table columns a staged scan reads when (MsArgs::stages)
 static std::string stages_text(const vdl_plan *p, size_t s, const MsArgs &args) {
     const size_t ns = p->fused.scans.size();
@@ -318,47 +342,114 @@ static bool specialised_args(vdl_ctx *c, const MScanCols &cols, const MScanDesc 
     }
     return true;
 }
+// The packed form (lazy 5: the filter columns from their bit-packed images, the columns that are only aggregate inputs late from their
+// byte images; 6: every column from its packed image, nothing late; a column without a packed image comes from its byte image with the
+// stripe) of scan s: its own binding -- the packed columns' bounds and factors are those of the packed images -- and arguments, or
+// false and why the form does not exist for this scan.  Only global aggregate scans over table columns have it.
+static bool packed_args(vdl_ctx *c, const vdl_plan *p, size_t s, bool grouped, int lazy, int u, MScanCols &cols, MScanDesc &d, MsArgs &args, std::string &why) {
+    if (grouped || s >= p->fused.scans.size()) { why = "the packed form serves global aggregate scans only, not grouped scans"; return false; }
+    const ScanPlan &sp = p->fused.scans[s];
+    for (const ScanColumn &sc : sp.cols)
+        if (sc.kind != VC_DIRECT) { why = "the packed form serves scans over table columns only, not scans with derived columns"; return false; }
+    if (!c->images) { why = "column images are off"; return false; }
+    if (u != 1 && u != 2 && u != 4 && u != 8 && u != 16) { why = "the packed form takes 1, 2, 4, 8 or 16 row pairs per slice (a lane's 32 values of a stripe split evenly)"; return false; }
+    int64_t bpr = 0;
+    bind_mscan(c, sp, cols, d, &bpr, p->row_offset, lazy == 5 ? 1 : 2);
+    if (cols.ncol > 10) { why = "the packed form takes at most 10 columns"; return false; }
+    // (a column without a packed image is read from its byte image -- or itself -- with the stripe)
+    if (!cols.packed) { why = lazy == 5 ? "no filter column has a packed image the scan may read" : "no column has a packed image the scan may read"; return false; }
+    args = mscan_args(cols);
+    if (lazy == 5) {
+        uint32_t used = 0;
+        for (int j = 0; j < d.nagg; j++) if (d.agg[j].kind != AGG_FIRST) used |= d.agg[j].used;
+        for (int k = 0; k < cols.ncol; k++)
+            if (!((cols.packed >> k) & 1u) && !cols.filtered[k] && ((used >> k) & 1u)) { args.stages |= (uint64_t)15 << (4 * k); args.lazy |= 1u << k; }
+        if (!args.lazy) { why = "no column to read late"; return false; }
+    }
+    return true;
+}
+// "l_shipdate:12 l_discount:4": the columns a packed form reads from packed images, with their bits per row
+static std::string packed_text(const vdl_plan *p, size_t s, const MScanCols &cols) {
+    std::string o;
+    for (int k = 0; k < cols.ncol && s < p->fused.scans.size() && (size_t)k < p->fused.scans[s].cols.size(); k++) {
+        if (!((cols.packed >> k) & 1u)) continue;
+        const std::string &name = p->fused.scans[s].cols[(size_t)k].name;
+        o += (o.empty() ? "" : " ") + name.substr(name.find('.') == std::string::npos ? 0 : name.find('.') + 1) + ":" + std::to_string(cols.pbits[k]);
+    }
+    return o;
+}
 static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, int u, int lazy /* 0 | eager filter columns of the staged form */, Specialised &out, std::string &why,
                               bool census = false) {
+    out = Specialised{};
     jit::Shape sh = jit_shape(p->mcols[s], p->mcfg[s]);
     if (u > 0) sh.u = u;
+    else if (lazy >= 5) sh.u = getenv("VDL_JIT_U") ? atoi(getenv("VDL_JIT_U")) : 2;      // (the packed form: up to 16 row pairs per slice)
     sh.census = census;
     std::vector<char> code;
     MsArgs args;
-    if (!specialised_args(c, p->mcols[s], p->mdesc[s], grouped, lazy, args, why)) return false;
-    if (!jit::compile(jit::mscan_source(args, p->mdesc[s], sh), c->arch, code, why)) { why = why.substr(0, 400); return false; }
+    const MScanCols *cols = &p->mcols[s];
+    const MScanDesc *desc = &p->mdesc[s];
+    if (lazy >= 5) {
+        // the packed form: its own binding, which replaces the plan's when the form is chosen
+        out.cols = std::make_shared<MScanCols>();
+        out.desc = std::make_shared<MScanDesc>();
+        if (!packed_args(c, p, s, grouped, lazy, sh.u, *out.cols, *out.desc, args, why)) return false;
+        out.desc->block_partials = p->mdesc[s].block_partials;
+        cols = out.cols.get();
+        desc = out.desc.get();
+    } else if (!specialised_args(c, p->mcols[s], p->mdesc[s], grouped, lazy, args, why)) return false;
+    if (!jit::compile(jit::mscan_source(args, *desc, sh), c->arch, code, why)) { why = why.substr(0, 400); return false; }
     // a specialised scan is 10-25 KB of code; ten times that means the compiler did not fold the descriptor (it then sits in
     // scratch memory and every descriptor-driven loop stays): such a build is slower than the precompiled kernel
     if (code.size() > (size_t)96 << 10) { why = "the descriptor did not fold (" + std::to_string(code.size()) + " B of code)"; return false; }
-    out.k = jit::load(code, why, jit::entry_name(jit::MSCAN, args, p->mdesc[s], sh));
+    out.k = jit::load(code, why, jit::entry_name(jit::MSCAN, args, *desc, sh));
     if (!out.k) return false;
     int per_cu = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, out.k->fn, 256, mscan_lds_bytes(p->mdesc[s], grouped)) != hipSuccess || per_cu < 1) {
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, out.k->fn, 256, mscan_lds_bytes(*desc, grouped)) != hipSuccess || per_cu < 1) {
         (void)hipGetLastError();
         per_cu = 2;
     }
     if (per_cu > 8) per_cu = 8;
     const int64_t tile = (int64_t)256 * 2 * sh.u;
     int64_t grid = (int64_t)c->num_cus * per_cu;
-    if (grid > p->mcols[s].n / tile) grid = p->mcols[s].n / tile;
+    // (the packed form: one wave per stripe of 2048 rows at a time, four per block)
+    const int64_t most = lazy >= 5 ? (img::stripes(cols->n) + 3) / 4 : cols->n / tile;
+    if (grid > most) grid = most;
     if (grid < 1) grid = 1;
-    out.grid = (int)grid; out.per_cu = per_cu; out.code_bytes = code.size(); out.name = jit_name(sh, p->mcols[s].image != 0); out.u = sh.u; out.lazy = lazy;
+    out.grid = (int)grid; out.per_cu = per_cu; out.code_bytes = code.size(); out.name = jit_name(sh, cols->image != 0); out.u = sh.u; out.lazy = lazy;
     if (lazy) out.name.insert(out.name.size() - 1, late_suffix(lazy));
     if (lazy) out.stages = stages_text(p, s, args);
+    if (lazy >= 5) { out.packed = packed_text(p, s, *cols); out.late = args.lazy; }
     return true;
+}
+// the note's words on a built form: "..., read late: ...", ", packed: l_shipdate:12 ..."
+static std::string form_text(const Specialised &sp) {
+    return (sp.packed.empty() ? "" : ", packed: " + sp.packed) + (sp.stages.empty() ? "" : ", read late: " + sp.stages);
+}
+// a chosen form's kernel, grid and -- the packed form -- binding become the scan's
+static void install_form(vdl_plan *p, size_t s, const Specialised &sp) {
+    if (sp.cols) {
+        int64_t *parts = p->mdesc[s].block_partials;
+        p->mcols[s] = *sp.cols;
+        p->mdesc[s] = *sp.desc;
+        p->mdesc[s].block_partials = parts;
+    }
+    p->mcfg[s].grid = sp.grid;
+    p->mjit[s] = sp.k;
+    p->mjit_form[s].u = sp.u; p->mjit_form[s].lazy = sp.lazy;
 }
 static bool specialise_scan(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, std::string *kname) {
     Specialised sp;
     std::string why;
     // (tests, profiles: VDL_JIT_LATE=1|2 forces the staged form -- with that many filter columns read with the tile, 4: all of them -- where a column allows it)
     const int late = getenv("VDL_JIT_LATE") ? std::max(1, atoi(getenv("VDL_JIT_LATE"))) : 0;
-    if (!(late && build_specialised(c, p, s, grouped, 0, late, sp, why)) && !build_specialised(c, p, s, grouped, 0, 0, sp, why)) { p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + why + "); "; return false; }
-    p->mcfg[s].grid = sp.grid;
-    p->mjit[s] = sp.k;
-    p->mjit_form[s].u = sp.u; p->mjit_form[s].lazy = sp.lazy;
+    // (5 | 6: the packed form, at 2 row pairs per slice unless VDL_JIT_U says otherwise; where it does not exist the note says why)
+    std::string why_late;
+    if (late && !build_specialised(c, p, s, grouped, 0, late, sp, why_late) && late >= 5) p->jit_note += "scan " + std::to_string(s) + ": no packed form (" + why_late + "); ";
+    if (!sp.k && !build_specialised(c, p, s, grouped, 0, 0, sp, why)) { p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + why + "); "; return false; }
+    install_form(p, s, sp);
     *kname = sp.name;
-    p->jit_note += "scan " + std::to_string(s) + ": " + sp.name + ", " + std::to_string(sp.code_bytes) + " B of code, " + std::to_string(sp.per_cu) + " blocks/CU" +
-                   (sp.stages.empty() ? "" : ", read late: " + sp.stages) + "; ";
+    p->jit_note += "scan " + std::to_string(s) + ": " + sp.name + ", " + std::to_string(sp.code_bytes) + " B of code, " + std::to_string(sp.per_cu) + " blocks/CU" + form_text(sp) + "; ";
     return true;
 }
 // blocks a specialised scan may be launched with, whatever rows-per-lane the tuner settles on: the partials area is sized for it
@@ -399,6 +490,28 @@ static void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
             if (const char *q = strstr(pin, "late=")) pin_late = atoi(q + 5);
             if (pin_u > 0) cands = {{pin_u, std::max(pin_late, 0)}};
         }
+        // then the packed forms (5: filter columns from their bit-packed images, aggregate inputs late; 6: every column packed), at 2 to
+        // 16 row pairs per slice (more rows per slice: more late loads in flight, fewer waves), with the same rule.  Not under a pin; VDL_JIT_PACKED=0 leaves them out, =only tries nothing else.
+        std::vector<std::pair<int, int>> packed_forms = {{2, 5}, {4, 5}, {8, 5}, {16, 5}, {2, 6}, {4, 6}, {8, 6}};
+        const char *packed_env = getenv("VDL_JIT_PACKED");
+        if (pin_u > 0 || (packed_env && strcmp(packed_env, "0") == 0)) packed_forms.clear();
+        else if (packed_env && strcmp(packed_env, "only") == 0) cands.clear();
+        if (!packed_forms.empty()) {                           // (forms the scan does not have are not compiled)
+            MScanCols pc;
+            auto pd = std::make_unique<MScanDesc>();
+            MsArgs pa;
+            std::string why;
+            if (!packed_args(c, p, s, grouped, 5, 2, pc, *pd, pa, why) && !packed_args(c, p, s, grouped, 6, 2, pc, *pd, pa, why)) packed_forms.clear();
+        }
+        cands.insert(cands.end(), packed_forms.begin(), packed_forms.end());
+        // (a scan that runs the packed form -- VDL_JIT_LATE=5 | 6 -- is timed in the other forms over its own binding again)
+        MScanCols cols_now = p->mcols[s];
+        auto desc_now = std::make_unique<MScanDesc>(p->mdesc[s]);
+        if (p->mjit_form[s].lazy >= 5) {
+            int64_t bpr = 0;
+            bind_mscan(c, p->fused.scans[s], p->mcols[s], p->mdesc[s], &bpr, p->row_offset);
+            p->mdesc[s].block_partials = desc_now->block_partials;
+        }
         // a candidate's time is the MEDIAN of five launches after the module's first, and a later candidate only replaces the one
         // in hand when it is more than 2 % quicker: forms within the noise of each other no longer swap places from run to run
         auto median_of = [](std::vector<float> &t) { std::sort(t.begin(), t.end()); return t[t.size() / 2]; };
@@ -406,18 +519,20 @@ static void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
         for (auto &cu : cands) {
             const int u = cu.first ? cu.first : best_u;
             const int lazy = cu.second;
-            if (u <= 0 || (int64_t)256 * 2 * u > p->mcols[s].n) continue;
+            if (u <= 0 || (lazy < 5 && (int64_t)256 * 2 * u > p->mcols[s].n)) continue;
             if (lazy == 1 && cu.first == best_u) continue;
             Specialised cand;
             std::string why;
             if (!build_specialised(c, p, s, grouped, u, lazy, cand, why)) continue;
             ScanLaunch cfg = p->mcfg[s];
             cfg.grid = cand.grid;
-            HIP_CHECK(hipMemcpyAsync(p->mdev[s]->p, &p->mdesc[s], sizeof(MScanDesc), hipMemcpyHostToDevice, c->stream));
+            const MScanCols &ccols = cand.cols ? *cand.cols : p->mcols[s];
+            const MScanDesc &cdesc = cand.desc ? *cand.desc : p->mdesc[s];
+            HIP_CHECK(hipMemcpyAsync(p->mdev[s]->p, &cdesc, sizeof(MScanDesc), hipMemcpyHostToDevice, c->stream));
             std::vector<float> times;
             for (int rep = 0; rep < 6; rep++) {
                 HIP_CHECK(hipEventRecord(e0, c->stream));
-                HIP_CHECK(launch_mscan(p->mcols[s], p->mdesc[s], (const MScanDesc *)p->mdev[s]->p, cfg, grouped, false, out, false, c->stream, cand.k->fn));
+                HIP_CHECK(launch_mscan(ccols, cdesc, (const MScanDesc *)p->mdev[s]->p, cfg, grouped, false, out, false, c->stream, cand.k->fn));
                 HIP_CHECK(hipEventRecord(e1, c->stream));
                 HIP_CHECK(hipEventSynchronize(e1));
                 float t = 0;
@@ -429,7 +544,11 @@ static void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
             if (!best.k || ms < best_ms * 0.98f) { best = cand; best_ms = ms; }
             if (!lazy && (best_u == 0 || cand.k == best.k)) best_u = u;       // the staged forms start from the quickest eager shape
         }
-        if (!best.k) continue;
+        if (!best.k) {
+            p->mcols[s] = cols_now;
+            p->mdesc[s] = *desc_now;
+            continue;
+        }
         if (!grouped && use_kscan(p->fused.scans[s]) && p->block_partials[s] && pin_u <= 0) {
             // the hand-tuned single-aggregate kernel is a candidate too
             float ms = 1e30f;
@@ -454,10 +573,9 @@ static void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
                 continue;
             }
         }
-        p->mjit[s] = best.k;
-        p->mcfg[s].grid = best.grid;
-        p->mjit_form[s].u = best.u; p->mjit_form[s].lazy = best.lazy;
-        p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + best.name + (best.stages.empty() ? "" : " (read late: " + best.stages + ")") + "; ";
+        install_form(p, s, best);
+        p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + best.name + (best.packed.empty() ? "" : " (packed: " + best.packed + ")") +
+                       (best.stages.empty() ? "" : " (read late: " + best.stages + ")") + "; ";
         if ((int)s == p->dominant)
             p->dominant_kernel = best.name + "_grid" + std::to_string(best.grid) + (grouped ? "_rep" + std::to_string(p->mdesc[s].replicas) : "");
     }
@@ -494,6 +612,34 @@ static int64_t scan_bytes_moved(vdl_ctx *c, vdl_plan *p, std::string &detail) {
     }
     Specialised cen;
     std::string why;
+    if (p->mjit_form[s].lazy >= 5) {
+        // the packed form: every packed column in whole stripes (its padding included), the late columns' lines counted by the census
+        // build of the form that ran (same binding)
+        if (!build_specialised(c, p, s, grouped, p->mjit_form[s].u, p->mjit_form[s].lazy, cen, why, true)) throw Error(VDL_ERR_UNSUPPORTED, "the census build of the packed scan failed: " + why);
+        BufP counts = dev_alloc(c, sizeof(unsigned long long) * kMaxVCols);
+        BufP words = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(p->n_words, 1));
+        HIP_CHECK(hipMemsetAsync(counts->p, 0, sizeof(unsigned long long) * kMaxVCols, c->stream));
+        MScanDesc d = *cen.desc;
+        d.census = (unsigned long long *)counts->p;
+        BufP ddev = dev_alloc(c, sizeof(MScanDesc));
+        HIP_CHECK(hipMemcpyAsync(ddev->p, &d, sizeof d, hipMemcpyHostToDevice, c->stream));
+        ScanLaunch cfg = p->mcfg[s];
+        cfg.grid = cen.grid;
+        int64_t *out = (int64_t *)words->p + p->word_offset[s];
+        HIP_CHECK(launch_mscan(*cen.cols, d, (const MScanDesc *)ddev->p, cfg, grouped, false, out, false, c->stream, cen.k->fn));
+        unsigned long long lines[kMaxVCols] = {};
+        c->fetch_to_host(counts->p, kMaxVCols, (int64_t *)lines, c->stream);
+        const MScanCols &pc = *cen.cols;
+        for (int k = 0; k < pc.ncol; k++) {
+            const bool packed = (pc.packed >> k) & 1u, late = (cen.late >> k) & 1u;
+            const int64_t b = packed ? img::packed_dwords(pc.n, pc.pbits[k]) * 4 : late ? (int64_t)lines[k] * 128 : pc.n * pc.width[k];
+            total += b;
+            detail += short_name(k) + "=" + std::to_string(b) + (packed ? "(packed: " + std::to_string(pc.pbits[k]) + " bits) " :
+                                                                   late ? "(late: " + std::to_string(lines[k]) + " lines of " + std::to_string((pc.n * pc.width[k] + 127) / 128) + ") " : " ");
+        }
+        detail += "(census of " + cen.name + ")";
+        return total;
+    }
     if (!build_specialised(c, p, s, grouped, p->mjit_form[s].u, p->mjit_form[s].lazy, cen, why, true)) throw Error(VDL_ERR_UNSUPPORTED, "the census build of the staged scan failed: " + why);
     BufP counts = dev_alloc(c, sizeof(unsigned long long) * kMaxVCols);
     BufP words = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(p->n_words, 1));
@@ -1377,6 +1523,8 @@ int vdl_use_own_stream(vdl_ctx *c) {
 static void build_image(vdl_ctx *c, Column &col) {
     col.image = img::Image{};
     col.image_buf.reset();
+    col.packed = img::Packed{};
+    col.packed_buf.reset();
     if (col.n <= 0 || col.width <= 1) return;
     BufP st = dev_alloc(c, 3 * sizeof(int64_t));
     HIP_CHECK(launch_image_stats(col.dev, col.width, col.n, (unsigned long long *)st->p, c->stream));
@@ -1387,9 +1535,19 @@ static void build_image(vdl_ctx *c, Column &col) {
     if (!im.width) return;
     BufP buf = dev_alloc(c, (size_t)col.n * (size_t)im.width);
     HIP_CHECK(launch_image_encode(col.dev, col.width, col.n, im.base, im.scale, buf->p, im.width, c->stream));
+    // the bit-packed image of the byte image: e' = e - emin in the bit length of emax - emin
+    const int64_t emin = (int64_t)(((uint64_t)mn - (uint64_t)im.base) / (uint64_t)im.scale), emax = (int64_t)(((uint64_t)mx - (uint64_t)im.base) / (uint64_t)im.scale);
+    const img::Packed pk = img::pack(im, emin, emax);
+    BufP pbuf;
+    if (pk.bits) {
+        pbuf = dev_alloc(c, (size_t)img::packed_dwords(col.n, pk.bits) * 4);
+        HIP_CHECK(launch_image_pack(buf->p, im.width, col.n, emin, pk.bits, pbuf->p, c->stream));
+    }
     HIP_CHECK(hipStreamSynchronize(c->stream));
     col.image = im;
     col.image_buf = buf;
+    col.packed = pk;
+    col.packed_buf = pbuf;
 }
 
 static void check_width(int w) {
@@ -1462,6 +1620,42 @@ int vdl_column_image_info(const vdl_ctx *c, const char *name, int *width, int64_
     if (base) *base = im.width ? im.base : 0;
     if (scale) *scale = im.width ? im.scale : 1;
     return VDL_OK;
+}
+
+int vdl_column_packed_info(const vdl_ctx *c, const char *name, int *bits, int64_t *base, int64_t *scale) {
+    if (!c || !name) return VDL_ERR_ARG;
+    auto it = c->cols.find(name);
+    if (it == c->cols.end()) return VDL_ERR_COLUMN;
+    const img::Packed &pk = it->second.packed;
+    if (bits) *bits = pk.bits;
+    if (base) *base = pk.bits ? pk.base : 0;
+    if (scale) *scale = pk.bits ? pk.scale : 1;
+    return VDL_OK;
+}
+
+int vdl_download_packed_image(vdl_ctx *c, const char *name, void *host_ptr, size_t bytes) {
+    if (!c || !name || !host_ptr) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        need_device(c);
+        const Column &col = find_col(c, name);
+        if (!col.packed.bits || !col.packed_buf) throw Error(VDL_ERR_ARG, std::string("column '") + name + "' has no packed image");
+        if (bytes != (size_t)img::packed_dwords(col.n, col.packed.bits) * 4) throw Error(VDL_ERR_ARG, "host buffer size does not match the packed image");
+        HIP_CHECK(hipMemcpyAsync(host_ptr, col.packed_buf->p, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int vdl_declare_packed_image(vdl_ctx *c, const char *name, int bits, int64_t base, int64_t scale) {
+    if (!c || !name) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        if (c->device >= 0) throw Error(VDL_ERR_ARG, "packed images are declared only on a context without a device (a device builds them)");
+        if (bits < 1 || bits > 32 || scale < 1) throw Error(VDL_ERR_ARG, "bits must lie in 1..32 and scale be positive");
+        auto it = c->cols.find(name);
+        if (it == c->cols.end()) throw Error(VDL_ERR_COLUMN, std::string("no column '") + name + "'");
+        it->second.packed.bits = bits; it->second.packed.base = base; it->second.packed.scale = scale;
+        it->second.packed_buf.reset();
+        c->catalog_version++;
+    });
 }
 
 int vdl_set_column_images(vdl_ctx *c, int on) {
@@ -1626,13 +1820,25 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
             // the staged or queue form of the same scan (VDL_JIT_LATE as in specialise_scan), refused where the tuner refuses it
             const int late = getenv("VDL_JIT_LATE") ? std::max(1, atoi(getenv("VDL_JIT_LATE"))) : 0;
             MsArgs args;
-            if (!specialised_args(c, cols, *d, grouped, late, args, log)) {
+            if (late >= 5) {
+                // the packed form (5 | 6, as build_specialised: 2 row pairs per slice unless VDL_JIT_U says otherwise), over its own binding
+                sh.u = getenv("VDL_JIT_U") ? atoi(getenv("VDL_JIT_U")) : 2;
+                MScanCols pc;
+                if (!packed_args(c, p, s, grouped, late, sh.u, pc, *d, args, log)) {
+                    p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + log + "); ";
+                    continue;
+                }
+                cols = pc;
+            } else if (!specialised_args(c, cols, *d, grouped, late, args, log)) {
                 p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + log + "); ";
                 continue;
             }
             if (!jit::compile(jit::mscan_source(args, *d, sh), c->arch, code, log))
                 throw Error(VDL_ERR_UNSUPPORTED, "scan " + std::to_string(s) + " does not build: " + log.substr(0, 2000));
-            p->jit_note += "scan " + std::to_string(s) + ": " + jit_name(sh, cols.image != 0) + (args.queued ? " (queue)" : args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";
+            std::string name = jit_name(sh, cols.image != 0);
+            if (args.packed) name.insert(name.size() - 1, late_suffix(late));
+            p->jit_note += "scan " + std::to_string(s) + ": " + name + (args.packed ? " (packed: " + packed_text(p, s, cols) + ")" : "") +
+                           (args.queued ? " (queue)" : args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";
         }
     });
 }

@@ -93,6 +93,10 @@ struct Column {
     // Aligned and padded like a column; it goes with the column (drop, re-registration)
     img::Image image;
     BufP image_buf;
+    // the bit-packed image of the byte image (img::Packed; bits 0 = none): read by the packed form of a specialised global aggregate
+    // scan.  Goes with the column like the byte image.  (packed_buf null with bits > 0: declared on a context without a device)
+    img::Packed packed;
+    BufP packed_buf;
 };
 
 // device-side vector of the general path

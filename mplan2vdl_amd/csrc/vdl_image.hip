@@ -66,7 +66,46 @@ __global__ __launch_bounds__(256) void k_image_encode(const void *col, int w, in
     }
 }
 
+// The bit-packed image (vdl_column_image.h, Packed): one thread per (stripe, lane) gathers its lane's 32 values e - emin from the byte
+// image and writes the lane's `bits` dwords; consecutive threads are consecutive lanes, so every dword store of a wave is 256
+// contiguous bytes.  Rows past n (the padding of the last stripe) are 0.
+template <typename T>
+__global__ __launch_bounds__(256) void k_image_pack(const T *img, int64_t n, int64_t emin, int bits, uint32_t *out, int64_t lanes) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const uint64_t mask = bits == 32 ? 0xffffffffull : (1ull << bits) - 1ull;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < lanes; t += stride) {
+        const int64_t s = t / 64, l = t % 64;
+        uint32_t *dst = out + s * bits * 64 + l;
+        uint64_t acc = 0;                                   // bits not yet written, from bit 0 of dword k
+        int have = 0, k = 0;
+        for (int j = 0; j < 32; j++) {
+            const int64_t i = s * 2048 + (int64_t)j * 64 + l;
+            const uint64_t e = i < n ? ((uint64_t)(int64_t)img[i] - (uint64_t)emin) & mask : 0ull;
+            acc |= e << have;
+            have += bits;
+            if (have >= 32) { dst[(int64_t)k * 64] = (uint32_t)acc; k++; acc >>= 32; have -= 32; }
+        }
+        if (have > 0) dst[(int64_t)k * 64] = (uint32_t)acc;      // (32 * bits is a whole number of dwords: never taken)
+    }
+}
+
 }  // namespace
+
+hipError_t launch_image_pack(const void *img, int img_bytes, int64_t n, int64_t emin, int bits, void *out, hipStream_t s) {
+    (void)hipGetLastError();
+    if (n <= 0) return hipSuccess;
+    if (bits < 1 || bits > 32) return hipErrorInvalidValue;
+    const int64_t lanes = (n + 2047) / 2048 * 64;
+    const int grid = (int)std::min<int64_t>((lanes + 255) / 256, 256 * 16);
+    switch (img_bytes) {
+    case 1: k_image_pack<int8_t><<<grid, 256, 0, s>>>((const int8_t *)img, n, emin, bits, (uint32_t *)out, lanes); break;
+    case 2: k_image_pack<int16_t><<<grid, 256, 0, s>>>((const int16_t *)img, n, emin, bits, (uint32_t *)out, lanes); break;
+    case 4: k_image_pack<int32_t><<<grid, 256, 0, s>>>((const int32_t *)img, n, emin, bits, (uint32_t *)out, lanes); break;
+    case 8: k_image_pack<int64_t><<<grid, 256, 0, s>>>((const int64_t *)img, n, emin, bits, (uint32_t *)out, lanes); break;
+    default: return hipErrorInvalidValue;
+    }
+    return launch_status();
+}
 
 hipError_t launch_image_stats(const void *col, int elem_bytes, int64_t n, unsigned long long *out3, hipStream_t s) {
     (void)hipGetLastError();

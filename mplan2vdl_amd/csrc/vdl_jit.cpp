@@ -194,7 +194,9 @@ static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, con
     o << "namespace vdl {\n";
     o << "constexpr MsArgs jit_args" << suffix << "() {\n    MsArgs a{};\n";
     o << "    a.ncol = " << C.ncol << "; a.widths = " << C.widths << "ull; a.filtered = " << C.filtered << "u; a.derived = " << C.derived
-      << "u; a.lazy = " << C.lazy << "u; a.stages = " << C.stages << "ull; a.queued = " << C.queued << "; a.decode = " << C.decode << "u;\n    return a;\n}\n";
+      << "u; a.lazy = " << C.lazy << "u; a.stages = " << C.stages << "ull; a.queued = " << C.queued << "; a.decode = " << C.decode << "u;\n";
+    if (C.packed) o << "    a.packed = " << C.packed << "u; a.pbits = " << C.pbits << "ull;\n";
+    o << "    return a;\n}\n";
     o << "constexpr MScanDesc jit_desc" << suffix << "() {\n    MScanDesc d{};\n";
     o << "    d.nagg = " << D.nagg << "; d.nkey = " << D.nkey << "; d.replicas = " << D.replicas << "; d.pmin = " << lit(D.pmin) << "; d.pcount = " << lit(D.pcount) << ";\n";
     int pool = 0;
@@ -239,7 +241,38 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
     std::ostringstream o;
     o << "#define VDL_SPEC_UNROLL _Pragma(\"unroll\")\n";
     if (kind == MSCAN && sh.census) o << "#define VDL_CENSUS 1\n";
-    if (kind == MSCAN && C.lazy && C.queued) {
+    if (kind == MSCAN && C.packed) o << "#define VDL_PACKED 1\n";
+    if (kind == MSCAN && C.lazy && C.packed) {
+        // the packed form (vdl_mscan_body.h VDL_PACKED): the filters of the packed columns as 32-bit unsigned compares on e', then the
+        // late columns from their byte images, one row per lane through a buffer resource over the stripe (a lane's rows are 64 apart:
+        // no pairs).  Census builds: the wave's lanes hold consecutive rows (stride w), so a lane is the first asker of its 128-byte
+        // line when no lower live lane lies in the same line.
+        auto ulit = [](int64_t x) { return std::to_string((uint64_t)x & 0xffffffffull) + "u"; };
+        o << "#define VDL_STAGED_PRE";
+        for (int c = 0; c < C.ncol; c++) {
+            if (!((C.filtered >> c) & 1u) || ((C.lazy >> c) & 1u)) continue;
+            if ((C.packed >> c) & 1u)
+                o << " _Pragma(\"unroll\") for (int r = 0; r < RW; r++) alive[r] = alive[r] & ((uint32_t)v[" << c << "][r] >= " << ulit(D.flo[c]) << ") & ((uint32_t)v[" << c
+                  << "][r] <= " << ulit(D.fhi[c]) << ");";
+            else          // (a filter column without a packed image: its byte image, read with the stripe)
+                o << " _Pragma(\"unroll\") for (int r = 0; r < RW; r++) alive[r] = alive[r] & (v[" << c << "][r] >= " << lit(D.flo[c]) << ") & (v[" << c << "][r] <= "
+                  << lit(D.fhi[c]) << ");";
+        }
+        o << "\n#define VDL_STAGED_POST";
+        for (int c = 0; c < C.ncol; c++) {
+            if (!((C.lazy >> c) & 1u)) continue;
+            const int w = C.width(c);
+            o << " { const __amdgpu_buffer_rsrc_t rs_ = buf_rsrc((const char *)Cr.ptr[" << c << "] + tile0 * " << w << ", (uint32_t)(tile_rows * " << w
+              << ")); _Pragma(\"unroll\") for (int r = 0; r < RW; r++) {";
+            if (sh.census)
+                o << " { const uint64_t m_ = __ballot(pass[r]); const uint64_t a_ = (uint64_t)Cr.ptr[" << c << "] + (uint64_t)(rowid[r] - Cr.row0) * " << w << "ull;"
+                  << " const int ln_ = (int)(threadIdx.x & 63u); int lo_ = ln_ - (int)((a_ & 127ull) / " << w << "ull); if (lo_ < 0) lo_ = 0;"
+                  << " const bool first_ = pass[r] && ((m_ >> lo_) & ((1ull << (ln_ - lo_)) - 1ull)) == 0ull;"
+                  << " const uint64_t f_ = __ballot(first_); if (ln_ == 0) census_cnt[" << c << "] += (unsigned long long)__popcll(f_); }";
+            o << " v[" << c << "][r] = buf_load_one<" << w << ">(rs_, pass[r], (uint32_t)(rowid[r] - Cr.row0 - tile0) * " << w << "u); } }";
+        }
+        o << "\n";
+    } else if (kind == MSCAN && C.lazy && C.queued) {
         // the queue form: only the filters of the columns that come with the tile, as straight-line code over the tile's rows
         o << "#define VDL_QUEUE_FILTER";
         for (int c = 0; c < C.ncol; c++)
@@ -352,7 +385,7 @@ std::string entry_name(Kind kind, const MsArgs &C, const MScanDesc &D, const Sha
     // (staged: how many filter columns come with the tile is part of the name too -- the profiles tell the forms apart by it)
     int eager_filters = 0;
     for (int c = 0; c < C.ncol; c++) eager_filters += ((C.filtered >> c) & 1u) && !((C.derived >> c) & 1u) && C.stage(c) == 0;
-    return std::string("vdl_jit_mscan_") + (sh.grouped ? "grouped_" : "") + "u" + std::to_string(sh.u) + (C.lazy ? "_staged" + std::to_string(eager_filters) + "_" : "_") +
+    return std::string("vdl_jit_mscan_") + (sh.grouped ? "grouped_" : "") + (C.packed ? "packed_" : "") + "u" + std::to_string(sh.u) + (C.lazy ? "_staged" + std::to_string(eager_filters) + "_" : "_") +
            (sh.census ? "census_" : "") + tag;
 }
 

@@ -82,6 +82,8 @@ hipError_t launch_gen_column(void *out, int elem_bytes, int64_t row0, int64_t n,
 // decimal trailing zeros all values share with the first row (19: all equal); then e = (v - base) / scale into img (1, 2 or 4 bytes)
 hipError_t launch_image_stats(const void *col, int elem_bytes, int64_t n, unsigned long long *out3, hipStream_t s);
 hipError_t launch_image_encode(const void *col, int elem_bytes, int64_t n, int64_t base, int64_t scale, void *img, int img_bytes, hipStream_t s);
+// the bit-packed image (vdl_column_image.h Packed) of a byte image: img::packed_dwords(n, bits) dwords at `out`
+hipError_t launch_image_pack(const void *img, int img_bytes, int64_t n, int64_t emin, int bits, void *out, hipStream_t s);
 
 // ---- per-operator kernels -----------------------------------------------------------------
 // validity bitmaps: bit (i & 63) of word (i >> 6); nullptr = every slot holds a value.

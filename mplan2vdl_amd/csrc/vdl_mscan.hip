@@ -32,7 +32,9 @@ static MsArgs ms_args(const MScanCols &cols) {
     MsArgs a;
     a.ncol = cols.ncol; a.n = cols.n; a.row0 = cols.row0; a.rowid_base = cols.rowid_global ? 0 : cols.row0;
     a.decode = cols.decode;
+    a.packed = cols.packed;
     for (int c = 0; c < cols.ncol; c++) {
+        if ((cols.packed >> c) & 1u) a.pbits |= (uint64_t)cols.pbits[c] << (6 * c);
         a.ptr[c] = cols.ptr[c];
         a.widths |= (uint64_t)cols.width[c] << (4 * c);
         if (cols.filtered[c]) a.filtered |= 1u << c;

@@ -72,6 +72,24 @@ __device__ __forceinline__ void buf_load_pair(__amdgpu_buffer_rsrc_t rs, bool on
         a = (int8_t)(x & 0xffu); b = (int8_t)(x >> 8);
     }
 }
+// one row of width W at byte offset `off`, 0 where !on (the single-row form of buf_load_pair)
+template <int W>
+__device__ __forceinline__ int64_t buf_load_one(__amdgpu_buffer_rsrc_t rs, bool on, uint32_t off) {
+    const int o = (int)(on ? off : kBufOut);
+    if (W == 8) { const auto x = __builtin_amdgcn_raw_buffer_load_b64(rs, o, 0, 0); return (int64_t)(((uint64_t)x[1] << 32) | x[0]); }
+    if (W == 4) return (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0);
+    if (W == 2) return (int16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, o, 0, 0);
+    return (int8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, o, 0, 0);
+}
+// value j of a lane's bit stream of `b` bits per value (the packed images of vdl_column_image.h): j and b are compile-time
+// constants in the specialised builds, so this is one bit-field extract, or an align and an extract where the value straddles
+// two dwords
+__device__ __forceinline__ uint32_t unpack_bits(const uint32_t (&w)[32], int j, int b) {
+    const int o = j * b, k = o >> 5, sh = o & 31;
+    if (b >= 32) return w[k & 31];
+    if (sh + b <= 32) return __builtin_amdgcn_ubfe(w[k & 31], (unsigned)sh, (unsigned)b);
+    return __builtin_amdgcn_ubfe(__builtin_amdgcn_alignbit(w[(k + 1) & 31], w[k & 31], (unsigned)sh), 0u, (unsigned)b);
+}
 // a value read from a column image (vdl_column_image.h) as the column holds it: base + scale * e, in wrapping 64-bit arithmetic
 __device__ __forceinline__ int64_t img_decode(int64_t e, int64_t base, int64_t scale) {
     return (int64_t)((uint64_t)base + (uint64_t)scale * (uint64_t)e);
@@ -430,6 +448,11 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
     int64_t cnt = 0, oob = 0;
     int64_t *mytab = lds;
     int trash = 0;
+#ifdef VDL_PACKED
+    constexpr bool PACKED = true;
+#else
+    constexpr bool PACKED = false;
+#endif
 #ifdef VDL_CENSUS
     // a census build (measurement, never timed): the generated late loads count, per column, the distinct 128-byte lines they
     // ask for -- the memory side fetches whole lines (tools/ubench/fetch_calib) -- in lane 0's registers
@@ -469,6 +492,11 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
         bool alive[RW];
 #pragma unroll
         for (int r = 0; r < RW; r++) alive[r] = !DER || (int64_t)((r >> 1) * (BS * 2) + (r & 1)) < rows_left;
+#ifdef VDL_PACKED
+        // (the packed form: rows of the last stripe at or past n are out)
+#pragma unroll
+        for (int r = 0; r < RW; r++) alive[r] = alive[r] && rowid[r] - Cr.row0 < Cr.n;
+#endif
         // (the stages arrive as generated straight-line code -- VDL_STAGED_PRE / _POST, vdl_jit.cpp: written as loops over
         // columns and stages with the stage numbers read from C, the compiler no longer folded the descriptor: 235 KB of code)
 #ifdef VDL_STAGED_PRE
@@ -485,7 +513,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
 #endif
         } else {
             eval_pass<NC, RW>(C, D, v, pass);
-            if (DER) {
+            if (DER || PACKED) {
 #pragma unroll
                 for (int r = 0; r < RW; r++) pass[r] = pass[r] & alive[r];
             }
@@ -598,6 +626,64 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
     };
 
     const int64_t ntiles = Cr.n / TILE;
+#ifdef VDL_PACKED
+    // The PACKED form (specialised global aggregate scans over table columns, C.packed): the columns of C.packed are read from their
+    // bit-packed images (vdl_column_image.h Packed), in lane-transposed stripes of 2048 rows -- row 2048 s + 64 j + l is value j of lane
+    // l -- that the waves take in turn.  A wave issues every dword load of a stripe (`bits` per packed column, 256 contiguous bytes
+    // each) before it unpacks any, then runs the stripe through process() ROWS values of its lanes at a time: the rows a wave holds
+    // for one j are 64 consecutive rows, so the late loads of a column (from its byte image, one row per lane) ask for the same lines
+    // as the tile forms do.  The tile loop's row pairs (2t, 2t + 1) do not match this layout: it is a loop of its own.
+    if (!GROUPED && !DER && C.packed) {
+        static_assert(32 % ROWS == 0, "a lane's 32 values of a stripe split into row slices");
+        const int lane = tid & (kWave - 1);
+        // (the stripe is wave-uniform, and the compiler is told so: its addresses and the late loads' buffer resources stay in scalar
+        // registers -- derived from tid / 64 they were per-lane values, and every late load became a loop over the lanes' resources)
+        const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+        const int64_t nstripes = (Cr.n + 2047) / 2048, wstride = (int64_t)gridDim.x * (BS / kWave);
+        for (int64_t s = (int64_t)blockIdx.x * (BS / kWave) + wave; s < nstripes; s += wstride) {
+            uint32_t pw[NC][32];
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                if ((C.packed >> c) & 1u) {                    // wave-uniform
+                    const int b = C.bits(c);
+                    const char *p = (const char *)Cr.ptr[c] + ((s * b) * kWave + lane) * 4;
+#pragma unroll
+                    for (int k = 0; k < 32; k++)
+                        if (k < b) pw[c][k] = stream_load<NT, uint32_t>(p + (int64_t)k * (kWave * 4));
+                }
+            }
+            // (every load of the stripe goes out before the first value is unpacked: left to itself the scheduler moved each load down to
+            // its first use, and a stripe became `bits` round trips to memory one after the other)
+            __builtin_amdgcn_sched_barrier(0);
+            const int64_t tile0 = s * 2048, tile_rows = Cr.n - tile0 < 2048 ? Cr.n - tile0 : 2048;
+#pragma unroll
+            for (int j0 = 0; j0 < 32; j0 += ROWS) {
+                int64_t v[NC][ROWS], rowid[ROWS];
+#pragma unroll
+                for (int r = 0; r < ROWS; r++) rowid[r] = Cr.row0 + tile0 + (int64_t)(j0 + r) * kWave + lane;
+#pragma unroll
+                for (int c = 0; c < NC; c++) {
+                    if ((C.packed >> c) & 1u) {                // wave-uniform
+#pragma unroll
+                        for (int r = 0; r < ROWS; r++) v[c][r] = (int64_t)unpack_bits(pw[c], j0 + r, C.bits(c));
+                    } else if (c < C.ncol && !((C.lazy >> c) & 1u)) {
+                        // a column without a packed image read with the stripe: 64 consecutive rows of its byte image per load (clamped to
+                        // the last row: rows past n are out anyway)
+#pragma unroll
+                        for (int r = 0; r < ROWS; r++) {
+                            const int64_t i = rowid[r] - Cr.row0;
+                            v[c][r] = load_scalar(Cr.ptr[c], C.width(c), i < Cr.n ? i : Cr.n - 1);
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < ROWS; r++) v[c][r] = 0;
+                    }
+                }
+                process(IntTag<ROWS>{}, v, rowid, (int64_t)1 << 40, IntTag<1>{}, tile0, tile_rows);
+            }
+        }
+    } else
+#endif
 #ifdef VDL_QUEUE_FILTER
     // The QUEUE form (C.queued; specialised builds whose first filter keeps a few rows in a hundred -- Q14: one month of seven years):
     // the filter column comes with the tile and is tested there; the rows still in are queued per wave (LDS ring of row numbers), and as

@@ -102,6 +102,8 @@ struct MScanCols {                           // host-side description of a scan'
     int lazy[kMaxVCols] = {};                // projection scan: the column decides nothing about a row's survival -- read it for survivors only
     uint32_t image = 0;                      // bit c: column c is read from its frame-of-reference image (vdl_column_image.h; bounds rewritten)
     uint32_t decode = 0;                     // bit c: ... and decoded by the kernel (MsArgs::decode)
+    uint32_t packed = 0;                     // bit c: read from its bit-packed image (MsArgs::packed), pbits[c] bits per row
+    int pbits[kMaxVCols] = {};
 };
 struct MAggDesc {
     int kind = 0;                            // AGG_SUM / AGG_MIN / AGG_MAX / AGG_FIRST
@@ -175,6 +177,11 @@ struct MsArgs {
     // the QUEUE form of a specialised scan that reads late (round 4): the columns outside `lazy` (the most selective filter column) come with the
     // tile and are filtered there; the rows still in are queued per wave and everything else is read for 64 of them at a time, every lane busy
     int queued = 0;
+    // the PACKED form of a specialised global aggregate scan (vdl_column_image.h Packed): bit c: column c is read from its bit-packed
+    // image in stripes of 2048 rows (ptr[c] = the image), pbits: 6 bits per column (columns 0..9), the bits per row
+    uint32_t packed = 0;
+    uint64_t pbits = 0;
+    VDL_SD constexpr int bits(int c) const { return c < 10 ? (int)((pbits >> (6 * c)) & 63u) : 0; }
     int64_t n = 0, row0 = 0;
     int64_t rowid_base = 0;                  // what a row-id column subtracts from the global row number: row0 (ids inside this shard) or 0
     const void *ptr[kMaxVCols] = {};

@@ -432,6 +432,25 @@ class Engine:
         self._check(self._L.vdl_column_image_info(self._c, name.encode(), ctypes.byref(w), ctypes.byref(b), ctypes.byref(s)))
         return w.value, b.value, s.value
 
+    def packed_info(self, name):
+        """(bits, base, scale) of a column's bit-packed image: v = base + scale * e'; bits 0 = none"""
+        b, base, s = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._L.vdl_column_packed_info(self._c, name.encode(), ctypes.byref(b), ctypes.byref(base), ctypes.byref(s)))
+        return b.value, base.value, s.value
+
+    def download_packed(self, name):
+        """the packed image's dwords (vdl_download_packed_image) as a uint32 array"""
+        bits = self.packed_info(name)[0]
+        n = ctypes.c_int64()
+        self._check(self._L.vdl_column_info(self._c, name.encode(), None, ctypes.byref(n), None))
+        out = np.empty((n.value + 2047) // 2048 * bits * 64, dtype=np.uint32)
+        self._check(self._L.vdl_download_packed_image(self._c, name.encode(), out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
+        return out
+
+    def declare_packed(self, name, bits, base=0, scale=1):
+        """a context without a device: the column has a packed image of `bits` bits (jit_check builds the packed form over it)"""
+        self._check(self._L.vdl_declare_packed_image(self._c, name.encode(), int(bits), int(base), int(scale)))
+
     def set_column_images(self, enabled):
         """False: scans read the catalog columns and ignore their images (tests, A/B runs in one process)"""
         self._check(self._L.vdl_set_column_images(self._c, 1 if enabled else 0))

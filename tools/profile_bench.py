@@ -54,6 +54,10 @@ def pin_of(label):
         return "u=%s,late=3" % m.group(1)
     if ",lateall>" in label:                       # every filter column with the tile, the aggregate inputs late
         return "u=%s,late=4" % m.group(1)
+    if ",packed,late>" in label:                   # filter columns from their bit-packed images, the aggregate inputs late
+        return "u=%s,late=5" % m.group(1)
+    if ",packed>" in label:                        # every column from its bit-packed image
+        return "u=%s,late=6" % m.group(1)
     late = re.search(r",late(\d?)>", label)
     return "u=%s,late=%s" % (m.group(1), (late.group(1) or "1") if late else "0")
 
