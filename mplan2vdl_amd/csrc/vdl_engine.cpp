@@ -8,6 +8,7 @@
 #include <chrono>
 
 #include "vdl_genexec.h"
+#include "vdl_specialise.h"
 
 namespace {
 
@@ -68,8 +69,13 @@ int64_t plan_words(const vdl_plan *p, std::vector<int32_t> *ops, bool *shardable
     return off;
 }
 
+}  // namespace
+
+namespace vdl {
+namespace eng {
+
 // single-aggregate scans over <= 4 columns take the tuned k_scan; everything else k_mscan
-static bool use_kscan(const ScanPlan &sp) {
+bool use_kscan(const ScanPlan &sp) {
     for (const ScanColumn &c : sp.cols) if (c.kind != VC_DIRECT) return false;       // derived columns (fused join scans): k_mscan
     if (getenv("VDL_NO_KSCAN")) return false;                                         // experiments: everything through k_mscan
     return sp.aggs.size() == 1 && sp.cols.size() <= 4;
@@ -125,9 +131,16 @@ static uint32_t raw_value_uses(const std::vector<ScanColumn> &sc, const std::vec
 }
 static const std::vector<KeyStep> *key_of(const ScanPlan &) { return nullptr; }
 static const std::vector<KeyStep> *key_of(const GroupScanPlan &gp) { return &gp.key; }
+// the grouped scan's key program and pivots
+static void bind_key(const ScanPlan &, MScanDesc &) {}
+static void bind_key(const GroupScanPlan &gp, MScanDesc &d) {
+    d.nkey = (int)gp.key.size();
+    for (int k = 0; k < d.nkey; k++) d.key[k] = gp.key[(size_t)k];
+    d.pmin = gp.pmin; d.pcount = gp.pcount;
+}
 
 // "name:width ..." of the columns (bits of `which`) a bound scan reads from their images: its entry in vdl_plan_image_columns
-static std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u) {
+std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which) {
     std::string t;
     for (int k = 0; k < cols.ncol && (size_t)k < sc.size(); k++)
         if (((cols.image & which) >> k) & 1u) t += (t.empty() ? "" : " ") + sc[(size_t)k].name + ":" + std::to_string(cols.width[k]);
@@ -136,7 +149,7 @@ static std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols
 
 template <typename PlanT>
 // packed: 0 = byte images only; 1 = the filter columns from their bit-packed images (the packed form), 2 = every table column that has one
-int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0, int packed = 0) {
+int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0, int packed) {
     cols = MScanCols{};
     d = MScanDesc{};
     cols.ncol = (int)sp.cols.size();
@@ -207,464 +220,26 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
             m.fa[f.col] = a; m.fs[f.col] = s;
         }
     }
+    bind_key(sp, d);
     return n;
 }
+template int64_t bind_mscan(vdl_ctx *, const ScanPlan &, MScanCols &, MScanDesc &, int64_t *, int64_t, int);
+template int64_t bind_mscan(vdl_ctx *, const GroupScanPlan &, MScanCols &, MScanDesc &, int64_t *, int64_t, int);
 
-// Run-time specialisation of one multi-aggregate scan (vdl_jit.cpp): the shape of the precompiled variant the launch
-// configuration chose, with exactly this scan's column count, and the descriptor as constants.  On success the kernel, its
-// grid (occupancy of the specialised code) and name replace the variant's; on failure the variant stays and the note says why.
-static jit::Shape jit_shape(const MScanCols &cols, const ScanLaunch &cfg) {
-    jit::Shape sh;
-    mscan_variant_shape(cfg, &sh.nc, &sh.u, &sh.vec, &sh.grouped, &sh.der);
-    sh.nc = cols.ncol;
-    for (int k = 0; k < cols.ncol; k++) sh.der |= cols.kind[k] != VC_DIRECT;
-    const char *u = getenv(sh.grouped ? "VDL_JIT_GROUP_U" : "VDL_JIT_U");
-    if (u && atoi(u) >= 1 && atoi(u) <= 8) sh.u = atoi(u);
-    return sh;
-}
-// (",img": some columns are read from their images -- a kernel that moves other bytes than the same form over the catalog columns)
-static std::string jit_name(const jit::Shape &sh, bool image) {
-    return "k_mscan_specialised<" + std::to_string(sh.nc) + "," + std::to_string(sh.u) + "," + (sh.vec ? "vec" : "novec") + "," + (sh.grouped ? "grouped" : "global") +
-           (sh.der ? ",derived" : "") + (image ? ",img" : "") + ">";
-}
-// the precompiled kernel's name, marked the same way
+}  // namespace eng
+}  // namespace vdl
+
+namespace {
+
+// the precompiled multi-aggregate kernel's name, ",img" where some columns are read from their images (as the specialised kernels' names: vdl_specialise.cpp)
 static std::string mscan_label(const ScanLaunch &cfg, const MScanCols &cols) {
     std::string n = mscan_kernel_name(cfg);
     if (cols.image && !n.empty() && n.back() == '>') n.insert(n.size() - 1, ",img");
     return n;
 }
-// filter columns a staged form reads with the tile: 1, 2; 3 = the queue form (one); 4 = all of them (only aggregate inputs and the
-// sources of derived columns read late)
-static int eager_filters_of(int lazy) { return lazy == 3 ? 1 : lazy == 4 ? kMaxVCols : lazy; }
-// (5, 6: the packed form -- the filter columns from their bit-packed images and the aggregate inputs late from their byte images, or
-// every column from its packed image: packed_args)
-static const char *late_suffix(int lazy) {
-    return lazy == 6 ? ",packed" : lazy == 5 ? ",packed,late" : lazy == 3 ? ",queue" : lazy == 4 ? ",lateall" : lazy > 1 ? ",late2" : ",late";
-}
-struct Specialised {
-    std::shared_ptr<jit::Kernel> k;
-    int grid = 0, per_cu = 0, u = 0, lazy = 0;
-    size_t code_bytes = 0;
-    std::string name, stages, packed;
-    std::shared_ptr<MScanCols> cols;      // the packed form: its binding (packed_args), else null (the plan's)
-    std::shared_ptr<MScanDesc> desc;
-    uint32_t late = 0;                    // the packed form: columns read late (MsArgs::lazy)
-};
-// "l_discount@1 l_quantity@2 l_extendedprice@last": which table columns a staged scan reads when (MsArgs::stages)
-static std::string stages_text(const vdl_plan *p, size_t s, const MsArgs &args) {
-    const size_t ns = p->fused.scans.size();
-    const std::vector<ScanColumn> &sc = s < ns ? p->fused.scans[s].cols : p->fused.gscans[s - ns].cols;
-    std::string o;
-    for (int k = 0; k < args.ncol && k < (int)sc.size(); k++) {
-        const int st = args.stage(k);
-        if (!st) continue;
-        const std::string &name = sc[(size_t)k].name;
-        o += (o.empty() ? "" : " ") + name.substr(name.find('.') == std::string::npos ? 0 : name.find('.') + 1) + "@" +
-             (st == 15 ? std::string("last") : st == 14 ? std::string("lookups") : std::to_string(st));
-    }
-    return o;
-}
-// fraction of a table column's rows inside [lo, hi], from 16 samples of 4096 rows spread over the column
-static double sampled_selectivity(vdl_ctx *c, const void *dev, int width, int64_t n, int64_t lo, int64_t hi) {
-    if (const char *a = getenv("VDL_JIT_ASSUME_SELECTIVITY")) return atof(a);      // (tests without a GPU: vdl_plan_jit_check of staged builds)
-    if (n <= 0 || !dev || c->device < 0) return 1.0;
-    const int64_t chunk = std::min<int64_t>(4096, n), pieces = std::max<int64_t>(1, std::min<int64_t>(16, n / chunk));
-    std::vector<char> host((size_t)(chunk * width));
-    int64_t in = 0, seen = 0;
-    for (int64_t k = 0; k < pieces; k++) {
-        const int64_t at = pieces > 1 ? (n - chunk) / (pieces - 1) * k : 0;
-        if (hipMemcpy(host.data(), (const char *)dev + at * width, (size_t)(chunk * width), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return 1.0; }
-        for (int64_t i = 0; i < chunk; i++) {
-            const int64_t x = width == 8 ? ((const int64_t *)host.data())[i] : width == 4 ? ((const int32_t *)host.data())[i]
-                            : width == 2 ? ((const int16_t *)host.data())[i] : ((const int8_t *)host.data())[i];
-            in += x >= lo && x <= hi;
-        }
-        seen += chunk;
-    }
-    return seen ? (double)in / (double)seen : 1.0;
-}
-
-// Stages of a specialised scan that reads late (MsArgs::stages): the most selective filter column on table columns comes
-// with the tile, the other filter columns in order of (sampled) selectivity for the rows still in, then the sources of
-// derived columns and of the group key, and last the columns that are only aggregate inputs.  0 = nothing to defer.
-static uint64_t staged_columns(vdl_ctx *c, const MScanCols &cols, const MScanDesc &d, bool grouped, uint32_t *lazy_mask, int eager_filters = 1) {
-    uint32_t source = 0, used = 0;
-    for (int k = 0; k < cols.ncol; k++) {
-        if (cols.kind[k] == VC_DIRECT) continue;
-        if (cols.kind[k] == VC_FORM) { for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dtests[k]; f++) source |= 1u << d.form[f].col; continue; }
-        if (d.dsrc[k] >= 0) source |= 1u << d.dsrc[k];
-        if (d.dsrc2[k] >= 0) source |= 1u << d.dsrc2[k];
-    }
-    if (grouped) {
-        for (int k = 0; k < d.nkey; k++) if (d.key[k].kind == KeyStep::LOAD) source |= 1u << d.key[k].col;
-        for (int k = 0; k < d.ncomp; k++) source |= 1u << d.comp[k].col;
-    }
-    for (int j = 0; j < d.nagg; j++) if (d.agg[j].kind != AGG_FIRST) used |= d.agg[j].used;
-    std::vector<std::pair<double, int>> filters;
-    for (int k = 0; k < cols.ncol; k++)
-        if (cols.kind[k] == VC_DIRECT && cols.filtered[k])
-            filters.push_back({sampled_selectivity(c, cols.ptr[k], cols.width[k], cols.n, cols.lo[k], cols.hi[k]), k});
-    std::sort(filters.begin(), filters.end());
-    uint64_t stages = 0;
-    uint32_t lazy = 0;
-    auto put = [&](int k, int st) { stages |= (uint64_t)st << (4 * k); if (st) lazy |= 1u << k; };
-    const bool selective = !filters.empty() && filters[0].first < 0.6;
-    // (eager_filters = 2: the second most selective filter column comes with the tile as well -- when the first leaves 14 % of
-    // the rows, 71 % of the second's sectors are touched anyway and 16-byte streaming loads beat masked 8-byte ones)
-    if (selective)
-        for (size_t i = (size_t)std::max(eager_filters, 1); i < filters.size(); i++) put(filters[i].second, (int)std::min<size_t>(i - (size_t)std::max(eager_filters, 1) + 1, 3));
-    for (int k = 0; k < cols.ncol; k++) {
-        if (cols.kind[k] != VC_DIRECT || cols.filtered[k]) continue;
-        if ((source >> k) & 1u) { if (selective) put(k, 14); }
-        else if ((used >> k) & 1u) put(k, 15);
-    }
-    *lazy_mask = lazy;
-    return stages;
-}
-// The arguments of a scan's specialised form `lazy` (0: every column with the tile; 1, 2, 4: staged; 3: the queue form), or false
-// and why the form does not exist for this scan.  The tuner (build_specialised) and vdl_plan_jit_check refuse the same forms for
-// the same reasons.
-static bool specialised_args(vdl_ctx *c, const MScanCols &cols, const MScanDesc &d, bool grouped, int lazy, MsArgs &args, std::string &why) {
-    args = mscan_args(cols);
-    if (!lazy) return true;
-    args.stages = staged_columns(c, cols, d, grouped, &args.lazy, eager_filters_of(lazy));
-    if (!args.lazy) { why = "no column to read late"; return false; }
-    if (lazy == 3) {
-        // the queue form: the most selective filter column with the tile, EVERY other table column for the queued rows
-        int eager = 0;
-        for (int k = 0; k < cols.ncol; k++) {
-            if (cols.kind[k] != VC_DIRECT) continue;
-            if (!((args.lazy >> k) & 1u)) { eager++; if (!cols.filtered[k]) { why = "a column that is no filter would come with the tile"; return false; } }
-        }
-        if (eager != 1) { why = "the queue form wants exactly one filter column with the tile"; return false; }
-        args.queued = 1;
-        args.stages = 0;
-    }
-    return true;
-}
-// The packed form (lazy 5: the filter columns from their bit-packed images, the columns that are only aggregate inputs late from their
-// byte images; 6: every column from its packed image, nothing late; a column without a packed image comes from its byte image with the
-// stripe) of scan s: its own binding -- the packed columns' bounds and factors are those of the packed images -- and arguments, or
-// false and why the form does not exist for this scan.  Only global aggregate scans over table columns have it.
-static bool packed_args(vdl_ctx *c, const vdl_plan *p, size_t s, bool grouped, int lazy, int u, MScanCols &cols, MScanDesc &d, MsArgs &args, std::string &why) {
-    if (grouped || s >= p->fused.scans.size()) { why = "the packed form serves global aggregate scans only, not grouped scans"; return false; }
-    const ScanPlan &sp = p->fused.scans[s];
-    for (const ScanColumn &sc : sp.cols)
-        if (sc.kind != VC_DIRECT) { why = "the packed form serves scans over table columns only, not scans with derived columns"; return false; }
-    if (!c->images) { why = "column images are off"; return false; }
-    if (u != 1 && u != 2 && u != 4 && u != 8 && u != 16) { why = "the packed form takes 1, 2, 4, 8 or 16 row pairs per slice (a lane's 32 values of a stripe split evenly)"; return false; }
-    int64_t bpr = 0;
-    bind_mscan(c, sp, cols, d, &bpr, p->row_offset, lazy == 5 ? 1 : 2);
-    if (cols.ncol > 10) { why = "the packed form takes at most 10 columns"; return false; }
-    // (a column without a packed image is read from its byte image -- or itself -- with the stripe)
-    if (!cols.packed) { why = lazy == 5 ? "no filter column has a packed image the scan may read" : "no column has a packed image the scan may read"; return false; }
-    args = mscan_args(cols);
-    if (lazy == 5) {
-        uint32_t used = 0;
-        for (int j = 0; j < d.nagg; j++) if (d.agg[j].kind != AGG_FIRST) used |= d.agg[j].used;
-        for (int k = 0; k < cols.ncol; k++)
-            if (!((cols.packed >> k) & 1u) && !cols.filtered[k] && ((used >> k) & 1u)) { args.stages |= (uint64_t)15 << (4 * k); args.lazy |= 1u << k; }
-        if (!args.lazy) { why = "no column to read late"; return false; }
-    }
-    return true;
-}
-// "l_shipdate:12 l_discount:4": the columns a packed form reads from packed images, with their bits per row
-static std::string packed_text(const vdl_plan *p, size_t s, const MScanCols &cols) {
-    std::string o;
-    for (int k = 0; k < cols.ncol && s < p->fused.scans.size() && (size_t)k < p->fused.scans[s].cols.size(); k++) {
-        if (!((cols.packed >> k) & 1u)) continue;
-        const std::string &name = p->fused.scans[s].cols[(size_t)k].name;
-        o += (o.empty() ? "" : " ") + name.substr(name.find('.') == std::string::npos ? 0 : name.find('.') + 1) + ":" + std::to_string(cols.pbits[k]);
-    }
-    return o;
-}
-static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, int u, int lazy /* 0 | eager filter columns of the staged form */, Specialised &out, std::string &why,
-                              bool census = false) {
-    out = Specialised{};
-    jit::Shape sh = jit_shape(p->mcols[s], p->mcfg[s]);
-    if (u > 0) sh.u = u;
-    else if (lazy >= 5) sh.u = getenv("VDL_JIT_U") ? atoi(getenv("VDL_JIT_U")) : 2;      // (the packed form: up to 16 row pairs per slice)
-    sh.census = census;
-    std::vector<char> code;
-    MsArgs args;
-    const MScanCols *cols = &p->mcols[s];
-    const MScanDesc *desc = &p->mdesc[s];
-    if (lazy >= 5) {
-        // the packed form: its own binding, which replaces the plan's when the form is chosen
-        out.cols = std::make_shared<MScanCols>();
-        out.desc = std::make_shared<MScanDesc>();
-        if (!packed_args(c, p, s, grouped, lazy, sh.u, *out.cols, *out.desc, args, why)) return false;
-        out.desc->block_partials = p->mdesc[s].block_partials;
-        cols = out.cols.get();
-        desc = out.desc.get();
-    } else if (!specialised_args(c, p->mcols[s], p->mdesc[s], grouped, lazy, args, why)) return false;
-    if (!jit::compile(jit::mscan_source(args, *desc, sh), c->arch, code, why)) { why = why.substr(0, 400); return false; }
-    // a specialised scan is 10-25 KB of code; ten times that means the compiler did not fold the descriptor (it then sits in
-    // scratch memory and every descriptor-driven loop stays): such a build is slower than the precompiled kernel
-    if (code.size() > (size_t)96 << 10) { why = "the descriptor did not fold (" + std::to_string(code.size()) + " B of code)"; return false; }
-    out.k = jit::load(code, why, jit::entry_name(jit::MSCAN, args, *desc, sh));
-    if (!out.k) return false;
-    int per_cu = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, out.k->fn, 256, mscan_lds_bytes(*desc, grouped)) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 2;
-    }
-    if (per_cu > 8) per_cu = 8;
-    const int64_t tile = (int64_t)256 * 2 * sh.u;
-    int64_t grid = (int64_t)c->num_cus * per_cu;
-    // (the packed form: one wave per stripe of 2048 rows at a time, four per block)
-    const int64_t most = lazy >= 5 ? (img::stripes(cols->n) + 3) / 4 : cols->n / tile;
-    if (grid > most) grid = most;
-    if (grid < 1) grid = 1;
-    out.grid = (int)grid; out.per_cu = per_cu; out.code_bytes = code.size(); out.name = jit_name(sh, cols->image != 0); out.u = sh.u; out.lazy = lazy;
-    if (lazy) out.name.insert(out.name.size() - 1, late_suffix(lazy));
-    if (lazy) out.stages = stages_text(p, s, args);
-    if (lazy >= 5) { out.packed = packed_text(p, s, *cols); out.late = args.lazy; }
-    return true;
-}
-// the note's words on a built form: "..., read late: ...", ", packed: l_shipdate:12 ..."
-static std::string form_text(const Specialised &sp) {
-    return (sp.packed.empty() ? "" : ", packed: " + sp.packed) + (sp.stages.empty() ? "" : ", read late: " + sp.stages);
-}
-// a chosen form's kernel, grid and -- the packed form -- binding become the scan's
-static void install_form(vdl_plan *p, size_t s, const Specialised &sp) {
-    if (sp.cols) {
-        int64_t *parts = p->mdesc[s].block_partials;
-        p->mcols[s] = *sp.cols;
-        p->mdesc[s] = *sp.desc;
-        p->mdesc[s].block_partials = parts;
-    }
-    p->mcfg[s].grid = sp.grid;
-    p->mjit[s] = sp.k;
-    p->mjit_form[s].u = sp.u; p->mjit_form[s].lazy = sp.lazy;
-}
-static bool specialise_scan(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, std::string *kname) {
-    Specialised sp;
-    std::string why;
-    // (tests, profiles: VDL_JIT_LATE=1|2 forces the staged form -- with that many filter columns read with the tile, 4: all of them -- where a column allows it)
-    const int late = getenv("VDL_JIT_LATE") ? std::max(1, atoi(getenv("VDL_JIT_LATE"))) : 0;
-    // (5 | 6: the packed form, at 2 row pairs per slice unless VDL_JIT_U says otherwise; where it does not exist the note says why)
-    std::string why_late;
-    if (late && !build_specialised(c, p, s, grouped, 0, late, sp, why_late) && late >= 5) p->jit_note += "scan " + std::to_string(s) + ": no packed form (" + why_late + "); ";
-    if (!sp.k && !build_specialised(c, p, s, grouped, 0, 0, sp, why)) { p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + why + "); "; return false; }
-    install_form(p, s, sp);
-    *kname = sp.name;
-    p->jit_note += "scan " + std::to_string(s) + ": " + sp.name + ", " + std::to_string(sp.code_bytes) + " B of code, " + std::to_string(sp.per_cu) + " blocks/CU" + form_text(sp) + "; ";
-    return true;
-}
 // blocks a specialised scan may be launched with, whatever rows-per-lane the tuner settles on: the partials area is sized for it
 static int max_scan_grid(const vdl_ctx *c, const vdl_plan *p, int chosen) { return p->use_jit ? std::max(chosen, c->num_cus * 8) : chosen; }
 
-// vdl_plan_set_jit(plan, 2): at the first run, with the real columns and lookup tables in place, every specialised scan is
-// built in up to eleven forms (a second each) -- 2, 3, 4, 6 row pairs per lane, then the staged forms that read late (one or two
-// filter columns with the tile) at the winner's and at smaller shapes -- and the quickest of three timed launches stays; for a
-// single-aggregate scan the hand-tuned k_scan is timed as well.  Which one wins depends on the registers the specialised
-// code needs, on how its blocks fill the CUs and on the filters' selectivity: Q1 at SF100 measured 4.13 / 4.04 / 4.30 /
-// 3.96 ms for 2 / 3 / 4 / 6 pairs (staged: 4.1-4.2), Q6 2.7 / 2.5 / 2.4 / 2.5 ms eager, 1.63 staged, 2.38 on k_scan.
-static void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
-    const size_t ns = p->fused.scans.size(), ng = p->fused.gscans.size();
-    struct Events {                                            // (destroyed on every way out, also a throwing HIP_CHECK)
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIP_CHECK(hipEventCreate(&ev.a));
-    HIP_CHECK(hipEventCreate(&ev.b));
-    const hipEvent_t e0 = ev.a, e1 = ev.b;
-    for (size_t s = 0; s < ns + ng; s++) {
-        if (!p->mjit[s]) continue;
-        const bool grouped = s >= ns;
-        int64_t *out = dev_words + (grouped ? p->gword_offset[s - ns] : p->word_offset[s]);
-        Specialised best;
-        float best_ms = 0;
-        std::string tried;
-        // rows per lane first; then, at the winner, at 2 and at 1, the staged form that reads late (fewer rows per lane suit it:
-        // its loads depend on each other, and what hides them is more waves, not more loads per wave)
-        // (3 = the queue form: one filter column with the tile, the rows still in queued per wave and finished 64 at a time)
-        // (4 = every filter column with the tile, only aggregate inputs late: over narrow images the filter columns cost little)
-        std::vector<std::pair<int, int>> cands = {{2, 0}, {3, 0}, {4, 0}, {6, 0}, {0, 1}, {3, 1}, {2, 1}, {1, 1}, {3, 2}, {2, 2}, {4, 2}, {4, 3}, {3, 3}, {6, 3},
-                                                  {2, 4}, {3, 4}, {4, 4}};
-        // VDL_JIT_PIN="u=3,late=2" (profiles: tools/profile_bench.sh runs the form a plain run chose, and nothing else): one candidate
-        int pin_u = 0, pin_late = -1;
-        if (const char *pin = getenv("VDL_JIT_PIN")) {
-            if (const char *q = strstr(pin, "u=")) pin_u = atoi(q + 2);
-            if (const char *q = strstr(pin, "late=")) pin_late = atoi(q + 5);
-            if (pin_u > 0) cands = {{pin_u, std::max(pin_late, 0)}};
-        }
-        // then the packed forms (5: filter columns from their bit-packed images, aggregate inputs late; 6: every column packed), at 2 to
-        // 16 row pairs per slice (more rows per slice: more late loads in flight, fewer waves), with the same rule.  Not under a pin; VDL_JIT_PACKED=0 leaves them out, =only tries nothing else.
-        std::vector<std::pair<int, int>> packed_forms = {{2, 5}, {4, 5}, {8, 5}, {16, 5}, {2, 6}, {4, 6}, {8, 6}};
-        const char *packed_env = getenv("VDL_JIT_PACKED");
-        if (pin_u > 0 || (packed_env && strcmp(packed_env, "0") == 0)) packed_forms.clear();
-        else if (packed_env && strcmp(packed_env, "only") == 0) cands.clear();
-        if (!packed_forms.empty()) {                           // (forms the scan does not have are not compiled)
-            MScanCols pc;
-            auto pd = std::make_unique<MScanDesc>();
-            MsArgs pa;
-            std::string why;
-            if (!packed_args(c, p, s, grouped, 5, 2, pc, *pd, pa, why) && !packed_args(c, p, s, grouped, 6, 2, pc, *pd, pa, why)) packed_forms.clear();
-        }
-        cands.insert(cands.end(), packed_forms.begin(), packed_forms.end());
-        // (a scan that runs the packed form -- VDL_JIT_LATE=5 | 6 -- is timed in the other forms over its own binding again)
-        MScanCols cols_now = p->mcols[s];
-        auto desc_now = std::make_unique<MScanDesc>(p->mdesc[s]);
-        if (p->mjit_form[s].lazy >= 5) {
-            int64_t bpr = 0;
-            bind_mscan(c, p->fused.scans[s], p->mcols[s], p->mdesc[s], &bpr, p->row_offset);
-            p->mdesc[s].block_partials = desc_now->block_partials;
-        }
-        // a candidate's time is the MEDIAN of five launches after the module's first, and a later candidate only replaces the one
-        // in hand when it is more than 2 % quicker: forms within the noise of each other no longer swap places from run to run
-        auto median_of = [](std::vector<float> &t) { std::sort(t.begin(), t.end()); return t[t.size() / 2]; };
-        int best_u = 0;
-        for (auto &cu : cands) {
-            const int u = cu.first ? cu.first : best_u;
-            const int lazy = cu.second;
-            if (u <= 0 || (lazy < 5 && (int64_t)256 * 2 * u > p->mcols[s].n)) continue;
-            if (lazy == 1 && cu.first == best_u) continue;
-            Specialised cand;
-            std::string why;
-            if (!build_specialised(c, p, s, grouped, u, lazy, cand, why)) continue;
-            ScanLaunch cfg = p->mcfg[s];
-            cfg.grid = cand.grid;
-            const MScanCols &ccols = cand.cols ? *cand.cols : p->mcols[s];
-            const MScanDesc &cdesc = cand.desc ? *cand.desc : p->mdesc[s];
-            HIP_CHECK(hipMemcpyAsync(p->mdev[s]->p, &cdesc, sizeof(MScanDesc), hipMemcpyHostToDevice, c->stream));
-            std::vector<float> times;
-            for (int rep = 0; rep < 6; rep++) {
-                HIP_CHECK(hipEventRecord(e0, c->stream));
-                HIP_CHECK(launch_mscan(ccols, cdesc, (const MScanDesc *)p->mdev[s]->p, cfg, grouped, false, out, false, c->stream, cand.k->fn));
-                HIP_CHECK(hipEventRecord(e1, c->stream));
-                HIP_CHECK(hipEventSynchronize(e1));
-                float t = 0;
-                HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-                if (rep > 0) times.push_back(t);                // the first launch of a module pays for its load
-            }
-            const float ms = median_of(times);
-            tried += " u=" + std::to_string(u) + (lazy ? late_suffix(lazy) : "") + ":" + std::to_string((int)(ms * 1000)) + "us";
-            if (!best.k || ms < best_ms * 0.98f) { best = cand; best_ms = ms; }
-            if (!lazy && (best_u == 0 || cand.k == best.k)) best_u = u;       // the staged forms start from the quickest eager shape
-        }
-        if (!best.k) {
-            p->mcols[s] = cols_now;
-            p->mdesc[s] = *desc_now;
-            continue;
-        }
-        if (!grouped && use_kscan(p->fused.scans[s]) && p->block_partials[s] && pin_u <= 0) {
-            // the hand-tuned single-aggregate kernel is a candidate too
-            float ms = 1e30f;
-            std::vector<float> times;
-            for (int rep = 0; rep < 6; rep++) {
-                HIP_CHECK(hipEventRecord(e0, c->stream));
-                HIP_CHECK(launch_scan(p->sargs[s], p->scfg[s], c->stream));
-                HIP_CHECK(launch_scan_finish(p->sargs[s].block_partials, p->scfg[s].grid, p->sargs[s].nagg, nullptr, p->sargs[s], out, c->stream));
-                HIP_CHECK(hipEventRecord(e1, c->stream));
-                HIP_CHECK(hipEventSynchronize(e1));
-                float t = 0;
-                HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-                if (rep > 0) times.push_back(t);
-            }
-            ms = median_of(times);
-            tried += std::string(" k_scan:") + std::to_string((int)(ms * 1000)) + "us";
-            if (ms < best_ms * 0.98f) {
-                p->kscan[s] = 1;
-                p->mjit[s] = nullptr;
-                p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + scan_kernel_name(p->scfg[s]) + "; ";
-                if ((int)s == p->dominant) p->dominant_kernel = std::string(scan_kernel_name(p->scfg[s])) + "_grid" + std::to_string(p->scfg[s].grid);
-                continue;
-            }
-        }
-        install_form(p, s, best);
-        p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + best.name + (best.packed.empty() ? "" : " (packed: " + best.packed + ")") +
-                       (best.stages.empty() ? "" : " (read late: " + best.stages + ")") + "; ";
-        if ((int)s == p->dominant)
-            p->dominant_kernel = best.name + "_grid" + std::to_string(best.grid) + (grouped ? "_rep" + std::to_string(p->mdesc[s].replicas) : "");
-    }
-    p->description = describe_plan(p);
-}
-
-// HBM bytes one launch of the dominant scan moves, counted rather than modelled.  The memory side fetches whole 128-byte lines,
-// one request per line, whatever part of the line the lanes ask for (tools/ubench/fetch_calib: TCC_EA0_RDREQ = lines touched
-// for streaming, every-other-sector and random masked 16-byte loads alike; FETCH_SIZE = 64 B per request).  A scan that reads
-// every column with the tile moves its algorithmic bytes.  A staged scan (late materialisation) moves the eager columns in
-// full plus, per late column, 128 B for every line in which some row was still in when the column was read: a CENSUS build of
-// the very form that ran (same rows per lane, same stages; vdl_jit.cpp VDL_CENSUS) counts those lines in one untimed launch
-// over the real columns.  detail: "column=bytes ..." for the note.
-static int64_t scan_bytes_moved(vdl_ctx *c, vdl_plan *p, std::string &detail) {
-    if (!p->bound || p->dominant < 0) throw Error(VDL_ERR_ARG, "vdl_plan_scan_traffic: run the (fused) plan first");
-    const size_t s = (size_t)p->dominant, ns = p->fused.scans.size();
-    const bool grouped = s >= ns;
-    const std::vector<ScanColumn> &sc = grouped ? p->fused.gscans[s - ns].cols : p->fused.scans[s].cols;
-    const MScanCols &cols = p->mcols[s];
-    auto short_name = [&](int k) { const std::string &n = sc[(size_t)k].name; return n.substr(n.find('.') == std::string::npos ? 0 : n.find('.') + 1); };
-    const bool staged = !(!grouped && p->kscan[s]) && p->mjit[s] && p->mjit_form[s].lazy > 0;
-    int64_t total = 0;
-    if (!grouped && p->kscan[s]) {                             // the hand-tuned single-aggregate kernel: its own argument block
-        const ScanArgs &a = p->sargs[s];
-        for (int k = 0; k < a.ncol; k++) { total += a.n * a.width[k]; detail += short_name(k) + "=" + std::to_string(a.n * a.width[k]) + " "; }
-        detail += "(every column read with the tile)";
-        return total;
-    }
-    if (!staged) {
-        for (int k = 0; k < cols.ncol; k++)
-            if (cols.kind[k] == VC_DIRECT) { total += cols.n * cols.width[k]; detail += short_name(k) + "=" + std::to_string(cols.n * cols.width[k]) + " "; }
-        detail += "(every column read with the tile)";
-        return total;
-    }
-    Specialised cen;
-    std::string why;
-    if (p->mjit_form[s].lazy >= 5) {
-        // the packed form: every packed column in whole stripes (its padding included), the late columns' lines counted by the census
-        // build of the form that ran (same binding)
-        if (!build_specialised(c, p, s, grouped, p->mjit_form[s].u, p->mjit_form[s].lazy, cen, why, true)) throw Error(VDL_ERR_UNSUPPORTED, "the census build of the packed scan failed: " + why);
-        BufP counts = dev_alloc(c, sizeof(unsigned long long) * kMaxVCols);
-        BufP words = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(p->n_words, 1));
-        HIP_CHECK(hipMemsetAsync(counts->p, 0, sizeof(unsigned long long) * kMaxVCols, c->stream));
-        MScanDesc d = *cen.desc;
-        d.census = (unsigned long long *)counts->p;
-        BufP ddev = dev_alloc(c, sizeof(MScanDesc));
-        HIP_CHECK(hipMemcpyAsync(ddev->p, &d, sizeof d, hipMemcpyHostToDevice, c->stream));
-        ScanLaunch cfg = p->mcfg[s];
-        cfg.grid = cen.grid;
-        int64_t *out = (int64_t *)words->p + p->word_offset[s];
-        HIP_CHECK(launch_mscan(*cen.cols, d, (const MScanDesc *)ddev->p, cfg, grouped, false, out, false, c->stream, cen.k->fn));
-        unsigned long long lines[kMaxVCols] = {};
-        c->fetch_to_host(counts->p, kMaxVCols, (int64_t *)lines, c->stream);
-        const MScanCols &pc = *cen.cols;
-        for (int k = 0; k < pc.ncol; k++) {
-            const bool packed = (pc.packed >> k) & 1u, late = (cen.late >> k) & 1u;
-            const int64_t b = packed ? img::packed_dwords(pc.n, pc.pbits[k]) * 4 : late ? (int64_t)lines[k] * 128 : pc.n * pc.width[k];
-            total += b;
-            detail += short_name(k) + "=" + std::to_string(b) + (packed ? "(packed: " + std::to_string(pc.pbits[k]) + " bits) " :
-                                                                   late ? "(late: " + std::to_string(lines[k]) + " lines of " + std::to_string((pc.n * pc.width[k] + 127) / 128) + ") " : " ");
-        }
-        detail += "(census of " + cen.name + ")";
-        return total;
-    }
-    if (!build_specialised(c, p, s, grouped, p->mjit_form[s].u, p->mjit_form[s].lazy, cen, why, true)) throw Error(VDL_ERR_UNSUPPORTED, "the census build of the staged scan failed: " + why);
-    BufP counts = dev_alloc(c, sizeof(unsigned long long) * kMaxVCols);
-    BufP words = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(p->n_words, 1));
-    HIP_CHECK(hipMemsetAsync(counts->p, 0, sizeof(unsigned long long) * kMaxVCols, c->stream));
-    MScanDesc d = p->mdesc[s];
-    d.census = (unsigned long long *)counts->p;
-    BufP ddev = dev_alloc(c, sizeof(MScanDesc));
-    HIP_CHECK(hipMemcpyAsync(ddev->p, &d, sizeof d, hipMemcpyHostToDevice, c->stream));
-    ScanLaunch cfg = p->mcfg[s];
-    cfg.grid = cen.grid;
-    int64_t *out = (int64_t *)words->p + (grouped ? p->gword_offset[s - ns] : p->word_offset[s]);
-    HIP_CHECK(launch_mscan(cols, d, (const MScanDesc *)ddev->p, cfg, grouped, false, out, false, c->stream, cen.k->fn));
-    unsigned long long lines[kMaxVCols] = {};
-    c->fetch_to_host(counts->p, kMaxVCols, (int64_t *)lines, c->stream);
-    const MsArgs args = [&] { MsArgs a = mscan_args(cols); uint32_t lz = 0; a.stages = staged_columns(c, cols, p->mdesc[s], grouped, &lz, eager_filters_of(p->mjit_form[s].lazy)); a.lazy = lz; return a; }();
-    for (int k = 0; k < cols.ncol; k++) {
-        if (cols.kind[k] != VC_DIRECT) continue;
-        const bool late = (args.lazy >> k) & 1u;
-        const int64_t b = late ? (int64_t)lines[k] * 128 : cols.n * cols.width[k];
-        total += b;
-        detail += short_name(k) + "=" + std::to_string(b) + (late ? "(late: " + std::to_string(lines[k]) + " lines of " + std::to_string((cols.n * cols.width[k] + 127) / 128) + ") " : " ");
-    }
-    detail += "(census of " + cen.name + ", full tiles)";
-    return total;
-}
 
 void bind_fused(vdl_ctx *c, vdl_plan *p) {
     const FusedPlan &F = p->fused;
@@ -679,7 +254,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
     p->mparts.assign(ns + ng, nullptr);
     p->mdev.resize(ns + ng);
     p->mjit.assign(ns + ng, nullptr);
-    p->mjit_form.assign(ns + ng, vdl_plan::JitForm{});
+    p->mjit_form.assign(ns + ng, ScanForm{});
     p->kscan.assign(ns + ng, 0);
     p->jit_note.clear();
     for (auto it = p->image_roles.begin(); it != p->image_roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->image_roles.erase(it) : std::next(it);
@@ -750,9 +325,6 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         const int64_t n = bind_mscan(c, gp, p->mcols[m], p->mdesc[m], &bpr, p->row_offset);
         p->image_roles["scan" + std::to_string(m)] = image_text(gp.cols, p->mcols[m]);
         MScanDesc &d = p->mdesc[m];
-        d.nkey = (int)gp.key.size();
-        for (int k = 0; k < d.nkey; k++) d.key[k] = gp.key[(size_t)k];
-        d.pmin = gp.pmin; d.pcount = gp.pcount;
         p->mcfg[m] = mscan_launch_config(p->mcols[m], d, true, c->num_cus);
         if (p->mcfg[m].variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no grouped-scan kernel variant for this shape");
         std::string jname;
@@ -829,9 +401,42 @@ static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vecto
     return n;
 }
 
+// One specialised pass of the projection scan: its translation unit, its entry point and what the note calls it
+struct PassSource { std::string source, label; const char *entry; };
+// the select pass (dimension and semi-join scans are the select pass with bitmap_only set)
+static PassSource select_pass(const MScanCols &cols, const MScanDesc &d) {
+    jit::Shape sh;
+    sh.nc = cols.ncol; sh.u = 4; sh.vec = project_select_vec(cols); sh.der = true;
+    return {jit::scan_source(jit::SELECT, mscan_args(cols), d, sh), std::string(jit::entry_name(jit::SELECT)) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + ">",
+            jit::entry_name(jit::SELECT)};
+}
+// the one-pass front: two descriptors in one kernel (jit::front_source)
+static PassSource one_pass_front(const MScanCols &scols, const MScanDesc &sd, const MScanCols &tcols, const MScanDesc &td) {
+    jit::Shape sh;
+    sh.nc = scols.ncol; sh.u = 4; sh.vec = project_select_vec(scols); sh.der = true;
+    return {jit::front_source(mscan_args(scols), sd, mscan_args(tcols), td, sh, tcols.ncol),
+            std::string(jit::entry_name(jit::FRONT)) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ((scols.image | tcols.image) ? ",img" : "") + ">",
+            jit::entry_name(jit::FRONT)};
+}
+// Compiles the pass and writes its line of the note: "role: entry<shape[,img]>, N B of code; ".  A run loads the kernel and falls back
+// to the precompiled one where it did not build ("role: not specialised (why); ", nullptr); vdl_plan_jit_check (`check`) loads
+// nothing and throws
+static std::shared_ptr<jit::Kernel> build_pass(vdl_ctx *c, vdl_plan *p, const std::string &role, const PassSource &ps, bool check) {
+    std::vector<char> code;
+    std::string why;
+    std::shared_ptr<jit::Kernel> k;
+    const bool built = jit::compile(ps.source, c->arch, code, why);
+    if (check && !built) throw Error(VDL_ERR_UNSUPPORTED, role + " does not build: " + why.substr(0, 2000));
+    if (built && !check) k = jit::load(code, why, ps.entry);
+    if (k || check) p->jit_note += role + ": " + ps.label + ", " + std::to_string(code.size()) + " B of code; ";
+    else p->jit_note += role + ": not specialised (" + why.substr(0, 400) + "); ";
+    return k;
+}
 // The projection scan's passes specialised for this plan (vdl_plan_set_jit): built at the first run after a catalog change,
-// kept by role ("select", "take", "dim<k>"); nullptr = the precompiled kernel (not asked for, or it did not build: the note says).
-static hipFunction_t front_kernel(vdl_ctx *c, vdl_plan *p, const std::string &role, jit::Kind kind, const MScanCols &cols, const MScanDesc &d) {
+// kept by role ("front", "dim<k>", "semi<k>"); nullptr = the precompiled kernel (not asked for, or it did not build: the note says).
+// (`source` is only called when the pass is built)
+template <typename MakeSource>
+static hipFunction_t front_kernel(vdl_ctx *c, vdl_plan *p, const std::string &role, MakeSource &&source) {
     if (!p->use_jit) return nullptr;
     vdl_plan::FrontKernel &fk = p->front_jit[role];
     if (fk.version == c->binding_version()) return fk.k ? fk.k->fn : nullptr;
@@ -841,35 +446,7 @@ static hipFunction_t front_kernel(vdl_ctx *c, vdl_plan *p, const std::string &ro
     }
     fk.version = c->binding_version();
     fk.k = nullptr;
-    jit::Shape sh;
-    sh.nc = cols.ncol; sh.u = 4; sh.vec = kind == jit::SELECT ? project_select_vec(cols) : false; sh.der = true;
-    std::vector<char> code;
-    std::string why;
-    if (jit::compile(jit::scan_source(kind, mscan_args(cols), d, sh), c->arch, code, why)) fk.k = jit::load(code, why, jit::entry_name(kind));
-    if (fk.k) p->jit_note += role + ": " + jit::entry_name(kind) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + ">, " + std::to_string(code.size()) + " B of code; ";
-    else p->jit_note += role + ": not specialised (" + why.substr(0, 400) + "); ";
-    return fk.k ? fk.k->fn : nullptr;
-}
-
-// the one-pass front specialised for this plan: two descriptors in one kernel (jit::front_source)
-static hipFunction_t front_kernel_one_pass(vdl_ctx *c, vdl_plan *p, const MScanCols &scols, const MScanDesc &sd, const MScanCols &tcols, const MScanDesc &td) {
-    if (!p->use_jit) return nullptr;
-    const std::string role = "front";
-    vdl_plan::FrontKernel &fk = p->front_jit[role];
-    if (fk.version == c->binding_version()) return fk.k ? fk.k->fn : nullptr;
-    {
-        const size_t at = p->jit_note.find(role + ": ");
-        if (at != std::string::npos) { const size_t end = p->jit_note.find("; ", at); p->jit_note.erase(at, end == std::string::npos ? std::string::npos : end + 2 - at); }
-    }
-    fk.version = c->binding_version();
-    fk.k = nullptr;
-    jit::Shape sh;
-    sh.nc = scols.ncol; sh.u = 4; sh.vec = project_select_vec(scols); sh.der = true;
-    std::vector<char> code;
-    std::string why;
-    if (jit::compile(jit::front_source(mscan_args(scols), sd, mscan_args(tcols), td, sh, tcols.ncol), c->arch, code, why)) fk.k = jit::load(code, why, jit::entry_name(jit::FRONT));
-    if (fk.k) p->jit_note += role + ": " + jit::entry_name(jit::FRONT) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ((scols.image | tcols.image) ? ",img" : "") + ">, " + std::to_string(code.size()) + " B of code; ";
-    else p->jit_note += role + ": not specialised (" + why.substr(0, 400) + "); ";
+    fk.k = build_pass(c, p, role, source(), false);
     return fk.k ? fk.k->fn : nullptr;
 }
 
@@ -954,7 +531,7 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
             p->prelude_rows[k] = n;
             d->out_ptr[0] = (int64_t *)p->prelude_buf[k]->p;
             HIP_CHECK(launch_project_select(cols, desc_on_device(c, p, "semi" + std::to_string(k), *d), c->num_cus, c->stream,
-                                            front_kernel(c, p, "semi" + std::to_string(k), jit::SELECT, cols, *d)));
+                                            front_kernel(c, p, "semi" + std::to_string(k), [&] { return select_pass(cols, *d); })));
             continue;
         }
         const size_t words = (size_t)std::max<int64_t>((n + 63) >> 6, 1);
@@ -964,7 +541,7 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         d->out_ptr[0] = (int64_t *)p->prelude_buf[k]->p;           // bitmap only: no positions, no counts
         d->bitmap_only = 1;
         HIP_CHECK(launch_project_select(cols, desc_on_device(c, p, "dim" + std::to_string(k), *d), c->num_cus, c->stream,
-                                        front_kernel(c, p, "dim" + std::to_string(k), jit::SELECT, cols, *d)));
+                                        front_kernel(c, p, "dim" + std::to_string(k), [&] { return select_pass(cols, *d); })));
     }
 }
 // hand the tables to a scan that looks them up
@@ -1338,7 +915,7 @@ bool run_projection(vdl_ctx *c, vdl_plan *p, std::map<int, DVec> &over) {
         auto pass = [&]() -> int64_t {
             if (back) *(volatile int64_t *)back = -1;
             HIP_CHECK(launch_project_front(scols, desc_on_device(c, p, "select", *sdesc), cols, desc_on_device(c, p, "take", d), look->p, (int64_t *)total->p, back,
-                                           c->num_cus, c->stream, front_kernel_one_pass(c, p, scols, *sdesc, cols, d)));
+                                           c->num_cus, c->stream, front_kernel(c, p, "front", [&] { return one_pass_front(scols, *sdesc, cols, d); })));
             // the host goes on as soon as it knows the number -- while the kernel's other batches still fetch their survivors --: what it
             // queues next runs behind the kernel anyway
             int64_t got = 0;
@@ -1753,15 +1330,6 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
         if (!p->fused.ok && p->fused.proj.ok) {
             // the fused front of a plan that does not fuse as a whole: both passes of the projection scan, and the dimension
             // scans its prelude holds
-            auto build = [&](const std::string &role, jit::Kind kind, const MScanCols &cols, const MScanDesc &d) {
-                jit::Shape sh;
-                sh.nc = cols.ncol; sh.u = 4; sh.vec = kind == jit::SELECT ? project_select_vec(cols) : false; sh.der = true;
-                std::vector<char> code;
-                std::string log;
-                if (!jit::compile(jit::scan_source(kind, mscan_args(cols), d, sh), c->arch, code, log))
-                    throw Error(VDL_ERR_UNSUPPORTED, role + " does not build: " + log.substr(0, 2000));
-                p->jit_note += role + ": " + jit::entry_name(kind) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + ">, " + std::to_string(code.size()) + " B of code; ";
-            };
             const FusedPlan &F = p->fused;
             for (size_t k = 0; k < F.prelude.size(); k++) {
                 const PreludeItem &it = F.prelude[k];
@@ -1776,70 +1344,14 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
                 p->image_roles[role] = image_text(it.cols, cols);
                 d->bitmap_only = semi ? 2 : 1;
                 if (semi) { d->pmin = it.modulus; d->nout = 1; d->out_col[0] = it.index_col; }
-                build(role, jit::SELECT, cols, *d);
+                build_pass(c, p, role, select_pass(cols, *d), true);
             }
             FrontBound fb;
             bind_front(c, p, fb);
-            {
-                jit::Shape sh;
-                sh.nc = fb.scols.ncol; sh.u = 4; sh.vec = project_select_vec(fb.scols); sh.der = true;
-                std::vector<char> code;
-                std::string log;
-                if (!jit::compile(jit::front_source(mscan_args(fb.scols), *fb.sdesc, mscan_args(fb.cols), *fb.d, sh, fb.cols.ncol), c->arch, code, log))
-                    throw Error(VDL_ERR_UNSUPPORTED, "front does not build: " + log.substr(0, 2000));
-                p->jit_note += std::string("front: ") + jit::entry_name(jit::FRONT) + "<" + std::to_string(sh.nc) + "," + std::to_string(fb.cols.ncol) +
-                               ((fb.scols.image | fb.cols.image) ? ",img" : "") + ">, " + std::to_string(code.size()) + " B of code; ";
-            }
+            build_pass(c, p, "front", one_pass_front(fb.scols, *fb.sdesc, fb.cols, *fb.d), true);
             return;
         }
-        if (!p->fused.ok) throw Error(VDL_ERR_UNSUPPORTED, "the plan has no fused scans: " + p->fused.why_not);
-        const FusedPlan &F = p->fused;
-        const size_t ns = F.scans.size();
-        for (size_t s = 0; s < ns + F.gscans.size(); s++) {
-            const bool grouped = s >= ns;
-            MScanCols cols;
-            auto d = std::make_unique<MScanDesc>();
-            int64_t bpr = 0;
-            if (grouped) {
-                const GroupScanPlan &gp = F.gscans[s - ns];
-                bind_mscan(c, gp, cols, *d, &bpr, 0);
-                p->image_roles["scan" + std::to_string(s)] = image_text(gp.cols, cols);
-                d->nkey = (int)gp.key.size();
-                for (int k = 0; k < d->nkey; k++) d->key[k] = gp.key[(size_t)k];
-                d->pmin = gp.pmin; d->pcount = gp.pcount;
-            } else {
-                bind_mscan(c, F.scans[s], cols, *d, &bpr, 0);
-                p->image_roles["scan" + std::to_string(s)] = image_text(F.scans[s].cols, cols);
-            }
-            const ScanLaunch cfg = mscan_launch_config(cols, *d, grouped, c->num_cus);
-            if (cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no scan kernel variant for this shape");
-            jit::Shape sh = jit_shape(cols, cfg);
-            if (getenv("VDL_JIT_CENSUS")) sh.census = true;              // (tests: the measurement build of a staged scan compiles too)
-            std::vector<char> code;
-            std::string log;
-            // the staged or queue form of the same scan (VDL_JIT_LATE as in specialise_scan), refused where the tuner refuses it
-            const int late = getenv("VDL_JIT_LATE") ? std::max(1, atoi(getenv("VDL_JIT_LATE"))) : 0;
-            MsArgs args;
-            if (late >= 5) {
-                // the packed form (5 | 6, as build_specialised: 2 row pairs per slice unless VDL_JIT_U says otherwise), over its own binding
-                sh.u = getenv("VDL_JIT_U") ? atoi(getenv("VDL_JIT_U")) : 2;
-                MScanCols pc;
-                if (!packed_args(c, p, s, grouped, late, sh.u, pc, *d, args, log)) {
-                    p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + log + "); ";
-                    continue;
-                }
-                cols = pc;
-            } else if (!specialised_args(c, cols, *d, grouped, late, args, log)) {
-                p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + log + "); ";
-                continue;
-            }
-            if (!jit::compile(jit::mscan_source(args, *d, sh), c->arch, code, log))
-                throw Error(VDL_ERR_UNSUPPORTED, "scan " + std::to_string(s) + " does not build: " + log.substr(0, 2000));
-            std::string name = jit_name(sh, cols.image != 0);
-            if (args.packed) name.insert(name.size() - 1, late_suffix(late));
-            p->jit_note += "scan " + std::to_string(s) + ": " + name + (args.packed ? " (packed: " + packed_text(p, s, cols) + ")" : "") +
-                           (args.queued ? " (queue)" : args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";
-        }
+        jit_check_scans(c, p);
     });
 }
 // ---- ORDER BY / LIMIT (vdl_plan_set_order) -----------------------------------------------------------------------------------

@@ -23,6 +23,7 @@
 #include "vdl_ir.h"
 #include "vdl_jit.h"
 #include "vdl_kernels.h"
+#include "vdl_scan_form.h"
 
 
 namespace vdl {
@@ -274,8 +275,7 @@ struct vdl_plan {
     bool use_jit = false;                    // vdl_plan_set_jit / VDL_JIT=1: scans specialised for this plan by hiprtc (vdl_jit.cpp)
     bool jit_tune = false, jit_tuned = false;   // ... =2: rows per lane chosen by timing at the first run
     std::vector<std::shared_ptr<vdl::jit::Kernel>> mjit;
-    struct JitForm { int u = 0, lazy = 0; };     // rows per lane / filter columns read with the tile (0 = not staged) of mjit[s]
-    std::vector<JitForm> mjit_form;
+    std::vector<ScanForm> mjit_form;         // the form mjit[s] was built in, with the row pairs per lane it runs at
     struct FrontKernel { uint64_t version = 0; std::shared_ptr<vdl::jit::Kernel> k; };
     std::map<std::string, FrontKernel> front_jit;   // specialised passes of the projection scan / dimension scans, by role
     std::vector<std::shared_ptr<vdl::MScanDesc>> host_descs;     // dimension scans of the current run (copied to the device asynchronously)
@@ -446,6 +446,13 @@ inline const Column &find_col(vdl_ctx *c, const std::string &name) {
 }
 
 std::string describe_plan(const vdl_plan *p);
+// vdl_engine.cpp, for vdl_specialise.cpp: a scan's binding (packed: 0 = byte images only; 1 = the filter columns from their bit-packed
+// images, 2 = every table column that has one; instantiated there for ScanPlan and GroupScanPlan), which scans the hand-tuned k_scan
+// serves, and a binding's entry in vdl_plan_image_columns
+template <typename PlanT>
+int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0, int packed = 0);
+bool use_kscan(const ScanPlan &sp);
+std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
 // sharded entry points refuse a plan with an order set
 inline void refuse_order_sharded(const vdl_plan *p) {
     if (p->order.set)

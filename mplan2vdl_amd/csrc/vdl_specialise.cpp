@@ -1,0 +1,474 @@
+// vdl_specialise.cpp -- run-time specialisation of the fused aggregate scans (vdl_jit.cpp compiles; the forms: vdl_scan_form.h):
+// binding a scan in a form, building it, choosing a form at bind time (VDL_JIT_LATE) or by timing at the first run (the tuner),
+// counting the bytes the chosen form moves, and vdl_plan_jit_check's builds without a GPU.  All of it is host-side orchestration.
+#include "vdl_specialise.h"
+
+namespace vdl {
+namespace eng {
+
+// Run-time specialisation of one multi-aggregate scan (vdl_jit.cpp): the shape of the precompiled variant the launch
+// configuration chose, with exactly this scan's column count, and the descriptor as constants.  On success the kernel, its
+// grid (occupancy of the specialised code) and name replace the variant's; on failure the variant stays and the note says why.
+// (f.u, where the form names one, replaces the variant's row pairs per lane)
+static jit::Shape jit_shape(const MScanCols &cols, const ScanLaunch &cfg, const ScanForm &f) {
+    jit::Shape sh;
+    mscan_variant_shape(cfg, &sh.nc, &sh.u, &sh.vec, &sh.grouped, &sh.der);
+    sh.nc = cols.ncol;
+    for (int k = 0; k < cols.ncol; k++) sh.der |= cols.kind[k] != VC_DIRECT;
+    const char *u = getenv(sh.grouped ? "VDL_JIT_GROUP_U" : "VDL_JIT_U");
+    if (u && atoi(u) >= 1 && atoi(u) <= 8) sh.u = atoi(u);
+    if (f.u > 0) sh.u = f.u;
+    else if (f.kind == ScanForm::PACKED) sh.u = getenv("VDL_JIT_U") ? atoi(getenv("VDL_JIT_U")) : 2;      // (the packed form: up to 16 row pairs per slice)
+    return sh;
+}
+// (",img": some columns are read from their images -- a kernel that moves other bytes than the same form over the catalog columns)
+static std::string jit_name(const jit::Shape &sh, bool image) {
+    return "k_mscan_specialised<" + std::to_string(sh.nc) + "," + std::to_string(sh.u) + "," + (sh.vec ? "vec" : "novec") + "," + (sh.grouped ? "grouped" : "global") +
+           (sh.der ? ",derived" : "") + (image ? ",img" : "") + ">";
+}
+// (tests, profiles: VDL_JIT_LATE=1|2 forces the staged form -- with that many filter columns read with the tile, 4: all of them -- where a column allows it;
+// 5 | 6: the packed form, at 2 row pairs per slice unless VDL_JIT_U says otherwise)
+static ScanForm form_asked_for() { return getenv("VDL_JIT_LATE") ? ScanForm::from_code(std::max(1, atoi(getenv("VDL_JIT_LATE")))) : ScanForm{}; }
+
+static const std::vector<ScanColumn> &scan_columns(const vdl_plan *p, size_t s) {
+    const size_t ns = p->fused.scans.size();
+    return s < ns ? p->fused.scans[s].cols : p->fused.gscans[s - ns].cols;
+}
+// a column's name without its table
+static std::string short_name(const std::string &name) { return name.substr(name.find('.') == std::string::npos ? 0 : name.find('.') + 1); }
+// "l_discount@1 l_quantity@2 l_extendedprice@last": which table columns a staged scan reads when (MsArgs::stages)
+static std::string stages_text(const vdl_plan *p, size_t s, const MsArgs &args) {
+    const std::vector<ScanColumn> &sc = scan_columns(p, s);
+    std::string o;
+    for (int k = 0; k < args.ncol && k < (int)sc.size(); k++) {
+        const int st = args.stage(k);
+        if (!st) continue;
+        o += (o.empty() ? "" : " ") + short_name(sc[(size_t)k].name) + "@" + (st == 15 ? std::string("last") : st == 14 ? std::string("lookups") : std::to_string(st));
+    }
+    return o;
+}
+// "l_shipdate:12 l_discount:4": the columns a packed form reads from packed images, with their bits per row
+static std::string packed_text(const vdl_plan *p, size_t s, const MScanCols &cols) {
+    const std::vector<ScanColumn> &sc = scan_columns(p, s);
+    std::string o;
+    for (int k = 0; k < cols.ncol && (size_t)k < sc.size(); k++)
+        if ((cols.packed >> k) & 1u) o += (o.empty() ? "" : " ") + short_name(sc[(size_t)k].name) + ":" + std::to_string(cols.pbits[k]);
+    return o;
+}
+// fraction of a table column's rows inside [lo, hi], from 16 samples of 4096 rows spread over the column
+static double sampled_selectivity(vdl_ctx *c, const void *dev, int width, int64_t n, int64_t lo, int64_t hi) {
+    if (const char *a = getenv("VDL_JIT_ASSUME_SELECTIVITY")) return atof(a);      // (tests without a GPU: vdl_plan_jit_check of staged builds)
+    if (n <= 0 || !dev || c->device < 0) return 1.0;
+    const int64_t chunk = std::min<int64_t>(4096, n), pieces = std::max<int64_t>(1, std::min<int64_t>(16, n / chunk));
+    std::vector<char> host((size_t)(chunk * width));
+    int64_t in = 0, seen = 0;
+    for (int64_t k = 0; k < pieces; k++) {
+        const int64_t at = pieces > 1 ? (n - chunk) / (pieces - 1) * k : 0;
+        if (hipMemcpy(host.data(), (const char *)dev + at * width, (size_t)(chunk * width), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return 1.0; }
+        for (int64_t i = 0; i < chunk; i++) {
+            const int64_t x = width == 8 ? ((const int64_t *)host.data())[i] : width == 4 ? ((const int32_t *)host.data())[i]
+                            : width == 2 ? ((const int16_t *)host.data())[i] : ((const int8_t *)host.data())[i];
+            in += x >= lo && x <= hi;
+        }
+        seen += chunk;
+    }
+    return seen ? (double)in / (double)seen : 1.0;
+}
+
+// Stages of a specialised scan that reads late (MsArgs::stages): the most selective filter column on table columns comes
+// with the tile, the other filter columns in order of (sampled) selectivity for the rows still in, then the sources of
+// derived columns and of the group key, and last the columns that are only aggregate inputs.  0 = nothing to defer.
+static uint64_t staged_columns(vdl_ctx *c, const MScanCols &cols, const MScanDesc &d, bool grouped, uint32_t *lazy_mask, int eager_filters = 1) {
+    uint32_t source = 0, used = 0;
+    for (int k = 0; k < cols.ncol; k++) {
+        if (cols.kind[k] == VC_DIRECT) continue;
+        if (cols.kind[k] == VC_FORM) { for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dtests[k]; f++) source |= 1u << d.form[f].col; continue; }
+        if (d.dsrc[k] >= 0) source |= 1u << d.dsrc[k];
+        if (d.dsrc2[k] >= 0) source |= 1u << d.dsrc2[k];
+    }
+    if (grouped) {
+        for (int k = 0; k < d.nkey; k++) if (d.key[k].kind == KeyStep::LOAD) source |= 1u << d.key[k].col;
+        for (int k = 0; k < d.ncomp; k++) source |= 1u << d.comp[k].col;
+    }
+    for (int j = 0; j < d.nagg; j++) if (d.agg[j].kind != AGG_FIRST) used |= d.agg[j].used;
+    std::vector<std::pair<double, int>> filters;
+    for (int k = 0; k < cols.ncol; k++)
+        if (cols.kind[k] == VC_DIRECT && cols.filtered[k])
+            filters.push_back({sampled_selectivity(c, cols.ptr[k], cols.width[k], cols.n, cols.lo[k], cols.hi[k]), k});
+    std::sort(filters.begin(), filters.end());
+    uint64_t stages = 0;
+    uint32_t lazy = 0;
+    auto put = [&](int k, int st) { stages |= (uint64_t)st << (4 * k); if (st) lazy |= 1u << k; };
+    const bool selective = !filters.empty() && filters[0].first < 0.6;
+    // (eager_filters = 2: the second most selective filter column comes with the tile as well -- when the first leaves 14 % of
+    // the rows, 71 % of the second's sectors are touched anyway and 16-byte streaming loads beat masked 8-byte ones)
+    if (selective)
+        for (size_t i = (size_t)std::max(eager_filters, 1); i < filters.size(); i++) put(filters[i].second, (int)std::min<size_t>(i - (size_t)std::max(eager_filters, 1) + 1, 3));
+    for (int k = 0; k < cols.ncol; k++) {
+        if (cols.kind[k] != VC_DIRECT || cols.filtered[k]) continue;
+        if ((source >> k) & 1u) { if (selective) put(k, 14); }
+        else if ((used >> k) & 1u) put(k, 15);
+    }
+    *lazy_mask = lazy;
+    return stages;
+}
+
+// What a form of a scan runs over -- its binding: columns and descriptor -- and the kernel arguments of the form
+struct BoundForm {
+    const MScanCols *cols = nullptr;          // the binding the caller handed in or, the packed forms, `own`
+    const MScanDesc *desc = nullptr;
+    std::shared_ptr<MScanCols> own_cols;
+    std::shared_ptr<MScanDesc> own_desc;
+    MsArgs args;
+};
+// Scan s in form f at u row pairs: the binding the form runs over and its arguments, or false and why the form does not exist for
+// this scan.  The tuner (build_specialised), the census and vdl_plan_jit_check refuse the same forms for the same reasons.
+// The eager, staged and queue forms run over the binding handed in (cols, d: the plan's, or vdl_plan_jit_check's own).
+// The packed form (the filter columns from their bit-packed images, the columns that are only aggregate inputs late from their byte
+// images; every_column: every column from its packed image, nothing late; a column without a packed image comes from its byte image
+// with the stripe) has its own binding -- the packed columns' bounds and factors are those of the packed images.  Only global
+// aggregate scans over table columns have it.
+static bool bind_form(vdl_ctx *c, const vdl_plan *p, size_t s, bool grouped, const ScanForm &f, int u, const MScanCols &cols, const MScanDesc &d, BoundForm &out,
+                      std::string &why) {
+    out = BoundForm{};
+    if (f.kind != ScanForm::PACKED) {
+        out.cols = &cols;
+        out.desc = &d;
+        out.args = mscan_args(cols);
+        if (f.kind == ScanForm::EAGER) return true;
+        MsArgs &args = out.args;
+        args.stages = staged_columns(c, cols, d, grouped, &args.lazy, f.kind == ScanForm::QUEUE ? 1 : f.eager_filters);
+        if (!args.lazy) { why = "no column to read late"; return false; }
+        if (f.kind == ScanForm::QUEUE) {
+            // the queue form: the most selective filter column with the tile, EVERY other table column for the queued rows
+            int eager = 0;
+            for (int k = 0; k < cols.ncol; k++) {
+                if (cols.kind[k] != VC_DIRECT) continue;
+                if (!((args.lazy >> k) & 1u)) { eager++; if (!cols.filtered[k]) { why = "a column that is no filter would come with the tile"; return false; } }
+            }
+            if (eager != 1) { why = "the queue form wants exactly one filter column with the tile"; return false; }
+            args.queued = 1;
+            args.stages = 0;
+        }
+        return true;
+    }
+    if (grouped || s >= p->fused.scans.size()) { why = "the packed form serves global aggregate scans only, not grouped scans"; return false; }
+    const ScanPlan &sp = p->fused.scans[s];
+    for (const ScanColumn &sc : sp.cols)
+        if (sc.kind != VC_DIRECT) { why = "the packed form serves scans over table columns only, not scans with derived columns"; return false; }
+    if (!c->images) { why = "column images are off"; return false; }
+    if (u != 1 && u != 2 && u != 4 && u != 8 && u != 16) { why = "the packed form takes 1, 2, 4, 8 or 16 row pairs per slice (a lane's 32 values of a stripe split evenly)"; return false; }
+    out.own_cols = std::make_shared<MScanCols>();
+    out.own_desc = std::make_shared<MScanDesc>();
+    MScanCols &pc = *out.own_cols;
+    MScanDesc &pd = *out.own_desc;
+    int64_t bpr = 0;
+    bind_mscan(c, sp, pc, pd, &bpr, p->row_offset, f.every_column ? 2 : 1);
+    pd.block_partials = d.block_partials;
+    out.cols = &pc;
+    out.desc = &pd;
+    if (pc.ncol > 10) { why = "the packed form takes at most 10 columns"; return false; }
+    // (a column without a packed image is read from its byte image -- or itself -- with the stripe)
+    if (!pc.packed) { why = f.every_column ? "no column has a packed image the scan may read" : "no filter column has a packed image the scan may read"; return false; }
+    out.args = mscan_args(pc);
+    if (!f.every_column) {
+        MsArgs &args = out.args;
+        uint32_t used = 0;
+        for (int j = 0; j < pd.nagg; j++) if (pd.agg[j].kind != AGG_FIRST) used |= pd.agg[j].used;
+        for (int k = 0; k < pc.ncol; k++)
+            if (!((pc.packed >> k) & 1u) && !pc.filtered[k] && ((used >> k) & 1u)) { args.stages |= (uint64_t)15 << (4 * k); args.lazy |= 1u << k; }
+        if (!args.lazy) { why = "no column to read late"; return false; }
+    }
+    return true;
+}
+
+// a scan built and loaded in one form
+struct Specialised {
+    std::shared_ptr<jit::Kernel> k;
+    int grid = 0, per_cu = 0;
+    ScanForm form;                        // (u: the row pairs per lane it was built at)
+    size_t code_bytes = 0;
+    std::string name, stages, packed;
+    BoundForm b;                          // the binding it was built over -- which becomes the plan's when the form is chosen -- and its arguments
+};
+// (cols, d: the byte-image binding of the scan -- the plan's, unless the plan runs a packed form: tune_specialised)
+static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, const ScanForm &f, const MScanCols &cols, const MScanDesc &d, Specialised &out, std::string &why,
+                              bool census = false) {
+    out = Specialised{};
+    jit::Shape sh = jit_shape(cols, p->mcfg[s], f);
+    sh.census = census;
+    std::vector<char> code;
+    if (!bind_form(c, p, s, grouped, f, sh.u, cols, d, out.b, why)) return false;
+    const MsArgs &args = out.b.args;
+    const MScanDesc &desc = *out.b.desc;
+    if (!jit::compile(jit::mscan_source(args, desc, sh), c->arch, code, why)) { why = why.substr(0, 400); return false; }
+    // a specialised scan is 10-25 KB of code; ten times that means the compiler did not fold the descriptor (it then sits in
+    // scratch memory and every descriptor-driven loop stays): such a build is slower than the precompiled kernel
+    if (code.size() > (size_t)96 << 10) { why = "the descriptor did not fold (" + std::to_string(code.size()) + " B of code)"; return false; }
+    out.k = jit::load(code, why, jit::entry_name(jit::MSCAN, args, desc, sh));
+    if (!out.k) return false;
+    int per_cu = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, out.k->fn, 256, mscan_lds_bytes(desc, grouped)) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = 2;
+    }
+    if (per_cu > 8) per_cu = 8;
+    const int64_t tile = (int64_t)256 * 2 * sh.u;
+    int64_t grid = (int64_t)c->num_cus * per_cu;
+    // (the packed form: one wave per stripe of 2048 rows at a time, four per block)
+    const int64_t most = f.kind == ScanForm::PACKED ? (img::stripes(out.b.cols->n) + 3) / 4 : out.b.cols->n / tile;
+    if (grid > most) grid = most;
+    if (grid < 1) grid = 1;
+    out.grid = (int)grid; out.per_cu = per_cu; out.code_bytes = code.size(); out.form = f; out.form.u = sh.u;
+    out.name = jit_name(sh, out.b.cols->image != 0);
+    out.name.insert(out.name.size() - 1, f.suffix());
+    out.stages = stages_text(p, s, args);
+    out.packed = packed_text(p, s, *out.b.cols);
+    return true;
+}
+// the note's words on a built form: "..., read late: ...", ", packed: l_shipdate:12 ..."
+static std::string form_text(const Specialised &sp) {
+    return (sp.packed.empty() ? "" : ", packed: " + sp.packed) + (sp.stages.empty() ? "" : ", read late: " + sp.stages);
+}
+// a chosen form's kernel, grid and binding become the scan's (the partials area stays the plan's)
+static void install_form(vdl_plan *p, size_t s, const Specialised &sp) {
+    int64_t *parts = p->mdesc[s].block_partials;
+    p->mcols[s] = *sp.b.cols;
+    p->mdesc[s] = *sp.b.desc;
+    p->mdesc[s].block_partials = parts;
+    p->mcfg[s].grid = sp.grid;
+    p->mjit[s] = sp.k;
+    p->mjit_form[s] = sp.form;
+}
+bool specialise_scan(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, std::string *kname) {
+    Specialised sp;
+    std::string why;
+    // (where the packed form does not exist the note says why)
+    const ScanForm late = form_asked_for();
+    std::string why_late;
+    if (late.kind != ScanForm::EAGER && !build_specialised(c, p, s, grouped, late, p->mcols[s], p->mdesc[s], sp, why_late) && late.kind == ScanForm::PACKED)
+        p->jit_note += "scan " + std::to_string(s) + ": no packed form (" + why_late + "); ";
+    if (!sp.k && !build_specialised(c, p, s, grouped, ScanForm{}, p->mcols[s], p->mdesc[s], sp, why)) { p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + why + "); "; return false; }
+    install_form(p, s, sp);
+    *kname = sp.name;
+    p->jit_note += "scan " + std::to_string(s) + ": " + sp.name + ", " + std::to_string(sp.code_bytes) + " B of code, " + std::to_string(sp.per_cu) + " blocks/CU" + form_text(sp) + "; ";
+    return true;
+}
+
+// vdl_plan_set_jit(plan, 2): at the first run, with the real columns and lookup tables in place, every specialised scan is
+// built in up to eleven forms (a second each) -- 2, 3, 4, 6 row pairs per lane, then the staged forms that read late (one or two
+// filter columns with the tile) at the winner's and at smaller shapes -- and the quickest of three timed launches stays; for a
+// single-aggregate scan the hand-tuned k_scan is timed as well.  Which one wins depends on the registers the specialised
+// code needs, on how its blocks fill the CUs and on the filters' selectivity: Q1 at SF100 measured 4.13 / 4.04 / 4.30 /
+// 3.96 ms for 2 / 3 / 4 / 6 pairs (staged: 4.1-4.2), Q6 2.7 / 2.5 / 2.4 / 2.5 ms eager, 1.63 staged, 2.38 on k_scan.
+void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
+    const size_t ns = p->fused.scans.size(), ng = p->fused.gscans.size();
+    struct Events {                                            // (destroyed on every way out, also a throwing HIP_CHECK)
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    HIP_CHECK(hipEventCreate(&ev.a));
+    HIP_CHECK(hipEventCreate(&ev.b));
+    // a candidate's time is the MEDIAN of five launches after the module's first, and a later candidate only replaces the one
+    // in hand when it is more than 2 % quicker: forms within the noise of each other no longer swap places from run to run
+    auto median_ms = [&](auto &&launch) {
+        std::vector<float> times;
+        for (int rep = 0; rep < 6; rep++) {
+            HIP_CHECK(hipEventRecord(ev.a, c->stream));
+            launch();
+            HIP_CHECK(hipEventRecord(ev.b, c->stream));
+            HIP_CHECK(hipEventSynchronize(ev.b));
+            float t = 0;
+            HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+            if (rep > 0) times.push_back(t);                    // the first launch of a module pays for its load
+        }
+        std::sort(times.begin(), times.end());
+        return times[times.size() / 2];
+    };
+    for (size_t s = 0; s < ns + ng; s++) {
+        if (!p->mjit[s]) continue;
+        const bool grouped = s >= ns;
+        int64_t *out = dev_words + (grouped ? p->gword_offset[s - ns] : p->word_offset[s]);
+        Specialised best;
+        float best_ms = 0;
+        std::string tried;
+        // {row pairs per lane (0: the quickest eager shape's), form as ScanForm::from_code}
+        // rows per lane first; then, at the winner, at 2 and at 1, the staged form that reads late (fewer rows per lane suit it:
+        // its loads depend on each other, and what hides them is more waves, not more loads per wave)
+        // (3 = the queue form: one filter column with the tile, the rows still in queued per wave and finished 64 at a time)
+        // (4 = every filter column with the tile, only aggregate inputs late: over narrow images the filter columns cost little)
+        std::vector<std::pair<int, int>> cands = {{2, 0}, {3, 0}, {4, 0}, {6, 0}, {0, 1}, {3, 1}, {2, 1}, {1, 1}, {3, 2}, {2, 2}, {4, 2}, {4, 3}, {3, 3}, {6, 3},
+                                                  {2, 4}, {3, 4}, {4, 4}};
+        // VDL_JIT_PIN="u=3,late=2" (profiles: tools/profile_bench.sh runs the form a plain run chose, and nothing else): one candidate
+        int pin_u = 0, pin_late = -1;
+        if (const char *pin = getenv("VDL_JIT_PIN")) {
+            if (const char *q = strstr(pin, "u=")) pin_u = atoi(q + 2);
+            if (const char *q = strstr(pin, "late=")) pin_late = atoi(q + 5);
+            if (pin_u > 0) cands = {{pin_u, std::max(pin_late, 0)}};
+        }
+        // then the packed forms (5: filter columns from their bit-packed images, aggregate inputs late; 6: every column packed), at 2 to
+        // 16 row pairs per slice (more rows per slice: more late loads in flight, fewer waves), with the same rule.  Not under a pin; VDL_JIT_PACKED=0 leaves them out, =only tries nothing else.
+        std::vector<std::pair<int, int>> packed_forms = {{2, 5}, {4, 5}, {8, 5}, {16, 5}, {2, 6}, {4, 6}, {8, 6}};
+        const char *packed_env = getenv("VDL_JIT_PACKED");
+        if (pin_u > 0 || (packed_env && strcmp(packed_env, "0") == 0)) packed_forms.clear();
+        else if (packed_env && strcmp(packed_env, "only") == 0) cands.clear();
+        if (!packed_forms.empty()) {                           // (forms the scan does not have are not compiled)
+            BoundForm b;
+            std::string why;
+            if (!bind_form(c, p, s, grouped, ScanForm::from_code(5), 2, p->mcols[s], p->mdesc[s], b, why) &&
+                !bind_form(c, p, s, grouped, ScanForm::from_code(6), 2, p->mcols[s], p->mdesc[s], b, why)) packed_forms.clear();
+        }
+        cands.insert(cands.end(), packed_forms.begin(), packed_forms.end());
+        // the forms without a binding of their own run over the scan's byte-image binding: the plan's, or -- a scan that runs the
+        // packed form now (VDL_JIT_LATE=5 | 6) -- one made here
+        const MScanCols *cols = &p->mcols[s];
+        const MScanDesc *desc = &p->mdesc[s];
+        MScanCols plain_cols;
+        std::unique_ptr<MScanDesc> plain_desc;
+        if (p->mjit_form[s].kind == ScanForm::PACKED) {
+            plain_desc = std::make_unique<MScanDesc>();
+            int64_t bpr = 0;
+            bind_mscan(c, p->fused.scans[s], plain_cols, *plain_desc, &bpr, p->row_offset);
+            plain_desc->block_partials = p->mdesc[s].block_partials;
+            cols = &plain_cols;
+            desc = plain_desc.get();
+        }
+        int best_u = 0;
+        for (auto &cu : cands) {
+            const ScanForm f = ScanForm::from_code(cu.second, cu.first ? cu.first : best_u);
+            if (f.u <= 0 || (f.kind != ScanForm::PACKED && (int64_t)256 * 2 * f.u > cols->n)) continue;
+            if (f.kind == ScanForm::STAGED && f.eager_filters == 1 && cu.first == best_u) continue;      // ({0, 1} ran it)
+            Specialised cand;
+            std::string why;
+            if (!build_specialised(c, p, s, grouped, f, *cols, *desc, cand, why)) continue;
+            ScanLaunch cfg = p->mcfg[s];
+            cfg.grid = cand.grid;
+            HIP_CHECK(hipMemcpyAsync(p->mdev[s]->p, cand.b.desc, sizeof(MScanDesc), hipMemcpyHostToDevice, c->stream));
+            const float ms = median_ms([&] { HIP_CHECK(launch_mscan(*cand.b.cols, *cand.b.desc, (const MScanDesc *)p->mdev[s]->p, cfg, grouped, false, out, false, c->stream, cand.k->fn)); });
+            tried += " u=" + std::to_string(f.u) + f.suffix() + ":" + std::to_string((int)(ms * 1000)) + "us";
+            if (!best.k || ms < best_ms * 0.98f) { best = cand; best_ms = ms; }
+            if (f.kind == ScanForm::EAGER && (best_u == 0 || cand.k == best.k)) best_u = f.u;       // the staged forms start from the quickest eager shape
+        }
+        if (!best.k) continue;
+        if (!grouped && use_kscan(p->fused.scans[s]) && p->block_partials[s] && pin_u <= 0) {
+            // the hand-tuned single-aggregate kernel is a candidate too
+            const float ms = median_ms([&] {
+                HIP_CHECK(launch_scan(p->sargs[s], p->scfg[s], c->stream));
+                HIP_CHECK(launch_scan_finish(p->sargs[s].block_partials, p->scfg[s].grid, p->sargs[s].nagg, nullptr, p->sargs[s], out, c->stream));
+            });
+            tried += std::string(" k_scan:") + std::to_string((int)(ms * 1000)) + "us";
+            if (ms < best_ms * 0.98f) {
+                p->kscan[s] = 1;
+                p->mjit[s] = nullptr;
+                p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + scan_kernel_name(p->scfg[s]) + "; ";
+                if ((int)s == p->dominant) p->dominant_kernel = std::string(scan_kernel_name(p->scfg[s])) + "_grid" + std::to_string(p->scfg[s].grid);
+                continue;
+            }
+        }
+        install_form(p, s, best);
+        p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + best.name + (best.packed.empty() ? "" : " (packed: " + best.packed + ")") +
+                       (best.stages.empty() ? "" : " (read late: " + best.stages + ")") + "; ";
+        if ((int)s == p->dominant)
+            p->dominant_kernel = best.name + "_grid" + std::to_string(best.grid) + (grouped ? "_rep" + std::to_string(p->mdesc[s].replicas) : "");
+    }
+    p->description = describe_plan(p);
+}
+
+// HBM bytes one launch of the dominant scan moves, counted rather than modelled.  The memory side fetches whole 128-byte lines,
+// one request per line, whatever part of the line the lanes ask for (tools/ubench/fetch_calib: TCC_EA0_RDREQ = lines touched
+// for streaming, every-other-sector and random masked 16-byte loads alike; FETCH_SIZE = 64 B per request).  A scan that reads
+// every column with the tile moves its algorithmic bytes.  A staged scan (late materialisation) moves the eager columns in
+// full plus, per late column, 128 B for every line in which some row was still in when the column was read: a CENSUS build of
+// the very form that ran (same rows per lane, same stages; vdl_jit.cpp VDL_CENSUS) counts those lines in one untimed launch
+// over the real columns.  detail: "column=bytes ..." for the note.
+int64_t scan_bytes_moved(vdl_ctx *c, vdl_plan *p, std::string &detail) {
+    if (!p->bound || p->dominant < 0) throw Error(VDL_ERR_ARG, "vdl_plan_scan_traffic: run the (fused) plan first");
+    const size_t s = (size_t)p->dominant, ns = p->fused.scans.size();
+    const bool grouped = s >= ns;
+    const std::vector<ScanColumn> &sc = scan_columns(p, s);
+    const bool staged = !(!grouped && p->kscan[s]) && p->mjit[s] && p->mjit_form[s].kind != ScanForm::EAGER;
+    int64_t total = 0;
+    if (!grouped && p->kscan[s]) {                             // the hand-tuned single-aggregate kernel: its own argument block
+        const ScanArgs &a = p->sargs[s];
+        for (int k = 0; k < a.ncol; k++) { total += a.n * a.width[k]; detail += short_name(sc[(size_t)k].name) + "=" + std::to_string(a.n * a.width[k]) + " "; }
+        detail += "(every column read with the tile)";
+        return total;
+    }
+    if (!staged) {
+        const MScanCols &cols = p->mcols[s];
+        for (int k = 0; k < cols.ncol; k++)
+            if (cols.kind[k] == VC_DIRECT) { total += cols.n * cols.width[k]; detail += short_name(sc[(size_t)k].name) + "=" + std::to_string(cols.n * cols.width[k]) + " "; }
+        detail += "(every column read with the tile)";
+        return total;
+    }
+    // the census build of the form that ran, over the same binding.  The packed form: every packed column in whole stripes (its padding
+    // included), the late columns' lines counted
+    const bool packed_form = p->mjit_form[s].kind == ScanForm::PACKED;
+    Specialised cen;
+    std::string why;
+    if (!build_specialised(c, p, s, grouped, p->mjit_form[s], p->mcols[s], p->mdesc[s], cen, why, true))
+        throw Error(VDL_ERR_UNSUPPORTED, std::string("the census build of the ") + (packed_form ? "packed" : "staged") + " scan failed: " + why);
+    BufP counts = dev_alloc(c, sizeof(unsigned long long) * kMaxVCols);
+    BufP words = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(p->n_words, 1));
+    HIP_CHECK(hipMemsetAsync(counts->p, 0, sizeof(unsigned long long) * kMaxVCols, c->stream));
+    const MScanCols &cols = *cen.b.cols;
+    MScanDesc d = *cen.b.desc;
+    d.census = (unsigned long long *)counts->p;
+    BufP ddev = dev_alloc(c, sizeof(MScanDesc));
+    HIP_CHECK(hipMemcpyAsync(ddev->p, &d, sizeof d, hipMemcpyHostToDevice, c->stream));
+    ScanLaunch cfg = p->mcfg[s];
+    cfg.grid = cen.grid;
+    int64_t *out = (int64_t *)words->p + (grouped ? p->gword_offset[s - ns] : p->word_offset[s]);
+    HIP_CHECK(launch_mscan(cols, d, (const MScanDesc *)ddev->p, cfg, grouped, false, out, false, c->stream, cen.k->fn));
+    unsigned long long lines[kMaxVCols] = {};
+    c->fetch_to_host(counts->p, kMaxVCols, (int64_t *)lines, c->stream);
+    for (int k = 0; k < cols.ncol; k++) {
+        if (cols.kind[k] != VC_DIRECT) continue;
+        const bool packed = (cols.packed >> k) & 1u, late = (cen.b.args.lazy >> k) & 1u;
+        const int64_t b = packed ? img::packed_dwords(cols.n, cols.pbits[k]) * 4 : late ? (int64_t)lines[k] * 128 : cols.n * cols.width[k];
+        total += b;
+        detail += short_name(sc[(size_t)k].name) + "=" + std::to_string(b) + (packed ? "(packed: " + std::to_string(cols.pbits[k]) + " bits) " :
+                                                                               late ? "(late: " + std::to_string(lines[k]) + " lines of " + std::to_string((cols.n * cols.width[k] + 127) / 128) + ") " : " ");
+    }
+    detail += "(census of " + cen.name + (packed_form ? ")" : ", full tiles)");
+    return total;
+}
+
+// Builds (hiprtc; no GPU needed) the specialised kernel of every multi-aggregate scan of the plan against the columns
+// registered now, without loading or running anything: the note lists each kernel with its code size, or why it failed.
+void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
+    if (!p->fused.ok) throw Error(VDL_ERR_UNSUPPORTED, "the plan has no fused scans: " + p->fused.why_not);
+    const FusedPlan &F = p->fused;
+    const size_t ns = F.scans.size();
+    for (size_t s = 0; s < ns + F.gscans.size(); s++) {
+        const bool grouped = s >= ns;
+        MScanCols cols;
+        auto d = std::make_unique<MScanDesc>();
+        int64_t bpr = 0;
+        if (grouped) bind_mscan(c, F.gscans[s - ns], cols, *d, &bpr, 0);
+        else bind_mscan(c, F.scans[s], cols, *d, &bpr, 0);
+        p->image_roles["scan" + std::to_string(s)] = image_text(scan_columns(p, s), cols);
+        const ScanLaunch cfg = mscan_launch_config(cols, *d, grouped, c->num_cus);
+        if (cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no scan kernel variant for this shape");
+        // the staged, queue or packed form of the same scan (VDL_JIT_LATE as in specialise_scan), refused where the tuner refuses it
+        const ScanForm late = form_asked_for();
+        jit::Shape sh = jit_shape(cols, cfg, late);
+        if (getenv("VDL_JIT_CENSUS")) sh.census = true;              // (tests: the measurement build of a staged scan compiles too)
+        std::vector<char> code;
+        std::string log;
+        BoundForm b;
+        if (!bind_form(c, p, s, grouped, late, sh.u, cols, *d, b, log)) {
+            p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + log + "); ";
+            continue;
+        }
+        if (!jit::compile(jit::mscan_source(b.args, *b.desc, sh), c->arch, code, log))
+            throw Error(VDL_ERR_UNSUPPORTED, "scan " + std::to_string(s) + " does not build: " + log.substr(0, 2000));
+        std::string name = jit_name(sh, b.cols->image != 0);
+        if (b.args.packed) name.insert(name.size() - 1, late.suffix());
+        p->jit_note += "scan " + std::to_string(s) + ": " + name + (b.args.packed ? " (packed: " + packed_text(p, s, *b.cols) + ")" : "") +
+                       (b.args.queued ? " (queue)" : b.args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";
+    }
+}
+
+}  // namespace eng
+}  // namespace vdl

@@ -2,7 +2,7 @@
 the row counts where its tile logic branches; the precompiled variants the JIT-off path can select; and columns whose
 frame-of-reference images sit exactly on the width limits of csrc/vdl_column_image.h.
 
-The tuner (vdl_engine.cpp: tune_specialised) times its candidates and keeps the quickest, so which form runs in a tuned
+The tuner (vdl_specialise.cpp: tune_specialised) times its candidates and keeps the quickest, so which form runs in a tuned
 benchmark is decided by timing, not by the suite.  VDL_JIT_PIN leaves the tuner one candidate: the tests here pin each
 (rows per lane u, staged form) pair in turn.  A form that does not exist for a scan (build_specialised refuses it) is
 dropped by the tuner without a word; REFUSED lists every such refusal the tests expect, with its reason, and both the GPU
@@ -304,8 +304,8 @@ def program(name, n=None):
 
 # ---- CPU: the tables above against the rules and the planner ----------------------------------------------------------------
 def test_forms_are_the_tuners_candidates():
-    """FORMS covers the tuner's candidate list (vdl_engine.cpp: tune_specialised), read from the source"""
-    src = open(os.path.join(ROOT, "mplan2vdl_amd", "csrc", "vdl_engine.cpp")).read()
+    """FORMS covers the tuner's candidate list (vdl_specialise.cpp: tune_specialised), read from the source"""
+    src = open(os.path.join(ROOT, "mplan2vdl_amd", "csrc", "vdl_specialise.cpp")).read()
     body = re.search(r"std::vector<std::pair<int, int>> cands = \{(.*?)\};", src, re.S).group(1)
     cands = [(int(a), int(b)) for a, b in re.findall(r"\{(\d+), (\d+)\}", body)]
     assert len(cands) == 17, cands
