@@ -150,6 +150,20 @@ int  vdl_plan_set_fusion(vdl_plan *plan, int enabled);
  * (no GPU needed): VDL_OK, or VDL_ERR_UNSUPPORTED with the compiler's message in vdl_last_error.
  * (The reference hands its text to an engine that generates code per program: /root/reference/README.md:57.) */
 int  vdl_plan_set_jit(vdl_plan *plan, int enabled);
+/* Filter bounds of the specialised code at run time.  By default the specialised code holds every literal of the query, so Q6
+ * for another year is another translation unit for every form the tuner tries and no cache ever hits.  at_run_time = 1: the
+ * generated code holds the SHAPE of each range filter and formula test only -- no lower bound, no upper bound, both, or a point
+ * (lo = hi: one equality compare); a bound at or beyond the end of the domain its column is read in counts as absent -- and
+ * reads the values from the plan's descriptor in device memory by scalar loads.  Plans that differ in bound values alone then
+ * share source, cache key and code object: the second one compiles nothing.  A change of shape or of structure (which columns
+ * are read late, a filter that vanishes) compiles anew.  Everything else stays a constant of the code.  Off by default
+ * (VDL_JIT_BOUNDS=runtime in the environment switches it on for every plan parsed afterwards); kernels built this way carry
+ * ",rtb" in the names vdl_plan_jit_note lists.  Takes effect at the plan's next run or vdl_plan_jit_check. */
+int  vdl_plan_set_jit_bounds(vdl_plan *plan, int at_run_time);
+/* Builds of specialised code in this process so far: compiled by hiprtc, read from $VDL_JIT_CACHE, found in memory.  Any pointer
+ * may be null.  (vdl_plan_jit_note also says, per scan of a plan that ran, how many of its builds came from a cache:
+ * "from cache: 2 of 3 builds of scan 0; ".) */
+void vdl_jit_counters(int64_t *compiled, int64_t *from_disk, int64_t *from_memory);
 const char *vdl_plan_jit_note(const vdl_plan *plan);
 int  vdl_plan_jit_check(vdl_ctx *ctx, vdl_plan *plan);
 /* Which catalog columns the plan's scans read from their images, as bound at its last run or vdl_plan_jit_check: one entry

@@ -257,6 +257,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
     p->mjit_form.assign(ns + ng, ScanForm{});
     p->kscan.assign(ns + ng, 0);
     p->jit_note.clear();
+    p->jit_builds.clear();
     for (auto it = p->image_roles.begin(); it != p->image_roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->image_roles.erase(it) : std::next(it);
     p->jit_tuned = false;
     p->gword_offset.assign(ng, 0);
@@ -404,32 +405,37 @@ static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vecto
 // One specialised pass of the projection scan: its translation unit, its entry point and what the note calls it
 struct PassSource { std::string source, label; const char *entry; };
 // the select pass (dimension and semi-join scans are the select pass with bitmap_only set)
-static PassSource select_pass(const MScanCols &cols, const MScanDesc &d) {
+// (rt: the plan's bounds at run time, vdl_plan_set_jit_bounds -- ",rtb" in the label)
+static PassSource select_pass(const MScanCols &cols, const MScanDesc &d, bool rt) {
     jit::Shape sh;
-    sh.nc = cols.ncol; sh.u = 4; sh.vec = project_select_vec(cols); sh.der = true;
-    return {jit::scan_source(jit::SELECT, mscan_args(cols), d, sh), std::string(jit::entry_name(jit::SELECT)) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + ">",
-            jit::entry_name(jit::SELECT)};
+    sh.nc = cols.ncol; sh.u = 4; sh.vec = project_select_vec(cols); sh.der = true; sh.rt_bounds = rt;
+    return {jit::scan_source(jit::SELECT, mscan_args(cols), d, sh),
+            std::string(jit::entry_name(jit::SELECT)) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + (rt ? ",rtb" : "") + ">", jit::entry_name(jit::SELECT)};
 }
 // the one-pass front: two descriptors in one kernel (jit::front_source)
-static PassSource one_pass_front(const MScanCols &scols, const MScanDesc &sd, const MScanCols &tcols, const MScanDesc &td) {
+static PassSource one_pass_front(const MScanCols &scols, const MScanDesc &sd, const MScanCols &tcols, const MScanDesc &td, bool rt) {
     jit::Shape sh;
-    sh.nc = scols.ncol; sh.u = 4; sh.vec = project_select_vec(scols); sh.der = true;
+    sh.nc = scols.ncol; sh.u = 4; sh.vec = project_select_vec(scols); sh.der = true; sh.rt_bounds = rt;
     return {jit::front_source(mscan_args(scols), sd, mscan_args(tcols), td, sh, tcols.ncol),
-            std::string(jit::entry_name(jit::FRONT)) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ((scols.image | tcols.image) ? ",img" : "") + ">",
+            std::string(jit::entry_name(jit::FRONT)) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ((scols.image | tcols.image) ? ",img" : "") + (rt ? ",rtb" : "") + ">",
             jit::entry_name(jit::FRONT)};
 }
 // Compiles the pass and writes its line of the note: "role: entry<shape[,img]>, N B of code; ".  A run loads the kernel and falls back
 // to the precompiled one where it did not build ("role: not specialised (why); ", nullptr); vdl_plan_jit_check (`check`) loads
 // nothing and throws
-static std::shared_ptr<jit::Kernel> build_pass(vdl_ctx *c, vdl_plan *p, const std::string &role, const PassSource &ps, bool check) {
+// (said: what was appended to the note, for a later rebuild of the role to take out again)
+static std::shared_ptr<jit::Kernel> build_pass(vdl_ctx *c, vdl_plan *p, const std::string &role, const PassSource &ps, bool check, std::string *said = nullptr) {
     std::vector<char> code;
     std::string why;
     std::shared_ptr<jit::Kernel> k;
-    const bool built = jit::compile(ps.source, c->arch, code, why);
+    jit::Origin from = jit::COMPILED;
+    const bool built = jit::compile(ps.source, c->arch, code, why, &from);
     if (check && !built) throw Error(VDL_ERR_UNSUPPORTED, role + " does not build: " + why.substr(0, 2000));
     if (built && !check) k = jit::load(code, why, ps.entry);
-    if (k || check) p->jit_note += role + ": " + ps.label + ", " + std::to_string(code.size()) + " B of code; ";
-    else p->jit_note += role + ": not specialised (" + why.substr(0, 400) + "); ";
+    std::string line = k || check ? role + ": " + ps.label + ", " + std::to_string(code.size()) + " B of code; " : role + ": not specialised (" + why.substr(0, 400) + "); ";
+    if (built && !check) { count_build(p, role, from); line += builds_text(p, role); }
+    p->jit_note += line;
+    if (said) *said = line;
     return k;
 }
 // The projection scan's passes specialised for this plan (vdl_plan_set_jit): built at the first run after a catalog change,
@@ -440,13 +446,15 @@ static hipFunction_t front_kernel(vdl_ctx *c, vdl_plan *p, const std::string &ro
     if (!p->use_jit) return nullptr;
     vdl_plan::FrontKernel &fk = p->front_jit[role];
     if (fk.version == c->binding_version()) return fk.k ? fk.k->fn : nullptr;
-    {   // a rebuild after a catalog change: this role's old line leaves the note
-        const size_t at = p->jit_note.find(role + ": ");
-        if (at != std::string::npos) { const size_t end = p->jit_note.find("; ", at); p->jit_note.erase(at, end == std::string::npos ? std::string::npos : end + 2 - at); }
+    if (!fk.said.empty()) {   // a rebuild after a catalog change: what the role said last time (its line and its builds) leaves the note
+        const size_t at = p->jit_note.find(fk.said);
+        if (at != std::string::npos) p->jit_note.erase(at, fk.said.size());
+        fk.said.clear();
+        p->jit_builds.erase(role);
     }
     fk.version = c->binding_version();
     fk.k = nullptr;
-    fk.k = build_pass(c, p, role, source(), false);
+    fk.k = build_pass(c, p, role, source(), false, &fk.said);
     return fk.k ? fk.k->fn : nullptr;
 }
 
@@ -531,7 +539,7 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
             p->prelude_rows[k] = n;
             d->out_ptr[0] = (int64_t *)p->prelude_buf[k]->p;
             HIP_CHECK(launch_project_select(cols, desc_on_device(c, p, "semi" + std::to_string(k), *d), c->num_cus, c->stream,
-                                            front_kernel(c, p, "semi" + std::to_string(k), [&] { return select_pass(cols, *d); })));
+                                            front_kernel(c, p, "semi" + std::to_string(k), [&] { return select_pass(cols, *d, p->jit_rt_bounds); })));
             continue;
         }
         const size_t words = (size_t)std::max<int64_t>((n + 63) >> 6, 1);
@@ -541,7 +549,7 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         d->out_ptr[0] = (int64_t *)p->prelude_buf[k]->p;           // bitmap only: no positions, no counts
         d->bitmap_only = 1;
         HIP_CHECK(launch_project_select(cols, desc_on_device(c, p, "dim" + std::to_string(k), *d), c->num_cus, c->stream,
-                                        front_kernel(c, p, "dim" + std::to_string(k), [&] { return select_pass(cols, *d); })));
+                                        front_kernel(c, p, "dim" + std::to_string(k), [&] { return select_pass(cols, *d, p->jit_rt_bounds); })));
     }
 }
 // hand the tables to a scan that looks them up
@@ -915,7 +923,7 @@ bool run_projection(vdl_ctx *c, vdl_plan *p, std::map<int, DVec> &over) {
         auto pass = [&]() -> int64_t {
             if (back) *(volatile int64_t *)back = -1;
             HIP_CHECK(launch_project_front(scols, desc_on_device(c, p, "select", *sdesc), cols, desc_on_device(c, p, "take", d), look->p, (int64_t *)total->p, back,
-                                           c->num_cus, c->stream, front_kernel(c, p, "front", [&] { return one_pass_front(scols, *sdesc, cols, d); })));
+                                           c->num_cus, c->stream, front_kernel(c, p, "front", [&] { return one_pass_front(scols, *sdesc, cols, d, p->jit_rt_bounds); })));
             // the host goes on as soon as it knows the number -- while the kernel's other batches still fetch their survivors --: what it
             // queues next runs behind the kernel anyway
             int64_t got = 0;
@@ -1283,6 +1291,7 @@ int vdl_parse(vdl_ctx *c, const char *text, size_t len, vdl_plan **out) {
         rewrite_program(p->prog);
         p->fused = fuse_program(p->prog);
         { const char *j = getenv("VDL_JIT"); p->use_jit = j && *j && *j != '0'; p->jit_tune = p->use_jit && atoi(j) >= 2; }
+        { const char *b = getenv("VDL_JIT_BOUNDS"); p->jit_rt_bounds = b && strcmp(b, "runtime") == 0; }
         p->description = describe_plan(p.get());
         *out = p.release();
     });
@@ -1312,6 +1321,17 @@ int vdl_plan_set_jit(vdl_plan *p, int enabled) {
     p->description = describe_plan(p);
     return VDL_OK;
 }
+int vdl_plan_set_jit_bounds(vdl_plan *p, int at_run_time) {
+    if (!p) return VDL_ERR_ARG;
+    if (p->jit_rt_bounds != (at_run_time != 0)) {             // other code: the scans are bound and built again, the front's passes too
+        p->bound = false;
+        p->jit_tuned = false;
+        p->front_jit.clear();
+    }
+    p->jit_rt_bounds = at_run_time != 0;
+    return VDL_OK;
+}
+void vdl_jit_counters(int64_t *compiled, int64_t *from_disk, int64_t *from_memory) { vdl::jit::counters(compiled, from_disk, from_memory); }
 const char *vdl_plan_jit_note(const vdl_plan *p) { return p ? p->jit_note.c_str() : ""; }
 int vdl_plan_image_columns(const vdl_plan *p, const char **list) {
     if (!p || !list) return VDL_ERR_ARG;
@@ -1344,11 +1364,11 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
                 p->image_roles[role] = image_text(it.cols, cols);
                 d->bitmap_only = semi ? 2 : 1;
                 if (semi) { d->pmin = it.modulus; d->nout = 1; d->out_col[0] = it.index_col; }
-                build_pass(c, p, role, select_pass(cols, *d), true);
+                build_pass(c, p, role, select_pass(cols, *d, p->jit_rt_bounds), true);
             }
             FrontBound fb;
             bind_front(c, p, fb);
-            build_pass(c, p, "front", one_pass_front(fb.scols, *fb.sdesc, fb.cols, *fb.d), true);
+            build_pass(c, p, "front", one_pass_front(fb.scols, *fb.sdesc, fb.cols, *fb.d, p->jit_rt_bounds), true);
             return;
         }
         jit_check_scans(c, p);

@@ -274,9 +274,14 @@ struct vdl_plan {
     std::vector<BufP> mparts, mdev;
     bool use_jit = false;                    // vdl_plan_set_jit / VDL_JIT=1: scans specialised for this plan by hiprtc (vdl_jit.cpp)
     bool jit_tune = false, jit_tuned = false;   // ... =2: rows per lane chosen by timing at the first run
+    // vdl_plan_set_jit_bounds / VDL_JIT_BOUNDS=runtime: the specialised code reads the values of range filters and formula tests from
+    // the launch's descriptor (jit::Shape::rt_bounds): plans that differ in their literals alone share its source, key and code
+    bool jit_rt_bounds = false;
+    // builds of specialised code for this plan, by role ("scan 0", "front", "dim3"): {all, of which found in a cache}
+    std::map<std::string, std::pair<int, int>> jit_builds;
     std::vector<std::shared_ptr<vdl::jit::Kernel>> mjit;
     std::vector<ScanForm> mjit_form;         // the form mjit[s] was built in, with the row pairs per lane it runs at
-    struct FrontKernel { uint64_t version = 0; std::shared_ptr<vdl::jit::Kernel> k; };
+    struct FrontKernel { uint64_t version = 0; std::shared_ptr<vdl::jit::Kernel> k; std::string said; };   // said: the role's part of jit_note, as appended
     std::map<std::string, FrontKernel> front_jit;   // specialised passes of the projection scan / dimension scans, by role
     std::vector<std::shared_ptr<vdl::MScanDesc>> host_descs;     // dimension scans of the current run (copied to the device asynchronously)
     std::shared_ptr<void> front_keep;                        // the fused front's bound descriptors of the current run, likewise

@@ -16,6 +16,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <atomic>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -186,10 +187,66 @@ bool branchy_late() {
     return e && atoi(e) != 0;
 }
 
+// ---- run-time bounds (Shape::rt_bounds) -----------------------------------------------------------------------------------
+// The generated text then holds the SHAPE of every range -- which sides are open, whether it is a point -- and no value: the
+// kernel reads the values from the launch's descriptor (vdl_mscan_body.h range_bounds), and plans that differ in their literals
+// alone yield one source, one cache entry, one kernel.  A side is open when its bound lies at or beyond the end of the domain the
+// column's values are read in: then no stored value fails it and the compare folds away as it does with the literal.
+struct Domain { int64_t lo = INT64_MIN, hi = INT64_MAX; };
+// what v[c] can hold: a packed image's 0 .. 2^bits - 1, a table column's or byte image's signed range at its width; anything for a
+// derived column and for a column decoded with the tile
+Domain column_domain(const MsArgs &C, int c) {
+    Domain d;
+    if (c < 0 || c >= C.ncol || (((C.derived | C.decode) >> c) & 1u)) return d;
+    if ((C.packed >> c) & 1u) { d.lo = 0; d.hi = C.bits(c) >= 63 ? INT64_MAX : ((int64_t)1 << C.bits(c)) - 1; return d; }
+    const int w = C.width(c);
+    if (w < 8) { d.lo = -((int64_t)1 << (8 * w - 1)); d.hi = ((int64_t)1 << (8 * w - 1)) - 1; }
+    return d;
+}
+struct RangeShape {
+    bool lo_open = false, hi_open = false, point = false;
+    // as the descriptor's constants (range_bounds): INT64_MIN / INT64_MAX: open; (0, 0): a point; (0, 1): both bounds are read
+    int64_t clo() const { return lo_open ? INT64_MIN : 0; }
+    int64_t chi() const { return hi_open ? INT64_MAX : point ? 0 : 1; }
+};
+RangeShape range_shape(const Domain &dom, int64_t lo, int64_t hi) {
+    RangeShape s;
+    s.lo_open = lo <= dom.lo;
+    s.hi_open = hi >= dom.hi;
+    s.point = !s.lo_open && !s.hi_open && lo == hi;
+    return s;
+}
+// "alive[r] & <tests of v[c][r] against the launch's bounds>" for one filter column of a generated stage line; `u32`: the
+// packed form's 32-bit unsigned compares
+std::string rt_filter_line(const MsArgs &C, const MScanDesc &D, int c, bool u32) {
+    const RangeShape s = range_shape(column_domain(C, c), D.flo[c], D.fhi[c]);
+    if (s.lo_open && s.hi_open) return "";
+    const std::string v = std::string(u32 ? "(uint32_t)" : "") + "v[" + std::to_string(c) + "][r]";
+    const std::string lo = std::string(u32 ? "(uint32_t)" : "") + "Dr.flo[" + std::to_string(c) + "]", hi = std::string(u32 ? "(uint32_t)" : "") + "Dr.fhi[" + std::to_string(c) + "]";
+    std::string t = " _Pragma(\"unroll\") for (int r = 0; r < RW; r++) alive[r] = alive[r]";
+    if (s.point) t += " & (" + v + " == " + lo + ")";
+    else {
+        if (!s.lo_open) t += " & (" + v + " >= " + lo + ")";
+        if (!s.hi_open) t += " & (" + v + " <= " + hi + ")";
+    }
+    return t + ";";
+}
+
+std::atomic<int64_t> g_compiled{0}, g_from_disk{0}, g_from_memory{0};
+
 }  // namespace
 
+void counters(int64_t *compiled, int64_t *from_disk, int64_t *from_memory) {
+    if (compiled) *compiled = g_compiled.load();
+    if (from_disk) *from_disk = g_from_disk.load();
+    if (from_memory) *from_memory = g_from_memory.load();
+}
+
 // the descriptor as constexpr functions: only what differs from the defaults is written
-static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, const char *suffix = "") {
+// (rt: run-time bounds -- the ranges' shapes in place of their values)
+static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, const char *suffix = "", bool rt = false) {
+    auto lo_of = [&](int col, int64_t lo, int64_t hi) { return rt ? range_shape(column_domain(C, col), lo, hi).clo() : lo; };
+    auto hi_of = [&](int col, int64_t lo, int64_t hi) { return rt ? range_shape(column_domain(C, col), lo, hi).chi() : hi; };
     std::ostringstream o;
     o << "namespace vdl {\n";
     o << "constexpr MsArgs jit_args" << suffix << "() {\n    MsArgs a{};\n";
@@ -201,7 +258,7 @@ static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, con
     o << "    d.nagg = " << D.nagg << "; d.nkey = " << D.nkey << "; d.replicas = " << D.replicas << "; d.pmin = " << lit(D.pmin) << "; d.pcount = " << lit(D.pcount) << ";\n";
     int pool = 0;
     for (int k = 0; k < C.ncol; k++) {
-        if ((C.filtered >> k) & 1u) o << "    d.flo[" << k << "] = " << lit(D.flo[k]) << "; d.fhi[" << k << "] = " << lit(D.fhi[k]) << ";\n";
+        if ((C.filtered >> k) & 1u) o << "    d.flo[" << k << "] = " << lit(lo_of(k, D.flo[k], D.fhi[k])) << "; d.fhi[" << k << "] = " << lit(hi_of(k, D.flo[k], D.fhi[k])) << ";\n";
         if ((C.decode >> k) & 1u) o << "    d.ibase[" << k << "] = " << lit(D.ibase[k]) << "; d.iscale[" << k << "] = " << lit(D.iscale[k]) << ";\n";
         if ((C.derived >> k) & 1u) {
             o << "    d.dkind[" << k << "] = " << D.dkind[k] << "; d.dsrc[" << k << "] = " << D.dsrc[k] << "; d.dsrc2[" << k << "] = " << D.dsrc2[k]
@@ -210,8 +267,9 @@ static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, con
         }
     }
     for (int f = 0; f < pool; f++)
-        o << "    d.form[" << f << "].op = " << D.form[f].op << "; d.form[" << f << "].col = " << D.form[f].col << "; d.form[" << f << "].lo = " << lit(D.form[f].lo)
-          << "; d.form[" << f << "].hi = " << lit(D.form[f].hi) << ";\n";
+        o << "    d.form[" << f << "].op = " << D.form[f].op << "; d.form[" << f << "].col = " << D.form[f].col << "; d.form[" << f << "].lo = "
+          << lit(D.form[f].op == FormStep::LEAF ? lo_of(D.form[f].col, D.form[f].lo, D.form[f].hi) : D.form[f].lo) << "; d.form[" << f << "].hi = "
+          << lit(D.form[f].op == FormStep::LEAF ? hi_of(D.form[f].col, D.form[f].lo, D.form[f].hi) : D.form[f].hi) << ";\n";
     o << "    d.ncomp = " << D.ncomp << "; d.key_masked = " << D.key_masked << "; d.key_mask = " << lit(D.key_mask) << ";\n";
     for (int k = 0; k < D.ncomp; k++)
         o << "    d.comp[" << k << "].col = " << D.comp[k].col << "; d.comp[" << k << "].rsh = " << D.comp[k].rsh << "; d.comp[" << k << "].lsh = " << D.comp[k].lsh
@@ -240,6 +298,8 @@ static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, con
 std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Shape &sh) {
     std::ostringstream o;
     o << "#define VDL_SPEC_UNROLL _Pragma(\"unroll\")\n";
+    const bool rt = sh.rt_bounds;
+    if (rt) o << "#define VDL_RT_BOUNDS 1\n";
     if (kind == MSCAN && sh.census) o << "#define VDL_CENSUS 1\n";
     if (kind == MSCAN && C.packed) o << "#define VDL_PACKED 1\n";
     if (kind == MSCAN && C.lazy && C.packed) {
@@ -251,7 +311,8 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
         o << "#define VDL_STAGED_PRE";
         for (int c = 0; c < C.ncol; c++) {
             if (!((C.filtered >> c) & 1u) || ((C.lazy >> c) & 1u)) continue;
-            if ((C.packed >> c) & 1u)
+            if (rt) o << rt_filter_line(C, D, c, (C.packed >> c) & 1u);
+            else if ((C.packed >> c) & 1u)
                 o << " _Pragma(\"unroll\") for (int r = 0; r < RW; r++) alive[r] = alive[r] & ((uint32_t)v[" << c << "][r] >= " << ulit(D.flo[c]) << ") & ((uint32_t)v[" << c
                   << "][r] <= " << ulit(D.fhi[c]) << ");";
             else          // (a filter column without a packed image: its byte image, read with the stripe)
@@ -276,7 +337,8 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
         // the queue form: only the filters of the columns that come with the tile, as straight-line code over the tile's rows
         o << "#define VDL_QUEUE_FILTER";
         for (int c = 0; c < C.ncol; c++)
-            if (!((C.derived >> c) & 1u) && !((C.lazy >> c) & 1u) && ((C.filtered >> c) & 1u))
+            if (!((C.derived >> c) & 1u) && !((C.lazy >> c) & 1u) && ((C.filtered >> c) & 1u) && rt) o << rt_filter_line(C, D, c, false);
+            else if (!((C.derived >> c) & 1u) && !((C.lazy >> c) & 1u) && ((C.filtered >> c) & 1u))
                 o << " _Pragma(\"unroll\") for (int r = 0; r < RW; r++) alive[r] = alive[r] & (v[" << c << "][r] >= " << lit(D.flo[c]) << ") & (v[" << c << "][r] <= " << lit(D.fhi[c]) << ");";
         o << "\n";
     } else if (kind == MSCAN && C.lazy) {
@@ -328,7 +390,8 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
             for (int c = 0; c < C.ncol; c++) {
                 if (((C.derived >> c) & 1u) || C.stage(c) != st) continue;
                 if (st > 0) o << load(c, "alive");
-                if ((C.filtered >> c) & 1u)
+                if (((C.filtered >> c) & 1u) && rt) o << rt_filter_line(C, D, c, false);
+                else if ((C.filtered >> c) & 1u)
                     o << " _Pragma(\"unroll\") for (int r = 0; r < RW; r++) alive[r] = alive[r] & (v[" << c << "][r] >= " << lit(D.flo[c]) << ") & (v[" << c << "][r] <= "
                       << lit(D.fhi[c]) << ");";
             }
@@ -337,7 +400,7 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
         for (int c = 0; c < C.ncol; c++) if (!((C.derived >> c) & 1u) && C.stage(c) == 15) o << load(c, "pass");
         o << "\n";
     }
-    o << "#define VDL_PROJ_U " << VDL_PROJ_U_HOST << "\n" << kEmbedded << "\n" << desc_text(kind, C, D);      // (the tile of the projection scan as this library was built)
+    o << "#define VDL_PROJ_U " << VDL_PROJ_U_HOST << "\n" << kEmbedded << "\n" << desc_text(kind, C, D, "", rt);      // (the tile of the projection scan as this library was built)
     const char *b = sh.vec ? "true" : "false";
     if (kind == MSCAN)
         o << "extern \"C\" __global__ __launch_bounds__(256) void " << entry_name(kind, C, D, sh) << "(const vdl::MsArgs Cr, const vdl::MScanDesc *__restrict__ Dp) {\n"
@@ -363,7 +426,8 @@ std::string mscan_source(const MsArgs &C, const MScanDesc &D, const Shape &sh) {
 std::string front_source(const MsArgs &Cs, const MScanDesc &Ds, const MsArgs &Ct, const MScanDesc &Dt, const Shape &sh, int nct) {
     std::ostringstream o;
     o << "#define VDL_SPEC_UNROLL _Pragma(\"unroll\")\n";
-    o << "#define VDL_PROJ_U " << VDL_PROJ_U_HOST << "\n#define VDL_FRONT_BATCH " << VDL_FRONT_BATCH_HOST << "\n" << kEmbedded << "\n" << desc_text(SELECT, Cs, Ds, "_s") << desc_text(TAKE, Ct, Dt, "_t");
+    if (sh.rt_bounds) o << "#define VDL_RT_BOUNDS 1\n";
+    o << "#define VDL_PROJ_U " << VDL_PROJ_U_HOST << "\n#define VDL_FRONT_BATCH " << VDL_FRONT_BATCH_HOST << "\n" << kEmbedded << "\n" << desc_text(SELECT, Cs, Ds, "_s", sh.rt_bounds) << desc_text(TAKE, Ct, Dt, "_t", sh.rt_bounds);
     const char *b = sh.vec ? "true" : "false";
     // (Q3's front: 107 VGPRs = 4 blocks per CU; asked to fit 5 or 6 waves per SIMD -- 96 / 80 registers, 12 / 76 bytes of scratch -- the pass
     // took the same 2.64-2.66 ms at SF100: it moves 14.7 GB, i.e. 5.5 TB/s, and is bound by that, not by occupancy)
@@ -381,15 +445,16 @@ const char *entry_name(Kind kind) { return kind == MSCAN ? "vdl_jit_mscan" : kin
 std::string entry_name(Kind kind, const MsArgs &C, const MScanDesc &D, const Shape &sh) {
     if (kind != MSCAN) return entry_name(kind);
     char tag[16];
-    snprintf(tag, sizeof tag, "%06llx", (unsigned long long)(fnv(desc_text(kind, C, D)) & 0xffffffull));      // which plan's scan
+    snprintf(tag, sizeof tag, "%06llx", (unsigned long long)(fnv(desc_text(kind, C, D, "", sh.rt_bounds)) & 0xffffffull));      // which plan's scan (run-time bounds: which shape of plan)
     // (staged: how many filter columns come with the tile is part of the name too -- the profiles tell the forms apart by it)
     int eager_filters = 0;
     for (int c = 0; c < C.ncol; c++) eager_filters += ((C.filtered >> c) & 1u) && !((C.derived >> c) & 1u) && C.stage(c) == 0;
     return std::string("vdl_jit_mscan_") + (sh.grouped ? "grouped_" : "") + (C.packed ? "packed_" : "") + "u" + std::to_string(sh.u) + (C.lazy ? "_staged" + std::to_string(eager_filters) + "_" : "_") +
-           (sh.census ? "census_" : "") + tag;
+           (sh.census ? "census_" : "") + tag + (sh.rt_bounds ? "_rtb" : "");
 }
 
-bool compile(const std::string &src, const std::string &arch, std::vector<char> &code, std::string &log) {
+bool compile(const std::string &src, const std::string &arch, std::vector<char> &code, std::string &log, Origin *origin) {
+    if (origin) *origin = COMPILED;
     std::string key = std::to_string(fnv(src)) + "_" + std::to_string(src.size()) + "_" + arch;
     {
         Rtc &r0 = rtc();
@@ -399,7 +464,7 @@ bool compile(const std::string &src, const std::string &arch, std::vector<char> 
     {
         std::lock_guard<std::mutex> g(g_mu);
         auto it = g_code.find(key);
-        if (it != g_code.end()) { code = it->second; return true; }
+        if (it != g_code.end()) { code = it->second; g_from_memory++; if (origin) *origin = FROM_MEMORY; return true; }
     }
     if (const char *dump = getenv("VDL_JIT_DUMP")) {           // debugging: the generated translation unit as a file
         std::ofstream f(std::string(dump) + "/vdl_" + key + ".hip");
@@ -409,7 +474,7 @@ bool compile(const std::string &src, const std::string &arch, std::vector<char> 
     std::string path;
     if (!dir.empty()) {
         path = dir + "/vdl_" + key + ".vdlco";
-        if (cache_read(path, src, code)) { std::lock_guard<std::mutex> g(g_mu); g_code[key] = code; return true; }
+        if (cache_read(path, src, code)) { std::lock_guard<std::mutex> g(g_mu); g_code[key] = code; g_from_disk++; if (origin) *origin = FROM_DISK; return true; }
     }
     Rtc &r = rtc();
     if (!r.lib || !r.why.empty()) { log = r.why.empty() ? "libhiprtc not usable" : r.why; return false; }
@@ -428,6 +493,7 @@ bool compile(const std::string &src, const std::string &arch, std::vector<char> 
     r.destroy(&prog);
     if (code.empty()) { log = "hiprtc produced no code"; return false; }
     if (!path.empty()) cache_write(path, src, code);
+    g_compiled++;
     std::lock_guard<std::mutex> g(g_mu);
     g_code[key] = code;
     return true;

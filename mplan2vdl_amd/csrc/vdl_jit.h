@@ -12,7 +12,10 @@ namespace vdl {
 namespace jit {
 
 struct Shape { int nc = 0, u = 0; bool vec = false, grouped = false, der = false;
-               bool census = false; };     // census: a staged scan's late loads also count the 128-byte lines they ask for (measurement builds)
+               bool census = false;        // census: a staged scan's late loads also count the 128-byte lines they ask for (measurement builds)
+               // run-time bounds (vdl_plan_set_jit_bounds): the text holds the shapes of the range filters and formula tests, the kernel
+               // reads their values from the launch's descriptor -- plans that differ in literals alone share source, key and code
+               bool rt_bounds = false; };
 
 // what is specialised: an aggregate scan, or the two passes of the projection scan (fused front; dimension scans are the
 // select pass with bitmap_only set)
@@ -25,7 +28,11 @@ std::string mscan_source(const MsArgs &C, const MScanDesc &D, const Shape &sh);
 // the one-pass front: select-side args / descriptor (sh.nc columns), take-side ones (nct columns)
 std::string front_source(const MsArgs &Cs, const MScanDesc &Ds, const MsArgs &Ct, const MScanDesc &Dt, const Shape &sh, int nct);
 // hiprtc (no GPU needed); cached per process and under $VDL_JIT_CACHE.  false: `log` says why
-bool compile(const std::string &src, const std::string &arch, std::vector<char> &code, std::string &log);
+// origin: where the code came from
+enum Origin : int { COMPILED = 0, FROM_DISK = 1, FROM_MEMORY = 2 };
+bool compile(const std::string &src, const std::string &arch, std::vector<char> &code, std::string &log, Origin *origin = nullptr);
+// builds of this process so far: by hiprtc, read from $VDL_JIT_CACHE, found in memory (vdl_jit_counters)
+void counters(int64_t *compiled, int64_t *from_disk, int64_t *from_memory);
 
 struct Kernel {
     hipModule_t mod = nullptr;

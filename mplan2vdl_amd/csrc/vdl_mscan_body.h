@@ -212,14 +212,38 @@ __device__ __forceinline__ void decode_tile(const MsArgs &C, const MScanDesc &D,
     }
 }
 
+// The bounds of one range filter or formula test.  (clo, chi) are the descriptor's the code was built for, (rlo, rhi) the same
+// pair of the launch's descriptor in device memory.  The precompiled kernels pass one object for both, a specialised build holds
+// the plan's values as constants.  A specialised build with run-time bounds (VDL_RT_BOUNDS, vdl_jit.cpp) keeps only the SHAPE of
+// the range as constants -- INT64_MIN: no lower bound, INT64_MAX: no upper bound, (0, 0): a point, one equality compare; any other
+// pair: a bound to read -- and takes the values from the launch's descriptor by scalar loads, so that plans which differ in
+// their literals alone share one kernel.  An open side still folds away, and a load nobody uses is never issued.
+// (the scan's row pipeline is a lambda with two or three call sites, inlined by the compiler's own judgement; the bound loads make
+// it dearer, and a scan as large as Q12's at 2 row pairs per lane was no longer inlined -- its descriptor then does not fold, 160 KB
+// of code --, so builds with run-time bounds insist)
+#ifdef VDL_RT_BOUNDS
+#define VDL_PROCESS_INLINE __attribute__((always_inline))
+#else
+#define VDL_PROCESS_INLINE
+#endif
+__device__ __forceinline__ void range_bounds(int64_t clo, int64_t chi, int64_t rlo, int64_t rhi, int64_t &lo, int64_t &hi) {
+#ifdef VDL_RT_BOUNDS
+    lo = clo == INT64_MIN ? clo : rlo;
+    hi = chi == INT64_MAX ? chi : (clo == 0 && chi == 0) ? lo : rhi;
+#else
+    lo = clo; hi = chi;
+#endif
+}
+
 template <int NC, int RW>
-__device__ __forceinline__ void eval_pass(const MsArgs &C, const MScanDesc &D, const int64_t (&v)[NC][RW], bool (&pass)[RW]) {
+__device__ __forceinline__ void eval_pass(const MsArgs &C, const MScanDesc &D, const MScanDesc &Dr, const int64_t (&v)[NC][RW], bool (&pass)[RW]) {
 #pragma unroll
     for (int r = 0; r < RW; r++) pass[r] = true;
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         if ((C.filtered >> c) & 1u) {                      // wave-uniform (bits only below ncol)
-            const int64_t lo = D.flo[c], hi = D.fhi[c];
+            int64_t lo, hi;
+            range_bounds(D.flo[c], D.fhi[c], Dr.flo[c], Dr.fhi[c], lo, hi);
 #pragma unroll
             for (int r = 0; r < RW; r++) pass[r] = pass[r] & (v[c][r] >= lo) & (v[c][r] <= hi);
         }
@@ -236,7 +260,8 @@ __device__ __forceinline__ void derive(const MsArgs &C, const MsArgs &Cr, const 
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (((C.filtered >> c) & 1u) && !((C.derived >> c) & 1u)) {
-                const int64_t lo = D.flo[c], hi = D.fhi[c];
+                int64_t lo, hi;
+                range_bounds(D.flo[c], D.fhi[c], Dr.flo[c], Dr.fhi[c], lo, hi);
 #pragma unroll
                 for (int r = 0; r < RW; r++) alive[r] = alive[r] & (v[c][r] >= lo) & (v[c][r] <= hi);
             }
@@ -274,7 +299,8 @@ __device__ __forceinline__ void derive(const MsArgs &C, const MsArgs &Cr, const 
                 VDL_SPEC_UNROLL
                 for (int j = 0; j < L; j++) {              // (runtime loops outside, the unrolled ones inside: the column array stays in registers)
                     const int col = D.form[a + j].col;
-                    const int64_t lo = D.form[a + j].lo, hi = D.form[a + j].hi;
+                    int64_t lo, hi;
+                    range_bounds(D.form[a + j].lo, D.form[a + j].hi, Dr.form[a + j].lo, Dr.form[a + j].hi, lo, hi);
 #pragma unroll
                     for (int k = 0; k < NC; k++) {
                         if (k < c && k == col) {           // scalar branch: one body runs
@@ -308,7 +334,8 @@ __device__ __forceinline__ void derive(const MsArgs &C, const MsArgs &Cr, const 
 #pragma unroll
                 for (int r = 0; r < RW; r++) v[c][r] = (int64_t)(stk[r] & 1u);
                 if ((C.filtered >> c) & 1u) {
-                    const int64_t lo = D.flo[c], hi = D.fhi[c];
+                    int64_t lo, hi;
+                    range_bounds(D.flo[c], D.fhi[c], Dr.flo[c], Dr.fhi[c], lo, hi);
 #pragma unroll
                     for (int r = 0; r < RW; r++) alive[r] = alive[r] & (v[c][r] >= lo) & (v[c][r] <= hi);
                 }
@@ -332,7 +359,8 @@ __device__ __forceinline__ void derive(const MsArgs &C, const MsArgs &Cr, const 
 #pragma unroll
                 for (int r = 0; r < RW; r++) v[c][r] = (int64_t)((uint64_t)x[r] - (uint64_t)y[r]);
                 if ((C.filtered >> c) & 1u) {               // (the projection scan has no second look at the filters: fold it here)
-                    const int64_t lo = D.flo[c], hi = D.fhi[c];
+                    int64_t lo, hi;
+                    range_bounds(D.flo[c], D.fhi[c], Dr.flo[c], Dr.fhi[c], lo, hi);
 #pragma unroll
                     for (int r = 0; r < RW; r++) alive[r] = alive[r] & (v[c][r] >= lo) & (v[c][r] <= hi);
                 }
@@ -372,7 +400,8 @@ __device__ __forceinline__ void derive(const MsArgs &C, const MsArgs &Cr, const 
             // a filter on the looked-up value (the dimension selection's bit, a dimension column's range) takes effect at
             // once: the lookups of the columns after it are then issued for the rows that are still in
             if ((C.filtered >> c) & 1u) {
-                const int64_t lo = D.flo[c], hi = D.fhi[c];
+                int64_t lo, hi;
+                range_bounds(D.flo[c], D.fhi[c], Dr.flo[c], Dr.fhi[c], lo, hi);
 #pragma unroll
                 for (int r = 0; r < RW; r++) alive[r] = alive[r] & (v[c][r] >= lo) & (v[c][r] <= hi);
             }
@@ -480,7 +509,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
     // tile0, tile_rows: the first row (an index into the columns) and the rows of the tile the lane's rows lie in -- wave-uniform, the
     // generated late loads build their buffer resources from them
     auto process = [&](auto rows_tag, int64_t (&v)[NC][decltype(rows_tag)::value], const int64_t (&rowid)[decltype(rows_tag)::value], int64_t rows_left, auto staged_tag,
-                       int64_t tile0, int64_t tile_rows) {
+                       int64_t tile0, int64_t tile_rows) VDL_PROCESS_INLINE {
         constexpr int RW = decltype(rows_tag)::value;
         bool pass[RW];
         // Staged reads (STAGED: specialised builds, when the tuner found them quicker): only the most selective filter column comes
@@ -512,7 +541,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
             VDL_STAGED_POST
 #endif
         } else {
-            eval_pass<NC, RW>(C, D, v, pass);
+            eval_pass<NC, RW>(C, D, Dr, v, pass);
             if (DER || PACKED) {
 #pragma unroll
                 for (int r = 0; r < RW; r++) pass[r] = pass[r] & alive[r];

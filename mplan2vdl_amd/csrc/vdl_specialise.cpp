@@ -6,12 +6,25 @@
 namespace vdl {
 namespace eng {
 
+void count_build(vdl_plan *p, const std::string &role, jit::Origin from) {
+    std::pair<int, int> &b = p->jit_builds[role];
+    b.first++;
+    b.second += from != jit::COMPILED;
+}
+std::string builds_text(const vdl_plan *p, const std::string &role) {
+    const auto it = p->jit_builds.find(role);
+    if (it == p->jit_builds.end()) return "";
+    return "from cache: " + std::to_string(it->second.second) + " of " + std::to_string(it->second.first) + " builds of " + role + "; ";
+}
+
 // Run-time specialisation of one multi-aggregate scan (vdl_jit.cpp): the shape of the precompiled variant the launch
 // configuration chose, with exactly this scan's column count, and the descriptor as constants.  On success the kernel, its
 // grid (occupancy of the specialised code) and name replace the variant's; on failure the variant stays and the note says why.
 // (f.u, where the form names one, replaces the variant's row pairs per lane)
-static jit::Shape jit_shape(const MScanCols &cols, const ScanLaunch &cfg, const ScanForm &f) {
+// (rt: the plan's bounds at run time, vdl_plan_set_jit_bounds)
+static jit::Shape jit_shape(const MScanCols &cols, const ScanLaunch &cfg, const ScanForm &f, bool rt) {
     jit::Shape sh;
+    sh.rt_bounds = rt;
     mscan_variant_shape(cfg, &sh.nc, &sh.u, &sh.vec, &sh.grouped, &sh.der);
     sh.nc = cols.ncol;
     for (int k = 0; k < cols.ncol; k++) sh.der |= cols.kind[k] != VC_DIRECT;
@@ -21,7 +34,8 @@ static jit::Shape jit_shape(const MScanCols &cols, const ScanLaunch &cfg, const 
     else if (f.kind == ScanForm::PACKED) sh.u = getenv("VDL_JIT_U") ? atoi(getenv("VDL_JIT_U")) : 2;      // (the packed form: up to 16 row pairs per slice)
     return sh;
 }
-// (",img": some columns are read from their images -- a kernel that moves other bytes than the same form over the catalog columns)
+// (",img": some columns are read from their images -- a kernel that moves other bytes than the same form over the catalog columns;
+// ",rtb", after the form's suffix: bounds at run time)
 static std::string jit_name(const jit::Shape &sh, bool image) {
     return "k_mscan_specialised<" + std::to_string(sh.nc) + "," + std::to_string(sh.u) + "," + (sh.vec ? "vec" : "novec") + "," + (sh.grouped ? "grouped" : "global") +
            (sh.der ? ",derived" : "") + (image ? ",img" : "") + ">";
@@ -195,13 +209,15 @@ struct Specialised {
 static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, const ScanForm &f, const MScanCols &cols, const MScanDesc &d, Specialised &out, std::string &why,
                               bool census = false) {
     out = Specialised{};
-    jit::Shape sh = jit_shape(cols, p->mcfg[s], f);
+    jit::Shape sh = jit_shape(cols, p->mcfg[s], f, p->jit_rt_bounds);
     sh.census = census;
     std::vector<char> code;
     if (!bind_form(c, p, s, grouped, f, sh.u, cols, d, out.b, why)) return false;
     const MsArgs &args = out.b.args;
     const MScanDesc &desc = *out.b.desc;
-    if (!jit::compile(jit::mscan_source(args, desc, sh), c->arch, code, why)) { why = why.substr(0, 400); return false; }
+    jit::Origin from = jit::COMPILED;
+    if (!jit::compile(jit::mscan_source(args, desc, sh), c->arch, code, why, &from)) { why = why.substr(0, 400); return false; }
+    count_build(p, "scan " + std::to_string(s), from);
     // a specialised scan is 10-25 KB of code; ten times that means the compiler did not fold the descriptor (it then sits in
     // scratch memory and every descriptor-driven loop stays): such a build is slower than the precompiled kernel
     if (code.size() > (size_t)96 << 10) { why = "the descriptor did not fold (" + std::to_string(code.size()) + " B of code)"; return false; }
@@ -221,7 +237,7 @@ static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, c
     if (grid < 1) grid = 1;
     out.grid = (int)grid; out.per_cu = per_cu; out.code_bytes = code.size(); out.form = f; out.form.u = sh.u;
     out.name = jit_name(sh, out.b.cols->image != 0);
-    out.name.insert(out.name.size() - 1, f.suffix());
+    out.name.insert(out.name.size() - 1, std::string(f.suffix()) + (sh.rt_bounds ? ",rtb" : ""));
     out.stages = stages_text(p, s, args);
     out.packed = packed_text(p, s, *out.b.cols);
     return true;
@@ -251,7 +267,8 @@ bool specialise_scan(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, std::strin
     if (!sp.k && !build_specialised(c, p, s, grouped, ScanForm{}, p->mcols[s], p->mdesc[s], sp, why)) { p->jit_note += "scan " + std::to_string(s) + ": not specialised (" + why + "); "; return false; }
     install_form(p, s, sp);
     *kname = sp.name;
-    p->jit_note += "scan " + std::to_string(s) + ": " + sp.name + ", " + std::to_string(sp.code_bytes) + " B of code, " + std::to_string(sp.per_cu) + " blocks/CU" + form_text(sp) + "; ";
+    p->jit_note += "scan " + std::to_string(s) + ": " + sp.name + ", " + std::to_string(sp.code_bytes) + " B of code, " + std::to_string(sp.per_cu) + " blocks/CU" + form_text(sp) + "; " +
+                   builds_text(p, "scan " + std::to_string(s));
     return true;
 }
 
@@ -360,14 +377,14 @@ void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
             if (ms < best_ms * 0.98f) {
                 p->kscan[s] = 1;
                 p->mjit[s] = nullptr;
-                p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + scan_kernel_name(p->scfg[s]) + "; ";
+                p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + scan_kernel_name(p->scfg[s]) + "; " + builds_text(p, "scan " + std::to_string(s));
                 if ((int)s == p->dominant) p->dominant_kernel = std::string(scan_kernel_name(p->scfg[s])) + "_grid" + std::to_string(p->scfg[s].grid);
                 continue;
             }
         }
         install_form(p, s, best);
         p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + best.name + (best.packed.empty() ? "" : " (packed: " + best.packed + ")") +
-                       (best.stages.empty() ? "" : " (read late: " + best.stages + ")") + "; ";
+                       (best.stages.empty() ? "" : " (read late: " + best.stages + ")") + "; " + builds_text(p, "scan " + std::to_string(s));
         if ((int)s == p->dominant)
             p->dominant_kernel = best.name + "_grid" + std::to_string(best.grid) + (grouped ? "_rep" + std::to_string(p->mdesc[s].replicas) : "");
     }
@@ -452,7 +469,7 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
         if (cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no scan kernel variant for this shape");
         // the staged, queue or packed form of the same scan (VDL_JIT_LATE as in specialise_scan), refused where the tuner refuses it
         const ScanForm late = form_asked_for();
-        jit::Shape sh = jit_shape(cols, cfg, late);
+        jit::Shape sh = jit_shape(cols, cfg, late, p->jit_rt_bounds);
         if (getenv("VDL_JIT_CENSUS")) sh.census = true;              // (tests: the measurement build of a staged scan compiles too)
         std::vector<char> code;
         std::string log;
@@ -465,6 +482,7 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
             throw Error(VDL_ERR_UNSUPPORTED, "scan " + std::to_string(s) + " does not build: " + log.substr(0, 2000));
         std::string name = jit_name(sh, b.cols->image != 0);
         if (b.args.packed) name.insert(name.size() - 1, late.suffix());
+        if (sh.rt_bounds) name.insert(name.size() - 1, ",rtb");
         p->jit_note += "scan " + std::to_string(s) + ": " + name + (b.args.packed ? " (packed: " + packed_text(p, s, *b.cols) + ")" : "") +
                        (b.args.queued ? " (queue)" : b.args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";
     }

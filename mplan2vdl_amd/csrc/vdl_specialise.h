@@ -15,6 +15,10 @@ void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words);
 int64_t scan_bytes_moved(vdl_ctx *c, vdl_plan *p, std::string &detail);
 // vdl_plan_jit_check of a fused plan: every scan's specialised kernel built (not loaded) against the columns registered now
 void jit_check_scans(vdl_ctx *c, vdl_plan *p);
+// one build of specialised code for `role` of the plan ("scan 0", "front", "dim3") and where its code came from; what the note says
+// about the role's builds so far: "from cache: 2 of 3 builds of scan 0; "
+void count_build(vdl_plan *p, const std::string &role, jit::Origin from);
+std::string builds_text(const vdl_plan *p, const std::string &role);
 
 }  // namespace eng
 }  // namespace vdl

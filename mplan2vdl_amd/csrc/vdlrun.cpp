@@ -172,7 +172,7 @@ bool read_reply(const std::string &path, Reply &r) {
 struct Options {
     int64_t rows = 60175;           // SF0.01 lineitem, /root/reference/tests/tpchnoorder/bounds.csv:59
     uint64_t seed = 0x5EED0006ULL;
-    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, encode = 0;
+    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0;
     std::string data_dir, shard = "lineitem";
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
@@ -212,6 +212,7 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
     vdl_plan_set_fusion(plan, o.fuse);
     vdl_plan_set_profiling(plan, o.profile);
     if (o.jit) vdl_plan_set_jit(plan, o.jit);
+    if (o.jit_share) vdl_plan_set_jit_bounds(plan, 1);
     if (!o.order_fields.empty() || o.limit > 0) {
         std::vector<const char *> fields;
         for (const std::string &f : o.order_fields) fields.push_back(f.c_str());
@@ -287,10 +288,11 @@ int main(int argc, char **argv) {
         else if (a == "--jit") o.jit = 1;
         else if (a == "--encode") o.encode = 1;
         else if (a == "--jit-tune") o.jit = 2;
+        else if (a == "--jit-share") o.jit_share = 1;      // filter bounds at run time: queries that differ in literals alone share the specialised code
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc],... ] [--limit N] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--encode] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc],... ] [--limit N] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }

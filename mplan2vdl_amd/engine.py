@@ -20,6 +20,15 @@ class VdlError(RuntimeError):
         self.code = code
 
 
+def jit_counters():
+    """Builds of specialised scan code in this process so far (vdl.h: vdl_jit_counters): {"compiled": by hiprtc, "from_disk": read
+    from $VDL_JIT_CACHE, "from_memory": built earlier in this process}."""
+    L = _lib.load()
+    a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    L.vdl_jit_counters(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+    return {"compiled": a.value, "from_disk": b.value, "from_memory": c.value}
+
+
 class DeviceValues:
     """An output left in device memory (Plan.set_device_outputs): int64 values at `ptr`, valid until the plan runs again."""
 
@@ -64,10 +73,14 @@ class Plan:
     def set_profiling(self, enabled):
         self._e._check(self._e._L.vdl_plan_set_profiling(self._h, int(bool(enabled))))
 
-    def set_jit(self, enabled, tune=False):
+    def set_jit(self, enabled, tune=False, runtime_bounds=None):
         """Scan kernels specialised for this plan by hiprtc at the next run; tune: rows per lane chosen by timing at that
-        run (vdl.h: vdl_plan_set_jit)."""
+        run (vdl.h: vdl_plan_set_jit).  runtime_bounds: the specialised code reads the values of the filter bounds from the plan's
+        descriptor, so that plans which differ in their literals alone share it (vdl.h: vdl_plan_set_jit_bounds); None leaves
+        the plan's setting (off, unless VDL_JIT_BOUNDS=runtime was set when it was parsed) as it is."""
         self._e._check(self._e._L.vdl_plan_set_jit(self._h, (2 if tune else 1) if enabled else 0))
+        if runtime_bounds is not None:
+            self._e._check(self._e._L.vdl_plan_set_jit_bounds(self._h, int(bool(runtime_bounds))))
 
     def jit_note(self):
         return self._e._L.vdl_plan_jit_note(self._h).decode()
