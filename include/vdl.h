@@ -177,6 +177,34 @@ int  vdl_plan_image_columns(const vdl_plan *plan, const char **list);
  * outputs to the host and synchronises. */
 int  vdl_run(vdl_ctx *ctx, vdl_plan *plan);
 
+/* ---- batched runs: plans that differ in their literals alone share one pass over the columns -----------------------------
+ * The same query for eight years, a dashboard's slices of one table: each vdl_run re-reads the same columns.  vdl_run_batch runs
+ * n plans in one call and ALWAYS produces every answer: after VDL_OK every plan holds what vdl_run of it alone would have left
+ * -- the same outputs bit for bit through vdl_output, an order set on the plan applied as vdl_run applies it.  Plans that can share
+ * a scan are grouped and each group is cut into batches of at most 8 plans -- fewer for scans of many aggregates: a lane keeps
+ * slots x (1 + aggregates) <= 32 accumulators in registers --; one kernel reads every tile once and tests it against each plan's
+ * bounds, with a count and accumulators per plan.  Every other plan runs alone through the vdl_run path inside the same call.
+ * Two plans share a scan when both are fused with specialisation on (vdl_plan_set_jit >= 1), each is exactly one global aggregate scan
+ * over table columns (no grouped scan, no derived columns, no lookup tables or semi-join sets) that is not known to be empty, they
+ * bind the same columns (same images, row count, row offset), and their generated code under run-time bounds is the same (the shapes
+ * of vdl_plan_set_jit_bounds; the batch always generates with the bounds at run time, whatever the plans' own setting).  The batch
+ * kernel is a code object of its own per width (",batch<K>,rtb>" in its name), cached like any other and kept loaded with the context:
+ * a second batch of the same width and shape with new literals compiles nothing.  Untuned plans get the eager form; when every plan
+ * of a batch tunes (vdl_plan_set_jit 2) the eager form at 2, 3, 4 row pairs per lane and the every-column packed form at 2, 4 are
+ * timed once per shape and width (VDL_JIT_PIN / VDL_JIT_U pin as they do for one plan); the forms that read late are not batched.
+ * n < 1, a null entry or the same plan twice: VDL_ERR_ARG.  A plan's failure is reported as vdl_run would report it, the message
+ * naming the plan's index; the plans after it may not have run.
+ * vdl_plan_batch_note: what the last vdl_run_batch / vdl_batch_jit_check did with the plan -- "batch <b>: slot <q> of <K>, <kernel name>"
+ * or "alone: <reason>" ("specialisation is off", "grouped scans are not batched", "its filter shapes differ from every other
+ * plan's", ...); "" after a plain vdl_run.
+ * vdl_batch_jit_check: like vdl_plan_jit_check, groups the plans and builds the batch kernels against the columns registered now
+ * without a device, and fills the notes.
+ * With vdl_plan_set_profiling every plan of a batch carries ONE timing, "timeInMicrosecondsForBatchedScan_<kernel>": the whole batch
+ * kernel's time, under a label of its own so that it is never read as a per-query figure. */
+int  vdl_run_batch(vdl_ctx *ctx, vdl_plan *const *plans, int n);
+const char *vdl_plan_batch_note(const vdl_plan *plan);
+int  vdl_batch_jit_check(vdl_ctx *ctx, vdl_plan *const *plans, int n);
+
 int  vdl_n_outputs(const vdl_plan *plan);
 /* k-th output in program order: `name` is the output field (resolve.py:64-78 splits it on
  * "__"), `tmp` the "tmpN" result key (N = id of the MaterializeCompact line). */

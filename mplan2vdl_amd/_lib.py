@@ -72,6 +72,9 @@ def load():
         "vdl_n_traced": (i32, [vp]),
         "vdl_traced": (i32, [vp, i32, P(i32), P(cp), P(i64), P(P(i64)), P(P(ctypes.c_uint8))]),
         "vdl_run": (i32, [vp, vp]),
+        "vdl_run_batch": (i32, [vp, P(vp), i32]),
+        "vdl_batch_jit_check": (i32, [vp, P(vp), i32]),
+        "vdl_plan_batch_note": (cp, [vp]),
         "vdl_n_outputs": (i32, [vp]),
         "vdl_output": (i32, [vp, i32, P(cp), P(cp), P(P(i64)), P(ctypes.c_size_t)]),
         "vdl_plan_set_device_outputs": (i32, [vp, i32]),
@@ -122,7 +125,7 @@ ABI_SYMBOLS = [
     "vdl_encode_column", "vdl_column_image_info", "vdl_column_packed_info", "vdl_download_packed_image", "vdl_declare_packed_image",
     "vdl_set_column_images",
     "vdl_parse", "vdl_plan_free", "vdl_plan_describe", "vdl_plan_is_fused", "vdl_plan_set_fusion",
-    "vdl_plan_set_profiling", "vdl_plan_set_jit", "vdl_plan_set_jit_bounds", "vdl_jit_counters", "vdl_plan_jit_note", "vdl_plan_jit_check", "vdl_plan_image_columns", "vdl_plan_set_trace", "vdl_n_traced", "vdl_traced", "vdl_run", "vdl_n_outputs", "vdl_output", "vdl_plan_set_device_outputs", "vdl_output_device", "vdl_n_timings", "vdl_timing",
+    "vdl_plan_set_profiling", "vdl_plan_set_jit", "vdl_plan_set_jit_bounds", "vdl_jit_counters", "vdl_plan_jit_note", "vdl_plan_jit_check", "vdl_plan_image_columns", "vdl_plan_set_trace", "vdl_n_traced", "vdl_traced", "vdl_run", "vdl_run_batch", "vdl_batch_jit_check", "vdl_plan_batch_note", "vdl_n_outputs", "vdl_output", "vdl_plan_set_device_outputs", "vdl_output_device", "vdl_n_timings", "vdl_timing",
     "vdl_plan_set_order", "vdl_plan_order_note", "vdl_order_host",
     "vdl_plan_scan_stats", "vdl_plan_scan_traffic", "vdl_plan_partial_spec", "vdl_plan_sharded_route", "vdl_run_local", "vdl_finalize", "vdl_finalize_begin", "vdl_finalize_end", "vdl_plan_set_row_offset", "vdl_plan_set_sharded_table", "vdl_resolve_first", "vdl_exchange_spec", "vdl_exchange_begin", "vdl_exchange_pack",
     "vdl_exchange_finish", "vdl_comm_unique_id", "vdl_comm_init", "vdl_comm_init_host", "vdl_comm_info", "vdl_comm_free", "vdl_run_sharded",

@@ -629,7 +629,7 @@ void run_fused_local(vdl_ctx *c, vdl_plan *p, int64_t *dev_words, bool single_ra
 // (merged) partial words into a pinned host slot and records an event; `end` waits for that event
 // only (not for younger work on the stream) and builds the outputs.
 void finalize_begin(vdl_ctx *c, vdl_plan *p, const int64_t *dev_words, int slot) {
-    if (!p->bound) throw Error(VDL_ERR_ARG, "vdl_finalize called before vdl_run_local");
+    if (!p->bound && !p->batch_words) throw Error(VDL_ERR_ARG, "vdl_finalize called before vdl_run_local");
     if (slot < 0 || slot > 1) throw Error(VDL_ERR_ARG, "finalisation slot must be 0 or 1");
     if (p->host_cap < p->n_words) {
         for (int k = 0; k < 2; k++) {
@@ -1466,6 +1466,7 @@ int vdl_run(vdl_ctx *c, vdl_plan *p) {
     return guard(c, [&] {
         need_device(c);
         p->order_note.clear();
+        p->batch_note.clear();
         if (p->use_fusion && p->fused.ok) {
             const int64_t nw = plan_words(p, nullptr, nullptr);
             if (!p->words || p->words_cap < nw) { p->words = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(nw, 1)); p->words_cap = nw; }
@@ -1494,6 +1495,140 @@ int vdl_run(vdl_ctx *c, vdl_plan *p) {
         if (!p->fallback_note.empty()) { p->timings.push_back({"fusedPlanAbandoned: " + p->fallback_note, 0.0}); p->fallback_note.clear(); }
     });
 }
+
+// ---- batched runs: plans that differ in their literals alone share one pass over the columns -----------
+namespace {
+// Groups the plans (vdl_specialise.cpp says which may share a scan and why not), cuts every group into batches of at most
+// batch_cap plans and runs each batch as one scan; every other plan runs alone through vdl_run.  check_only (vdl_batch_jit_check):
+// the grouping, the builds and the notes, nothing loaded or run.
+void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
+    std::vector<BatchMember> members;
+    members.reserve((size_t)n);
+    std::vector<std::string> alone((size_t)n);
+    for (int i = 0; i < n; i++) {
+        vdl_plan *p = plans[i];
+        p->batch_note.clear();
+        alone[(size_t)i] = batch_alone_reason(p);
+        if (!alone[(size_t)i].empty()) continue;
+        BatchMember m;
+        m.index = i;
+        try { batch_bind(c, p, m); } catch (const Error &e) { alone[(size_t)i] = std::string("its scan does not bind (") + e.what() + ")"; continue; }
+        members.push_back(std::move(m));
+    }
+    // groups in the order of their first plan; a plan with no partner says whether it was the columns or the shape
+    std::vector<std::vector<BatchMember *>> groups;
+    for (BatchMember &m : members) {
+        bool placed = false;
+        for (auto &g : groups)
+            if (g[0]->cols_key == m.cols_key && g[0]->shape_key == m.shape_key) { g.push_back(&m); placed = true; break; }
+        if (!placed) groups.push_back({&m});
+    }
+    std::vector<std::vector<BatchMember *>> batches;
+    for (auto &g : groups) {
+        if (g.size() == 1) {
+            bool same_cols = false;
+            for (const BatchMember &o : members) same_cols |= &o != g[0] && o.cols_key == g[0]->cols_key;
+            alone[(size_t)g[0]->index] = same_cols ? "its filter shapes differ from every other plan's" : members.size() > 1 ? "no other plan scans the same columns" : "no other plan of the call can share a scan";
+            continue;
+        }
+        const size_t cap = (size_t)batch_cap(g[0]->desc->nagg);
+        if (cap < 2) { for (BatchMember *m : g) alone[(size_t)m->index] = "a scan of " + std::to_string(m->desc->nagg) + " aggregates leaves no room for a second plan's accumulators"; continue; }
+        for (size_t at = 0; at < g.size(); at += cap) {
+            const size_t k = std::min(cap, g.size() - at);
+            if (k == 1) { alone[(size_t)g[at]->index] = "the one plan left over when its group was cut into batches of " + std::to_string(cap); continue; }
+            batches.emplace_back(g.begin() + (std::ptrdiff_t)at, g.begin() + (std::ptrdiff_t)(at + k));
+        }
+    }
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    };
+    for (size_t b = 0; b < batches.size(); b++) {
+        const std::vector<BatchMember *> &ms = batches[b];
+        const int K = (int)ms.size();
+        bool tune = true, profiling = false;
+        int64_t *outs[kMaxBatch] = {};
+        for (int q = 0; q < K; q++) {
+            vdl_plan *p = ms[(size_t)q]->p;
+            tune = tune && p->jit_tune;
+            profiling = profiling || p->profiling;
+            if (check_only) continue;
+            const int64_t nw = ms[(size_t)q]->desc->nagg + 1;
+            if (!p->words || p->words_cap < nw) { p->words = dev_alloc(c, sizeof(int64_t) * (size_t)nw); p->words_cap = nw; }
+            outs[q] = (int64_t *)p->words->p;
+            p->order_note.clear();
+            if (!p->bound || p->bound_version != c->binding_version()) {
+                // finalize_begin / finalize_end read the plan's word layout: one global scan, its words first.  The plan stays unbound -- its
+                // own kernels are built when it is run alone
+                p->bound = false;
+                p->reduce_ops.clear();
+                p->n_words = plan_words(p, &p->reduce_ops, nullptr);
+                p->word_offset.assign(1, 0);
+                p->gword_offset.clear();
+                p->batch_words = true;
+            }
+        }
+        Events ev;
+        if (profiling && !check_only) { HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); }
+        std::string name;
+        try {
+            name = batch_scan(c, ms, tune, check_only, outs, ev.a, ev.b);
+        } catch (const Error &e) {
+            throw Error(e.code, "plan " + std::to_string(ms[0]->index) + " (batch " + std::to_string(b) + "): " + e.what());
+        }
+        for (int q = 0; q < K; q++)
+            ms[(size_t)q]->p->batch_note = "batch " + std::to_string(b) + ": slot " + std::to_string(q) + " of " + std::to_string(K) + ", " + name;
+        if (check_only) continue;
+        for (int q = 0; q < K; q++) finalize_begin(c, ms[(size_t)q]->p, (const int64_t *)ms[(size_t)q]->p->words->p, 0);
+        float ms_scan = 0;
+        for (int q = 0; q < K; q++) {
+            vdl_plan *p = ms[(size_t)q]->p;
+            try {
+                finalize_end(c, p, 0);
+                p->batch_words = false;
+                if (p->order.set) order_outputs_on_host(p);
+            } catch (const Error &e) {
+                p->batch_words = false;
+                throw Error(e.code, "plan " + std::to_string(ms[(size_t)q]->index) + ": " + e.what());
+            }
+            if (ev.a && q == 0) HIP_CHECK(hipEventElapsedTime(&ms_scan, ev.a, ev.b));       // (the copies behind the scan are done: so is the scan)
+            // the whole batch kernel's time, under a label of its own: never a per-query figure
+            if (ev.a && p->profiling) p->timings.push_back({"timeInMicrosecondsForBatchedScan_" + name, (double)ms_scan * 1e3});
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        if (alone[(size_t)i].empty()) continue;
+        if (!check_only) {
+            const int rc = vdl_run(c, plans[i]);
+            if (rc != VDL_OK) throw Error(rc, "plan " + std::to_string(i) + ": " + c->err);
+        }
+        plans[i]->batch_note = "alone: " + alone[(size_t)i];
+    }
+}
+int batch_args_ok(vdl_ctx *c, vdl_plan *const *plans, int n, const char *who) {
+    if (!c) return VDL_ERR_ARG;
+    auto fail = [&](const std::string &why) { c->err = std::string(who) + ": " + why; return (int)VDL_ERR_ARG; };
+    if (!plans || n < 1) return fail("no plans given");
+    for (int i = 0; i < n; i++) {
+        if (!plans[i]) return fail("plan " + std::to_string(i) + " is null");
+        for (int j = 0; j < i; j++) if (plans[j] == plans[i]) return fail("plans " + std::to_string(j) + " and " + std::to_string(i) + " are the same plan");
+    }
+    return VDL_OK;
+}
+}  // namespace
+
+int vdl_run_batch(vdl_ctx *c, vdl_plan *const *plans, int n) {
+    if (const int rc = batch_args_ok(c, plans, n, "vdl_run_batch")) return rc;
+    return guard(c, [&] {
+        need_device(c);
+        run_batches(c, plans, n, false);
+    });
+}
+int vdl_batch_jit_check(vdl_ctx *c, vdl_plan *const *plans, int n) {
+    if (const int rc = batch_args_ok(c, plans, n, "vdl_batch_jit_check")) return rc;
+    return guard(c, [&] { run_batches(c, plans, n, true); });
+}
+const char *vdl_plan_batch_note(const vdl_plan *p) { return p ? p->batch_note.c_str() : ""; }
 
 int vdl_n_outputs(const vdl_plan *p) { return p ? (int)p->outs.size() : 0; }
 int vdl_output(const vdl_plan *p, int k, const char **name, const char **tmp, const int64_t **vals, size_t *n) {

@@ -120,6 +120,7 @@ struct ExprNode;
 struct LazyGather;
 struct CommState;        // vdl_comm.cpp: the context's communicator (RCCL or host transport)
 struct ShardState;       // vdl_comm.cpp: per-plan buffers of the sharded fold route
+struct BatchEntry;       // vdl_specialise.cpp: a batched scan's kernel and device buffers
 
 struct DVec {
     enum Kind { NONE, DENSE, COLUMN, RANGE, ONEHOT, OHCONST, SPARSE, EXPR, LAZYG } kind = NONE;
@@ -197,6 +198,8 @@ struct vdl_ctx {
     uint64_t binding_version() const { return catalog_version + (overlay_epoch << 40); }
     std::shared_ptr<Pool> pool = std::make_shared<Pool>();
     std::shared_ptr<CommState> comm;       // vdl_comm_init / vdl_comm_init_host
+    // batched scans (vdl_run_batch) by shape, columns and width: the loaded kernel with its grid, the descriptors and partials on the device
+    std::map<std::string, std::shared_ptr<BatchEntry>> batches;
     std::string err;
     // a few words of PINNED host memory for the round trips of the executors (survivor counts, sortedness verdicts): a copy
     // into pageable memory is staged by the runtime and cost 20-30 us of idle GPU each (Q3 at SF10: three of them per query)
@@ -287,6 +290,8 @@ struct vdl_plan {
     std::shared_ptr<void> front_keep;                        // the fused front's bound descriptors of the current run, likewise
     std::vector<char> kscan;                 // [scan] runs on the single-aggregate k_scan (decided when the plan is bound / tuned)
     std::string jit_note;                    // what was specialised, or why not
+    std::string batch_note;                  // what the last vdl_run_batch / vdl_batch_jit_check did with this plan ("" after a plain vdl_run)
+    bool batch_words = false;                // vdl_run_batch: n_words / word_offset are set for a finalisation although the plan is not bound
     // by scan role ("scan<k>", "front.select", "front.take", "dim<k>", "semi<k>"): the catalog columns the scan bound last read from their
     // images, "name:width ..." (vdl_plan_image_columns); roles without one hold ""
     std::map<std::string, std::string> image_roles;

@@ -300,6 +300,7 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
     o << "#define VDL_SPEC_UNROLL _Pragma(\"unroll\")\n";
     const bool rt = sh.rt_bounds;
     if (rt) o << "#define VDL_RT_BOUNDS 1\n";
+    if (kind == MSCAN && sh.batch) o << "#define VDL_BATCH " << sh.batch << "\n#define VDL_BATCH_NAGG " << D.nagg << "\n";
     if (kind == MSCAN && sh.census) o << "#define VDL_CENSUS 1\n";
     if (kind == MSCAN && C.packed) o << "#define VDL_PACKED 1\n";
     if (kind == MSCAN && C.lazy && C.packed) {
@@ -402,7 +403,12 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
     }
     o << "#define VDL_PROJ_U " << VDL_PROJ_U_HOST << "\n" << kEmbedded << "\n" << desc_text(kind, C, D, "", rt);      // (the tile of the projection scan as this library was built)
     const char *b = sh.vec ? "true" : "false";
-    if (kind == MSCAN)
+    if (kind == MSCAN && sh.batch)
+        o << "extern \"C\" __global__ __launch_bounds__(256) void " << entry_name(kind, C, D, sh) << "(const vdl::MsArgs Cr, const vdl::MsBatch B) {\n"
+             "    constexpr vdl::MsArgs C = vdl::jit_args();\n"
+             "    constexpr vdl::MScanDesc D = vdl::jit_desc();\n"
+             "    vdl::mscan_body<" << sh.nc << ", " << sh.u << ", " << b << ", " << b << ", false, false, false>(C, Cr, D, *B.d[0], B);\n}\n";
+    else if (kind == MSCAN)
         o << "extern \"C\" __global__ __launch_bounds__(256) void " << entry_name(kind, C, D, sh) << "(const vdl::MsArgs Cr, const vdl::MScanDesc *__restrict__ Dp) {\n"
              "    constexpr vdl::MsArgs C = vdl::jit_args();\n"
              "    constexpr vdl::MScanDesc D = vdl::jit_desc();\n"
@@ -450,7 +456,7 @@ std::string entry_name(Kind kind, const MsArgs &C, const MScanDesc &D, const Sha
     int eager_filters = 0;
     for (int c = 0; c < C.ncol; c++) eager_filters += ((C.filtered >> c) & 1u) && !((C.derived >> c) & 1u) && C.stage(c) == 0;
     return std::string("vdl_jit_mscan_") + (sh.grouped ? "grouped_" : "") + (C.packed ? "packed_" : "") + "u" + std::to_string(sh.u) + (C.lazy ? "_staged" + std::to_string(eager_filters) + "_" : "_") +
-           (sh.census ? "census_" : "") + tag + (sh.rt_bounds ? "_rtb" : "");
+           (sh.census ? "census_" : "") + tag + (sh.batch ? "_batch" + std::to_string(sh.batch) : "") + (sh.rt_bounds ? "_rtb" : "");
 }
 
 bool compile(const std::string &src, const std::string &arch, std::vector<char> &code, std::string &log, Origin *origin) {

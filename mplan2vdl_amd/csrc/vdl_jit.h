@@ -15,7 +15,10 @@ struct Shape { int nc = 0, u = 0; bool vec = false, grouped = false, der = false
                bool census = false;        // census: a staged scan's late loads also count the 128-byte lines they ask for (measurement builds)
                // run-time bounds (vdl_plan_set_jit_bounds): the text holds the shapes of the range filters and formula tests, the kernel
                // reads their values from the launch's descriptor -- plans that differ in literals alone share source, key and code
-               bool rt_bounds = false; };
+               bool rt_bounds = false;
+               // a batched scan (vdl_run_batch): that many plans' descriptors per launch, each with its own count and accumulators
+               // (vdl_mscan_body.h VDL_BATCH); 0 = the scan of one plan.  Always with rt_bounds: that is what makes the code shareable
+               int batch = 0; };
 
 // what is specialised: an aggregate scan, or the two passes of the projection scan (fused front; dimension scans are the
 // select pass with bitmap_only set)

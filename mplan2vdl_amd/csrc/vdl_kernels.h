@@ -57,6 +57,10 @@ const char *mscan_kernel_name(const ScanLaunch &cfg);
 // jit_fn: the scan kernel specialised for this plan (vdl_jit.cpp) instead of the precompiled variant cfg names
 hipError_t launch_mscan(const MScanCols &cols, const MScanDesc &d, const MScanDesc *dev_desc, const ScanLaunch &cfg, bool grouped,
                         bool never, int64_t *out, bool resolve_first, hipStream_t s, hipFunction_t jit_fn = nullptr);
+// A batched scan (vdl_run_batch): `fn` is the kernel specialised for k plans that share `cols` (vdl_jit.cpp, Shape::batch), b.d[q] slot
+// q's descriptor on the device, b.partials room for grid x k x (1 + nagg) words; the finish step folds the blocks' partials and leaves slot
+// q's 1 + nagg words at outs[q].  d: any slot's descriptor on the host (the aggregates' kinds are the same in all of them).
+hipError_t launch_mscan_batch(const MScanCols &cols, const MScanDesc &d, const MsBatch &b, int k, int grid, int64_t *const *outs, hipStream_t s, hipFunction_t fn);
 // for the specialiser: the by-value arguments, the chosen variant's shape, the dynamic LDS of a launch
 MsArgs mscan_args(const MScanCols &cols);
 void mscan_variant_shape(const ScanLaunch &cfg, int *nc, int *u, bool *vec, bool *grouped, bool *der);

@@ -68,6 +68,26 @@ __global__ __launch_bounds__(256) void k_mscan_finish(const MScanDesc *__restric
     if (lane == 0) out[i] = x;
 }
 
+// the finish step of a batched scan: out[q][w] = fold over blocks of partials[b][q][w]; one wave per word
+struct MsBatchFinish {
+    const int64_t *partials;
+    int64_t *out[kMaxBatch];
+    int k, w;
+    int rk[kMaxGroupAggs + 1];
+};
+__global__ __launch_bounds__(256) void k_mscan_batch_finish(const MsBatchFinish f, int nblocks) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int i = (int)blockIdx.x * (int)(blockDim.x / kWave) + (int)(threadIdx.x / kWave);
+    const int words = f.k * f.w;
+    if (i >= words) return;
+    const int q = i / f.w, w = i % f.w;
+    const int rk = f.rk[w];
+    int64_t x = r_identity(rk);
+    for (int b = lane; b < nblocks; b += kWave) x = r_combine(rk, x, f.partials[(int64_t)b * words + i]);
+    x = wave_reduce(x, rk);
+    if (lane == 0) f.out[q][w] = x;
+}
+
 // FoldChoose per group: replace the group's smallest (global) row id by that row's column value.
 // owned_only (sharded execution, after the MIN all-reduce of the row ids): only the rank that holds the
 // row writes the value, every other rank writes 0, and a SUM all-reduce then spreads it.
@@ -201,6 +221,28 @@ hipError_t launch_mscan(const MScanCols &cols, const MScanDesc &d, const MScanDe
     const int64_t words = grouped ? d.pcount * (d.nagg + 1) + 1 : d.nagg + 1;
     k_mscan_finish<<<(int)((words + 3) / 4), 256, 0, s>>>(dev_desc, nblocks, grouped ? 1 : 0, out);
     if (grouped && resolve_first) k_mscan_first<<<(int)((d.pcount + 255) / 256), 256, 0, s>>>(ms_args(cols), dev_desc, 0, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_mscan_batch(const MScanCols &cols, const MScanDesc &d, const MsBatch &b, int k, int grid, int64_t *const *outs, hipStream_t s, hipFunction_t fn) {
+    (void)hipGetLastError();
+    if (k < 2 || k > kMaxBatch || k * (d.nagg + 1) > kMaxBatchWords || grid < 1 || !fn) return hipErrorInvalidValue;
+    int nblocks = 0;
+    if (cols.n > 0) {
+        MsArgs a = ms_args(cols);
+        MsBatch bb = b;
+        void *params[] = {&a, &bb};
+        const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, (unsigned)kMsBlock, 1, 1, 0, s, params, nullptr);
+        if (e != hipSuccess) return e;
+        nblocks = grid;
+    }
+    MsBatchFinish f;
+    f.partials = b.partials;
+    f.k = k; f.w = d.nagg + 1;
+    for (int q = 0; q < kMaxBatch; q++) f.out[q] = q < k ? outs[q] : nullptr;
+    f.rk[0] = R_SUM;
+    for (int j = 0; j < kMaxGroupAggs; j++) f.rk[j + 1] = j >= d.nagg || d.agg[j].kind == AGG_SUM ? R_SUM : d.agg[j].kind == AGG_MAX ? R_MAX : R_MIN;      // (rk_of, on the host)
+    k_mscan_batch_finish<<<(k * f.w + 3) / 4, 256, 0, s>>>(f, nblocks);
     return hipGetLastError();
 }
 

@@ -250,6 +250,42 @@ __device__ __forceinline__ void eval_pass(const MsArgs &C, const MScanDesc &D, c
     }
 }
 
+#ifdef VDL_BATCH
+// eval_pass of a batched scan: it runs once per slot, so its compares are the kernel's cost (Q6 x 8: five per row and slot), and they
+// are made as narrow as the column.  A closed side of a range under run-time bounds lies strictly inside the domain its column is read
+// in (vdl_jit.cpp range_shape: a bound at or beyond the domain's end is an open side and folds away) or selects nothing; the bounds of
+// a packed column are the packed image's, 32 unsigned bits, and those of a column or byte image of 1 or 2 bytes are handed in clamped
+// to one step outside its domain (vdl_specialise.cpp batch_launch), 32 signed bits, for every slot: they have one shape.
+template <int NC, int RW>
+__device__ __forceinline__ void eval_pass_narrow(const MsArgs &C, const MScanDesc &D, const MScanDesc &Dr, const int64_t (&v)[NC][RW], bool (&pass)[RW]) {
+#pragma unroll
+    for (int r = 0; r < RW; r++) pass[r] = true;
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        if ((C.filtered >> c) & 1u) {                      // wave-uniform (bits only below ncol)
+            int64_t lo, hi;
+            range_bounds(D.flo[c], D.fhi[c], Dr.flo[c], Dr.fhi[c], lo, hi);
+            if ((C.packed >> c) & 1u) {
+#pragma unroll
+                for (int r = 0; r < RW; r++) pass[r] = pass[r] & ((uint32_t)v[c][r] >= (uint32_t)lo) & ((uint32_t)v[c][r] <= (uint32_t)hi);
+            } else if (C.width(c) < 4 && D.flo[c] != INT64_MIN && D.fhi[c] != INT64_MAX) {
+#pragma unroll
+                for (int r = 0; r < RW; r++) pass[r] = pass[r] & ((int32_t)v[c][r] >= (int32_t)lo) & ((int32_t)v[c][r] <= (int32_t)hi);
+            } else if (C.width(c) < 4 && D.flo[c] != INT64_MIN) {
+#pragma unroll
+                for (int r = 0; r < RW; r++) pass[r] = pass[r] & ((int32_t)v[c][r] >= (int32_t)lo);
+            } else if (C.width(c) < 4 && D.fhi[c] != INT64_MAX) {
+#pragma unroll
+                for (int r = 0; r < RW; r++) pass[r] = pass[r] & ((int32_t)v[c][r] <= (int32_t)hi);
+            } else {
+#pragma unroll
+                for (int r = 0; r < RW; r++) pass[r] = pass[r] & (v[c][r] >= lo) & (v[c][r] <= hi);
+            }
+        }
+    }
+}
+#endif
+
 // Derived columns (vdl_fuse.h VColKind): values looked up through an earlier column -- the dimension side of an FK join
 // seen from the fact table (Vlite.hs:1199-1282).  `alive` starts as "the direct range filters pass", so rows a cheap
 // filter already rejects do no lookups (Q14 keeps 1 row in 84); a lookup out of range makes the row EPS (alive = false).
@@ -463,7 +499,11 @@ __device__ __forceinline__ void eval_term(const MAggDesc &d, const int64_t (&v)[
 // same objects for both; a kernel specialised for one plan (vdl_jit.cpp) passes compile-time constants for C and D, and the
 // compiler folds every descriptor-driven branch and loop of this body away.
 template <int NC, int U, bool VEC, bool NT, bool GROUPED, bool DER, bool STAGED = false>
-__device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, const MScanDesc &D, const MScanDesc &Dr) {
+__device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, const MScanDesc &D, const MScanDesc &Dr
+#ifdef VDL_BATCH
+                                           , const MsBatch &B
+#endif
+                                           ) {
     extern __shared__ int64_t lds[];
     constexpr int BS = kMsBlock, TILE = BS * 2 * U, ROWS = 2 * U;
     const int tid = threadIdx.x;
@@ -489,6 +529,23 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
 #pragma unroll
     for (int c = 0; c < NC; c++) census_cnt[c] = 0;
 #endif
+#ifdef VDL_BATCH
+    // The BATCHED form (vdl_run_batch; specialised global aggregate scans over table columns, every column read with the tile or the
+    // stripe): VDL_BATCH plans share the pass.  A row's values and its aggregate terms do not depend on anybody's bounds and are
+    // computed once; the filters and the accumulation run once per slot, against that slot's descriptor (B.d[q]: scalar loads), into
+    // that slot's own count and accumulators -- VDL_BATCH x (1 + VDL_BATCH_NAGG) 64-bit values per lane, in registers (the host
+    // caps the product at kMaxBatchWords), not in LDS lane slots: nothing is launched with dynamic LDS.
+    static_assert(!GROUPED && !DER && !STAGED, "batched scans are global aggregate scans over table columns that read nothing late");
+    static_assert(VDL_BATCH >= 2 && VDL_BATCH <= kMaxBatch && VDL_BATCH * (1 + VDL_BATCH_NAGG) <= kMaxBatchWords, "the slots' accumulators fit their registers");
+    constexpr int KB = VDL_BATCH, NA = VDL_BATCH_NAGG, NA1 = NA > 0 ? NA : 1;
+    int64_t bcnt[KB], bacc[KB][NA1];
+#pragma unroll
+    for (int q = 0; q < KB; q++) {
+        bcnt[q] = 0;
+#pragma unroll
+        for (int j = 0; j < NA; j++) bacc[q][j] = r_identity(rk_of(D.agg[j].kind));
+    }
+#else
     if (GROUPED) {
         for (int r = 0; r < R; r++)
             for (int64_t i = tid; i < words; i += BS) {
@@ -505,6 +562,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
         for (int j = 0; j < nagg; j++) lds[(int64_t)j * BS + tid] = r_identity(rk_of(D.agg[j].kind));
     }
     __syncthreads();
+#endif
 
     // tile0, tile_rows: the first row (an index into the columns) and the rows of the tile the lane's rows lie in -- wave-uniform, the
     // generated late loads build their buffer resources from them
@@ -528,6 +586,45 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
 #endif
         // (the stages arrive as generated straight-line code -- VDL_STAGED_PRE / _POST, vdl_jit.cpp: written as loops over
         // columns and stages with the stage numbers read from C, the compiler no longer folded the descriptor: 235 KB of code)
+#ifdef VDL_BATCH
+        {
+            int64_t t[NA1][RW];
+#pragma unroll
+            for (int j = 0; j < NA; j++) eval_term<NC, RW>(D.agg[j], v, rowid, t[j]);
+#pragma unroll
+            for (int q = 0; q < KB; q++) {
+                bool pq[RW];
+                eval_pass_narrow<NC, RW>(C, D, *B.d[q], v, pq);
+                if (PACKED) {
+#pragma unroll
+                    for (int r = 0; r < RW; r++) pq[r] = pq[r] & alive[r];
+                }
+                // (the slot's count is the WAVE's: the population of each row's lane mask, scalar work -- lane 0 hands it in at the end)
+                int here = 0;
+#pragma unroll
+                for (int r = 0; r < RW; r++) here += __popcll(__ballot(pq[r]));
+                bcnt[q] += here;
+#pragma unroll
+                for (int j = 0; j < NA; j++) {
+                    const int rk = rk_of(D.agg[j].kind);
+                    int64_t s = r_identity(rk);
+                    if (rk == R_SUM) {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) s = (int64_t)((uint64_t)s + (uint64_t)(pq[r] ? t[j][r] : 0));
+                    } else if (rk == R_MIN) {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) s = (pq[r] && t[j][r] < s) ? t[j][r] : s;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) s = (pq[r] && t[j][r] > s) ? t[j][r] : s;
+                    }
+                    bacc[q][j] = r_combine(rk, bacc[q][j], s);
+                }
+            }
+            (void)rows_left; (void)tile0; (void)tile_rows; (void)staged;
+            return;
+        }
+#endif
 #ifdef VDL_STAGED_PRE
         if (staged) { VDL_STAGED_PRE }
 #endif
@@ -843,6 +940,35 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
     __syncthreads();
     __shared__ int64_t red[kMsBlock / kWave];
     const int lane = tid & (kWave - 1), wave = tid / kWave;
+#ifdef VDL_BATCH
+    {
+        // the block's partials, [slot][count, aggregates]: every value folded over the wave, then over the block's waves by the lane
+        // that writes it
+        constexpr int WB = NA + 1;
+        __shared__ int64_t bred[kMsBlock / kWave][KB * WB];
+#pragma unroll
+        for (int q = 0; q < KB; q++) {
+#pragma unroll
+            for (int w = 0; w < WB; w++) {
+                const int rk = w == 0 ? R_SUM : rk_of(D.agg[w > 0 ? w - 1 : 0].kind);
+                const int64_t x = w == 0 ? bcnt[q] : wave_reduce(bacc[q][w > 0 ? w - 1 : 0], rk);      // (the counts are wave-uniform already)
+                if (lane == 0) bred[wave][q * WB + w] = x;
+            }
+        }
+        __syncthreads();
+        if (tid < KB * WB) {
+            const int w = tid % WB;
+            int rk = R_SUM;
+#pragma unroll
+            for (int j = 0; j < NA; j++) if (w == j + 1) rk = rk_of(D.agg[j].kind);
+            int64_t y = bred[0][tid];
+            for (int k = 1; k < kMsBlock / kWave; k++) y = r_combine(rk, y, bred[k][tid]);
+            B.partials[(int64_t)blockIdx.x * (KB * WB) + tid] = y;
+        }
+        (void)red; (void)cnt; (void)oob; (void)mytab; (void)trash; (void)rstride; (void)R;
+        return;
+    }
+#endif
 #ifdef VDL_CENSUS
     if (lane == 0 && Dr.census) {
 #pragma unroll

@@ -156,6 +156,16 @@ struct MScanDesc {                           // lives in device memory, read wit
 };
 constexpr int kMaxCarry = 2;
 
+// A batched scan (vdl_run_batch; VDL_BATCH in vdl_mscan_body.h): up to kMaxBatch plans that differ in the values of their bounds
+// alone are answered by one pass over the columns.  The kernel takes the plans' descriptors -- d[q] is slot q's, read like any
+// launch descriptor: wave-uniform scalar loads -- and one partials area for all of them, [grid][slots][1 + nagg] words.
+constexpr int kMaxBatch = 8;
+constexpr int kMaxBatchWords = 32;           // slots x (1 + nagg): a lane keeps that many 64-bit accumulators in registers
+struct MsBatch {
+    const MScanDesc *d[kMaxBatch] = {};
+    int64_t *partials = nullptr;
+};
+
 // What the scan kernels take by value: column bases (kept in the global address space), the widths and the
 // filtered-column set packed into one word each.  (MScanCols itself held 64 SGPRs live across the tile loop -- widths,
 // flags and sixteen 64-bit bounds -- and the grouped kernel spilled hundreds of scalar values into VGPR lanes; the

@@ -272,6 +272,28 @@ bool specialise_scan(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, std::strin
     return true;
 }
 
+struct TimingEvents {                                          // (destroyed on every way out, also a throwing HIP_CHECK)
+    hipEvent_t a = nullptr, b = nullptr;
+    ~TimingEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+// a candidate's time is the MEDIAN of five launches after the module's first, and a later candidate only replaces the one
+// in hand when it is more than 2 % quicker: forms within the noise of each other no longer swap places from run to run
+template <typename Launch>
+static float median_launch_ms(vdl_ctx *c, TimingEvents &ev, Launch &&launch) {
+    std::vector<float> times;
+    for (int rep = 0; rep < 6; rep++) {
+        HIP_CHECK(hipEventRecord(ev.a, c->stream));
+        launch();
+        HIP_CHECK(hipEventRecord(ev.b, c->stream));
+        HIP_CHECK(hipEventSynchronize(ev.b));
+        float t = 0;
+        HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (rep > 0) times.push_back(t);                    // the first launch of a module pays for its load
+    }
+    std::sort(times.begin(), times.end());
+    return times[times.size() / 2];
+}
+
 // vdl_plan_set_jit(plan, 2): at the first run, with the real columns and lookup tables in place, every specialised scan is
 // built in up to eleven forms (a second each) -- 2, 3, 4, 6 row pairs per lane, then the staged forms that read late (one or two
 // filter columns with the tile) at the winner's and at smaller shapes -- and the quickest of three timed launches stays; for a
@@ -280,28 +302,10 @@ bool specialise_scan(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, std::strin
 // 3.96 ms for 2 / 3 / 4 / 6 pairs (staged: 4.1-4.2), Q6 2.7 / 2.5 / 2.4 / 2.5 ms eager, 1.63 staged, 2.38 on k_scan.
 void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
     const size_t ns = p->fused.scans.size(), ng = p->fused.gscans.size();
-    struct Events {                                            // (destroyed on every way out, also a throwing HIP_CHECK)
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
+    TimingEvents ev;
     HIP_CHECK(hipEventCreate(&ev.a));
     HIP_CHECK(hipEventCreate(&ev.b));
-    // a candidate's time is the MEDIAN of five launches after the module's first, and a later candidate only replaces the one
-    // in hand when it is more than 2 % quicker: forms within the noise of each other no longer swap places from run to run
-    auto median_ms = [&](auto &&launch) {
-        std::vector<float> times;
-        for (int rep = 0; rep < 6; rep++) {
-            HIP_CHECK(hipEventRecord(ev.a, c->stream));
-            launch();
-            HIP_CHECK(hipEventRecord(ev.b, c->stream));
-            HIP_CHECK(hipEventSynchronize(ev.b));
-            float t = 0;
-            HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-            if (rep > 0) times.push_back(t);                    // the first launch of a module pays for its load
-        }
-        std::sort(times.begin(), times.end());
-        return times[times.size() / 2];
-    };
+    auto median_ms = [&](auto &&launch) { return median_launch_ms(c, ev, launch); };
     for (size_t s = 0; s < ns + ng; s++) {
         if (!p->mjit[s]) continue;
         const bool grouped = s >= ns;
@@ -486,6 +490,210 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
         p->jit_note += "scan " + std::to_string(s) + ": " + name + (b.args.packed ? " (packed: " + packed_text(p, s, *b.cols) + ")" : "") +
                        (b.args.queued ? " (queue)" : b.args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";
     }
+}
+
+// ---- batched runs ------------------------------------------------------------------------------------------------------------
+// Which plans share a scan is decided here, next to bind_form: the conditions are the packed form's (one global aggregate scan over
+// table columns) plus "the same columns" and "the same generated code under run-time bounds".
+std::string batch_alone_reason(const vdl_plan *p) {
+    if (!p->use_fusion || !p->fused.ok) return "the plan is not fused";
+    if (!p->use_jit) return "specialisation is off";
+    const FusedPlan &F = p->fused;
+    if (!F.gscans.empty()) return "grouped scans are not batched";
+    if (F.scans.size() != 1) return "the plan has " + std::to_string(F.scans.size()) + " scans, a batch shares exactly one";
+    if (!F.prelude.empty()) return "scans with lookup tables or semi-join sets are not batched";
+    for (const ScanColumn &sc : F.scans[0].cols)
+        if (sc.kind != VC_DIRECT) return "scans with derived columns are not batched";
+    if (F.scans[0].never) return "its filters can hold for no row: there is nothing to scan";
+    return "";
+}
+int batch_cap(int nagg) { return std::min(kMaxBatch, kMaxBatchWords / (1 + std::max(nagg, 0))); }
+
+// the shape of a batch's kernel in form f: the scan's own shape, with the bounds at run time whatever the plans' own setting
+static jit::Shape batch_shape(const BatchMember &m, const ScanForm &f, int k) {
+    jit::Shape sh = jit_shape(m.cols, m.cfg, f, true);
+    sh.grouped = false;
+    sh.der = false;
+    sh.batch = k;
+    return sh;
+}
+void batch_bind(vdl_ctx *c, vdl_plan *p, BatchMember &m) {
+    m.p = p;
+    m.desc = std::make_shared<MScanDesc>();
+    int64_t bpr = 0;
+    bind_mscan(c, p->fused.scans[0], m.cols, *m.desc, &bpr, p->row_offset);
+    m.cfg = mscan_launch_config(m.cols, *m.desc, false, c->num_cus);
+    if (m.cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no multi-aggregate scan kernel variant for this shape");
+    std::ostringstream k;
+    k << m.cols.ncol << ":" << m.cols.n << ":" << m.cols.row0 << ":" << m.cols.image;
+    for (int i = 0; i < m.cols.ncol; i++) k << ":" << m.cols.ptr[i] << "/" << m.cols.width[i];
+    m.cols_key = k.str();
+    m.shape_key = jit::entry_name(jit::MSCAN, mscan_args(m.cols), *m.desc, batch_shape(m, ScanForm{}, 0));
+}
+
+}  // namespace eng
+}  // namespace vdl
+
+struct vdl::eng::BatchEntry {
+    std::shared_ptr<jit::Kernel> k;
+    int grid = 0, per_cu = 0;
+    ScanForm form;                             // (u: the row pairs per lane / per slice it was built at)
+    std::string name, entry;
+    size_t code_bytes = 0;
+    BufP descs, partials;
+    size_t partial_words = 0;
+    std::vector<unsigned char> shadow;         // what `descs` holds: uploaded again only when some slot's descriptor changed
+};
+
+namespace vdl {
+namespace eng {
+
+// every member's binding in form f -- packed bounds live in the packed image's domain -- or false and why: the form does not exist for
+// a member, or the members' bindings in it do not give ONE code over ONE set of columns (a bound that falls off a packed image's end
+// for one plan only is another shape there)
+static bool batch_bind_form(vdl_ctx *c, const std::vector<BatchMember *> &ms, const ScanForm &f, const jit::Shape &sh, std::vector<BoundForm> &bound, std::string &entry,
+                            std::string &why) {
+    const size_t K = ms.size();
+    bound.assign(K, BoundForm{});
+    for (size_t q = 0; q < K; q++) {
+        if (!bind_form(c, ms[q]->p, 0, false, f, sh.u, ms[q]->cols, *ms[q]->desc, bound[q], why)) return false;
+        const MsArgs &a = bound[q].args, &a0 = bound[0].args;
+        const std::string name = jit::entry_name(jit::MSCAN, a, *bound[q].desc, sh);
+        if (q == 0) entry = name;
+        bool same = name == entry && a.n == a0.n && a.row0 == a0.row0 && a.packed == a0.packed && a.pbits == a0.pbits && a.widths == a0.widths && a.ncol == a0.ncol;
+        for (int k = 0; k < a0.ncol && same; k++) same = a.ptr[k] == a0.ptr[k];
+        if (!same) { why = "the plans' bindings differ in this form"; return false; }
+    }
+    return true;
+}
+// the batch's kernel over the members' bindings: compiled, and unless check_only loaded, with the grid its registers allow
+static bool batch_build(vdl_ctx *c, const ScanForm &f, const jit::Shape &sh, const std::vector<BoundForm> &bound, const std::string &entry, bool check_only, BatchEntry &out,
+                        std::string &why) {
+    const MsArgs &args = bound[0].args;
+    const MScanDesc &desc = *bound[0].desc;
+    std::vector<char> code;
+    if (!jit::compile(jit::mscan_source(args, desc, sh), c->arch, code, why)) { why = why.substr(0, 2000); return false; }
+    if (code.size() > (size_t)96 << 10) { why = "the descriptor did not fold (" + std::to_string(code.size()) + " B of code)"; return false; }
+    out = BatchEntry{};
+    out.form = f; out.form.u = sh.u;
+    out.code_bytes = code.size();
+    out.entry = entry;
+    out.name = jit_name(sh, bound[0].cols->image != 0);
+    out.name.insert(out.name.size() - 1, std::string(f.suffix()) + ",batch" + std::to_string(sh.batch) + ",rtb");
+    if (check_only) return true;
+    out.k = jit::load(code, why, entry);
+    if (!out.k) return false;
+    int per_cu = 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, out.k->fn, 256, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 2; }
+    if (per_cu > 8) per_cu = 8;
+    int64_t grid = (int64_t)c->num_cus * per_cu;
+    // (the packed form: one wave per stripe of 2048 rows at a time, four per block)
+    const int64_t most = f.kind == ScanForm::PACKED ? (img::stripes(args.n) + 3) / 4 : args.n / ((int64_t)256 * 2 * sh.u);
+    if (grid > most) grid = most;
+    if (grid < 1) grid = 1;
+    out.grid = (int)grid; out.per_cu = per_cu;
+    return true;
+}
+
+// the slots' descriptors on the device (uploaded when they differ from what is there), the partials area, the launch
+static void batch_launch(vdl_ctx *c, BatchEntry &e, const std::vector<BoundForm> &bound, int64_t *const *outs) {
+    const int K = (int)bound.size(), W = bound[0].desc->nagg + 1;
+    std::vector<unsigned char> want(sizeof(MScanDesc) * (size_t)K);
+    for (int q = 0; q < K; q++) {
+        MScanDesc d = *bound[(size_t)q].desc;
+        d.block_partials = nullptr;                            // (the batch has one partials area: MsBatch)
+        // the kernel compares a 1- or 2-byte column in 32 bits (eval_pass_narrow): a bound beyond the column's domain says the same one
+        // step outside it
+        const MsArgs &a = bound[(size_t)q].args;
+        for (int k = 0; k < a.ncol; k++) {
+            if (!((a.filtered >> k) & 1u) || ((a.packed >> k) & 1u) || a.width(k) >= 4) continue;
+            const int64_t top = ((int64_t)1 << (8 * a.width(k) - 1));
+            d.flo[k] = std::min(d.flo[k], top);
+            d.fhi[k] = std::max(d.fhi[k], -top - 1);
+        }
+        std::memcpy(want.data() + sizeof(MScanDesc) * (size_t)q, &d, sizeof d);
+    }
+    if (!e.descs) e.descs = dev_alloc(c, want.size());
+    if (want != e.shadow) {
+        e.shadow.swap(want);                                   // (the source of the copy stays put until the next upload)
+        HIP_CHECK(hipMemcpyAsync(e.descs->p, e.shadow.data(), e.shadow.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    const size_t words = (size_t)e.grid * (size_t)K * (size_t)W;
+    if (!e.partials || e.partial_words < words) { e.partials = dev_alloc(c, sizeof(int64_t) * words); e.partial_words = words; }
+    MsBatch b;
+    for (int q = 0; q < K; q++) b.d[q] = (const MScanDesc *)e.descs->p + q;
+    b.partials = (int64_t *)e.partials->p;
+    HIP_CHECK(launch_mscan_batch(*bound[0].cols, *bound[0].desc, b, K, e.grid, outs, c->stream, e.k->fn));
+}
+
+std::string batch_scan(vdl_ctx *c, const std::vector<BatchMember *> &ms, bool tune, bool check_only, int64_t *const *outs, hipEvent_t ev0, hipEvent_t ev1) {
+    const int K = (int)ms.size();
+    if (K < 2 || K > batch_cap(ms[0]->desc->nagg)) throw Error(VDL_ERR_ARG, "a batch of " + std::to_string(K) + " plans does not fit the kernel");
+    // VDL_JIT_PIN="u=2,late=6" leaves the tuner one candidate as it does for a plan's own scan: late=6 the packed form, any other value eager
+    int pin_u = 0, pin_late = 0;
+    const char *pin = tune ? getenv("VDL_JIT_PIN") : nullptr;
+    if (pin) {
+        if (const char *q = strstr(pin, "u=")) pin_u = atoi(q + 2);
+        if (const char *q = strstr(pin, "late=")) pin_late = atoi(q + 5);
+    }
+    const char *env_u = getenv("VDL_JIT_U");
+    const std::string key = ms[0]->shape_key + "|" + ms[0]->cols_key + "|" + std::to_string(K) + (tune ? "|tuned|" : "||") + (pin ? pin : "") + "|" + (env_u ? env_u : "") +
+                            (c->images ? "|img" : "|") + (check_only ? "|check" : "");
+    std::vector<BoundForm> bound;
+    std::string why, entry;
+    std::shared_ptr<BatchEntry> e;
+    auto hit = c->batches.find(key);
+    if (hit != c->batches.end()) {
+        // the kernel in hand serves these plans when their bindings in its form give its code again (the eager form: always)
+        e = hit->second;
+        if (!batch_bind_form(c, ms, e->form, batch_shape(*ms[0], e->form, K), bound, entry, why) || entry != e->entry) { c->batches.erase(hit); e = nullptr; }
+    }
+    if (!e) {
+        // {row pairs per lane or slice (0: the launch configuration's), form as ScanForm::from_code}: untuned the eager form as the scan's own
+        // shape has it; tuned the eager form at 2, 3, 4 and the every-column packed form at 2, 4, by the tuner's rule; the staged, queue
+        // and packed-late forms are not batched
+        std::vector<std::pair<int, int>> cands = {{0, 0}};
+        if (tune && pin_u > 0) cands = {{pin_u, pin_late == 6 ? 6 : 0}};
+        else if (tune && !check_only) cands = {{2, 0}, {3, 0}, {4, 0}, {2, 6}, {4, 6}};
+        TimingEvents ev;
+        if (cands.size() > 1) { HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); }
+        float best_ms = 0;
+        std::vector<BoundForm> best_bound;
+        std::string first_why;
+        for (const auto &cu : cands) {
+            const ScanForm f = ScanForm::from_code(cu.second, cu.first);
+            const jit::Shape sh = batch_shape(*ms[0], f, K);
+            if (cands.size() > 1 && f.kind != ScanForm::PACKED && (int64_t)256 * 2 * sh.u > ms[0]->cols.n) continue;
+            auto cand = std::make_shared<BatchEntry>();
+            std::vector<BoundForm> cb;
+            std::string cwhy, centry;
+            if (!batch_bind_form(c, ms, f, sh, cb, centry, cwhy) || !batch_build(c, f, sh, cb, centry, check_only, *cand, cwhy)) {
+                if (first_why.empty()) first_why = cwhy;
+                continue;
+            }
+            float ms_ = 0;
+            if (cands.size() > 1) ms_ = median_launch_ms(c, ev, [&] { batch_launch(c, *cand, cb, outs); });
+            if (!e || ms_ < best_ms * 0.98f) { e = cand; best_ms = ms_; best_bound = cb; }
+        }
+        if (!e && !(cands.size() == 1 && cands[0] == std::make_pair(0, 0))) {
+            // no candidate exists for these plans (a table shorter than a tile, a pinned packed form without packed images): the eager form
+            const ScanForm f{};
+            const jit::Shape sh = batch_shape(*ms[0], f, K);
+            auto cand = std::make_shared<BatchEntry>();
+            if (batch_bind_form(c, ms, f, sh, best_bound, entry, why) && batch_build(c, f, sh, best_bound, entry, check_only, *cand, why)) e = cand;
+            else first_why = why;
+        }
+        if (!e) throw Error(VDL_ERR_UNSUPPORTED, "the batched scan does not build: " + first_why);
+        bound = best_bound;
+        if (c->batches.size() > 256) c->batches.clear();
+        c->batches[key] = e;
+    }
+    if (!check_only) {
+        if (ev0) HIP_CHECK(hipEventRecord(ev0, c->stream));
+        batch_launch(c, *e, bound, outs);
+        if (ev1) HIP_CHECK(hipEventRecord(ev1, c->stream));
+    }
+    return e->name;
 }
 
 }  // namespace eng

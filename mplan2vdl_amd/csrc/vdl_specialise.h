@@ -20,5 +20,29 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p);
 void count_build(vdl_plan *p, const std::string &role, jit::Origin from);
 std::string builds_text(const vdl_plan *p, const std::string &role);
 
+
+// ---- batched runs (vdl_run_batch, vdl_batch_jit_check): plans that differ in their literals alone share one pass over the columns ----
+// why a plan cannot share a scan with any other, in the words its batch note carries; "" = it may
+std::string batch_alone_reason(const vdl_plan *p);
+// a plan's one scan as a batch sees it: its eager binding (made here, the plan's own bound state is not touched) and the two keys that
+// decide which plans go together -- the columns (addresses, widths, images, rows, row offset) and the shape of the generated code
+// under run-time bounds (jit::entry_name: the descriptor's text with the ranges' shapes in place of their values)
+struct BatchMember {
+    vdl_plan *p = nullptr;
+    int index = 0;                              // the plan's place in the caller's list
+    MScanCols cols;
+    std::shared_ptr<MScanDesc> desc;
+    ScanLaunch cfg;
+    std::string cols_key, shape_key;
+};
+void batch_bind(vdl_ctx *c, vdl_plan *p, BatchMember &m);
+// the widest batch for scans of this many aggregates: kMaxBatch, or what kMaxBatchWords accumulators per lane allow
+int batch_cap(int nagg);
+// one batch of 2 .. batch_cap plans of one group: its kernel built (kept with the context, per shape, columns and width: a second batch
+// of the same kind compiles and loads nothing) and, unless check_only, launched on the context's stream between the two events (may
+// be null) -- slot q's 1 + nagg words end up at outs[q].  Returns the kernel's name, "k_mscan_specialised<...,batch<K>,rtb>".
+// tune: the candidate forms timed first (eager at 2, 3, 4 row pairs per lane, every column packed at 2, 4 per slice; VDL_JIT_PIN pins)
+std::string batch_scan(vdl_ctx *c, const std::vector<BatchMember *> &ms, bool tune, bool check_only, int64_t *const *outs, hipEvent_t ev0, hipEvent_t ev1);
+
 }  // namespace eng
 }  // namespace vdl

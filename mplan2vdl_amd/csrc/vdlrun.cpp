@@ -20,6 +20,11 @@
 // --order-by FIELD[:asc|:desc],... names outputs by their full field name or their tmpN key, --limit N keeps the first N rows
 // (vdl_plan_set_order): the reply has the same shape with shorter, ordered lists, so resolve.py decodes it untouched.  Not with
 // --gpus: the ranks hold disjoint result rows and the merge of per-rank top-N results is not built.
+//   ... | vdlrun --jit --batch b.vdl --batch c.vdl ...                             several programs, one pass where they can share it
+// --batch FILE (repeatable; needs --jit or --jit-tune): the program on stdin and the programs in the files run as ONE vdl_run_batch --
+// those that differ in their literals alone share one scan of the columns, the others run alone inside the same call -- and one reply
+// is printed per line, stdin's first.  The options (--order-by included) apply to every program.  One line per program "vdlrun:
+// batch: <vdl_plan_batch_note>" goes to stderr.  Not with --gpus: a sharded run takes one plan.
 #include <signal.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -177,6 +182,8 @@ struct Options {
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
     long long limit = 0;
+    std::vector<std::string> batch_files;       // --batch
+    std::vector<std::string> batch_texts;       // ... and what they hold
 };
 
 // "a:desc,b,c:asc" -> fields and directions; false = malformed (empty list or field, unknown direction)
@@ -203,25 +210,35 @@ bool parse_order_by(const std::string &list, Options &o) {
 }
 
 // one rank of `world` (world = 1 without --gpus: plain vdl_run); comm_dir = where rank 0 leaves the communicator id
-int run_rank(const Options &o, const std::string &text, int rank, int world, const std::string &comm_dir, Reply &reply) {
+// (more: the replies of the --batch programs, in their order)
+int run_rank(const Options &o, const std::string &text, int rank, int world, const std::string &comm_dir, Reply &reply, std::vector<Reply> *more = nullptr) {
     vdl_ctx *ctx = nullptr;
     int rc = vdl_open(&ctx, o.describe ? -1 : (world > 1 || !comm_dir.empty() ? rank : o.device));
     if (rc) return die(ctx, "vdl_open", rc);
-    vdl_plan *plan = nullptr;
-    if ((rc = vdl_parse(ctx, text.data(), text.size(), &plan))) return die(ctx, "vdl_parse", rc);
-    vdl_plan_set_fusion(plan, o.fuse);
-    vdl_plan_set_profiling(plan, o.profile);
-    if (o.jit) vdl_plan_set_jit(plan, o.jit);
-    if (o.jit_share) vdl_plan_set_jit_bounds(plan, 1);
-    if (!o.order_fields.empty() || o.limit > 0) {
-        std::vector<const char *> fields;
-        for (const std::string &f : o.order_fields) fields.push_back(f.c_str());
-        if ((rc = vdl_plan_set_order(plan, (int)fields.size(), fields.data(), o.order_desc.data(), o.limit))) return die(ctx, "vdl_plan_set_order", rc);
+    std::vector<vdl_plan *> plans;
+    std::string loads = text;                                  // every program's text: what --data looks for Loads in
+    for (size_t k = 0; k <= o.batch_texts.size(); k++) {
+        const std::string &t = k ? o.batch_texts[k - 1] : text;
+        if (k) loads += "\n" + t;
+        vdl_plan *one = nullptr;
+        if ((rc = vdl_parse(ctx, t.data(), t.size(), &one))) return die(ctx, "vdl_parse", rc);
+        vdl_plan_set_fusion(one, o.fuse);
+        vdl_plan_set_profiling(one, o.profile);
+        if (o.jit) vdl_plan_set_jit(one, o.jit);
+        if (o.jit_share) vdl_plan_set_jit_bounds(one, 1);
+        if (!o.order_fields.empty() || o.limit > 0) {
+            std::vector<const char *> fields;
+            for (const std::string &f : o.order_fields) fields.push_back(f.c_str());
+            if ((rc = vdl_plan_set_order(one, (int)fields.size(), fields.data(), o.order_desc.data(), o.limit))) return die(ctx, "vdl_plan_set_order", rc);
+        }
+        plans.push_back(one);
+        if (o.describe) break;
     }
+    vdl_plan *plan = plans[0];
     if (o.describe) { std::fputs(vdl_plan_describe(plan), stdout); return 0; }
     int64_t row0 = 0;
     if (!o.data_dir.empty()) {
-        if (load_data_dir(ctx, o.data_dir, text, o.shard, rank, world, &row0, o.encode != 0)) return 1;
+        if (load_data_dir(ctx, o.data_dir, loads, o.shard, rank, world, &row0, o.encode != 0)) return 1;
     } else {
         row0 = o.rows * rank / world;
         const int64_t mine = o.rows * (rank + 1) / world - row0;
@@ -230,7 +247,10 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
         if (o.encode)
             for (const GenSpec &g : kLineitem) if ((rc = vdl_encode_column(ctx, g.name))) return die(ctx, "vdl_encode_column", rc);
     }
-    if (comm_dir.empty()) {
+    if (comm_dir.empty() && plans.size() > 1) {
+        if ((rc = vdl_run_batch(ctx, plans.data(), (int)plans.size()))) return die(ctx, "vdl_run_batch", rc);
+        for (vdl_plan *one : plans) std::fprintf(stderr, "vdlrun: batch: %s\n", vdl_plan_batch_note(one));
+    } else if (comm_dir.empty()) {
         if ((rc = vdl_run(ctx, plan))) return die(ctx, "vdl_run", rc);
     } else {
         unsigned char id[VDL_COMM_ID_BYTES];
@@ -260,12 +280,13 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
         if ((rc = vdl_run_sharded(ctx, plan))) return die(ctx, "vdl_run_sharded", rc);
     }
     collect(plan, reply);
+    for (size_t k = 1; k < plans.size() && more; k++) { more->emplace_back(); collect(plans[k], more->back()); }
     if (o.encode && rank == 0) {
         const char *list = "";
         vdl_plan_image_columns(plan, &list);
         std::fprintf(stderr, "vdlrun: images: %s\n", list);
     }
-    vdl_plan_free(plan);
+    for (vdl_plan *one : plans) vdl_plan_free(one);
     vdl_close(ctx);
     return 0;
 }
@@ -281,6 +302,7 @@ int main(int argc, char **argv) {
         else if (a == "--device" && i + 1 < argc) o.device = std::atoi(argv[++i]);
         else if (a == "--gpus" && i + 1 < argc) o.gpus = std::atoi(argv[++i]);
         else if (a == "--shard" && i + 1 < argc) o.shard = argv[++i];
+        else if (a == "--batch" && i + 1 < argc) o.batch_files.push_back(argv[++i]);
         else if (a == "--order-by" && i + 1 < argc && parse_order_by(argv[i + 1], o)) i++;
         else if (a == "--limit" && i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]) &&
                  std::strlen(argv[i + 1]) <= 18) o.limit = std::atoll(argv[++i]);
@@ -292,9 +314,13 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc],... ] [--limit N] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc],... ] [--limit N] [--batch FILE ...] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
+    }
+    if (!o.batch_files.empty() && !o.jit) {                    // (only specialised scans are batched: without --jit every program would run alone)
+        std::fprintf(stderr, "usage: vdlrun --batch FILE needs --jit or --jit-tune: a batch shares a scan specialised for its plans\n");
+        return 2;
     }
     if (o.gpus < 1 || o.gpus > 128) { std::fprintf(stderr, "vdlrun: --gpus must be 1 .. 128\n"); return 2; }
     std::string text((std::istreambuf_iterator<char>(std::cin)), std::istreambuf_iterator<char>());
@@ -305,10 +331,20 @@ int main(int argc, char **argv) {
                              "top-N results is not built; run the ordered query on one GPU\n");
         return 3;
     }
+    if (sharded && !o.describe && !o.batch_files.empty()) {
+        std::fprintf(stderr, "vdlrun: --batch is not served with --gpus: a sharded run takes one plan; run the batch on one GPU\n");
+        return 3;
+    }
+    for (const std::string &path : o.batch_files) {
+        std::ifstream f(path, std::ios::binary);
+        if (!f) { std::fprintf(stderr, "vdlrun: cannot read %s\n", path.c_str()); return 1; }
+        o.batch_texts.push_back(std::string((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>()));
+    }
     if (!sharded || o.describe) {
         Reply r;
-        const int rc = run_rank(o, text, 0, 1, "", r);
-        if (rc == 0 && !o.describe) print_reply(r);
+        std::vector<Reply> more;
+        const int rc = run_rank(o, text, 0, 1, "", r, &more);
+        if (rc == 0 && !o.describe) { print_reply(r); for (const Reply &m : more) print_reply(m); }
         return rc;
     }
     // one process per GPU, forked before anything in this process has touched HIP (no HIP call above this line)

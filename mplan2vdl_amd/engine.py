@@ -160,6 +160,11 @@ class Plan:
             timings[label.value.decode()] = int(round(us.value))
         return {"results": results, "timings": timings}
 
+    def batch_note(self):
+        """What the last Engine.run_batch / Engine.batch_jit_check did with this plan: "batch <b>: slot <q> of <K>, <kernel>" or
+        "alone: <reason>"; "" after a plain run() (vdl.h: vdl_plan_batch_note)."""
+        return (self._e._L.vdl_plan_batch_note(self._h) or b"").decode()
+
     def execute(self):
         """vdl_run only: the outputs stay in the plan (borrowed until the next run); `collect()` converts them."""
         self._e._check(self._e._L.vdl_run(self._e._c, self._h))
@@ -481,6 +486,24 @@ class Engine:
         plan = Plan(self, h, vdl_text)
         self._plans.add(plan)
         return plan
+
+    def _handles(self, plans):
+        plans = list(plans)
+        return plans, (ctypes.c_void_p * max(len(plans), 1))(*[p._h if p is not None else None for p in plans])
+
+    def run_batch(self, plans, as_numpy=False):
+        """Run the plans in one call (vdl.h: vdl_run_batch): those that differ in their literals alone share one pass over the
+        columns, the others run alone; the list of the dicts `Plan.run()` returns, in the plans' order.  `Plan.batch_note()` says
+        what became of each."""
+        plans, arr = self._handles(plans)
+        self._check(self._L.vdl_run_batch(self._c, arr, len(plans)))
+        return [p._collect(as_numpy) for p in plans]
+
+    def batch_jit_check(self, plans):
+        """Group the plans and build the batch kernels against the registered columns without a device (vdl_batch_jit_check); the notes."""
+        plans, arr = self._handles(plans)
+        self._check(self._L.vdl_batch_jit_check(self._c, arr, len(plans)))
+        return [p.batch_note() for p in plans]
 
     def run_vdl(self, vdl_text, fuse=True):
         plan = self.parse(vdl_text)
