@@ -118,6 +118,31 @@ int  vdl_declare_packed_image(vdl_ctx *ctx, const char *name, int bits, int64_t 
 /* on = 0: scans bind the catalog columns and ignore the images (tests, A/B comparisons in one process); default 1 */
 int  vdl_set_column_images(vdl_ctx *ctx, int on);
 
+/* ---- step images ------------------------------------------------------------------
+ * A column that never decreases and whose consecutive rows differ by 0 or 1 -- the join index of a table clustered by its
+ * parent, lineitem.lineitem_orders -- can be kept as its first value, one bit per row and one anchor per 64 rows.  With
+ * G = ceil(nrows / 64) groups:
+ *   heads[g]   uint64: bit i is 1 iff row r = 64 g + i has r >= 1 and v[r] != v[r - 1]
+ *   anchors[g] uint32: v[64 g - 1] - base for g >= 1, anchors[0] = 0                  (base = v[0])
+ *   v[r] = base + anchors[r >> 6] + popcount(heads[r >> 6] & (~0 >> (63 - (r & 63))))
+ * 12 bytes per 64 rows.  The scans that look things up through such a column -- fused fronts, dimension scans, semi-join
+ * scans -- read the step image in place of the column or its byte image and decode it as the tile comes in, always to the
+ * column's own values: results are the same.  Fused aggregate scans do not read it.
+ * Strictly opt-in: vdl_encode_steps builds the step image of a generated, uploaded or registered column (for a registered
+ * column the caller promises not to write it afterwards), 1 <= nrows < 2^32 at any element width.  A column that does not
+ * qualify gets none, and the call still returns VDL_OK.  The image goes with its column (drop, re-registration) and is
+ * ignored while vdl_set_column_images(ctx, 0).  VDL_STEP_IMAGES=1 in the environment makes vdl_encode_column try a step
+ * image as well. */
+int  vdl_encode_steps(vdl_ctx *ctx, const char *name);
+/* present 0: the column has no step image (base and groups are then 0); otherwise its base and G */
+int  vdl_column_steps_info(const vdl_ctx *ctx, const char *name, int *present, int64_t *base, int64_t *groups);
+/* the image's `groups` (= G) head words and anchors */
+int  vdl_download_steps_image(vdl_ctx *ctx, const char *name, uint64_t *heads, uint32_t *anchors, int64_t groups);
+/* contexts without a device (vdl_plan_jit_check): declare a registered column's step image (no bytes behind it) */
+int  vdl_declare_steps_image(vdl_ctx *ctx, const char *name, int64_t base);
+/* on = 0: scans leave the step images unbound and read what they read without them (A/B runs in one process); default 1 */
+int  vdl_set_step_images(vdl_ctx *ctx, int on);
+
 /* ---- plans --------------------------------------------------------------------- */
 
 /* Parse the VDL text, check it, and build the execution plan (operator fusion included).
@@ -172,6 +197,11 @@ int  vdl_plan_jit_check(vdl_ctx *ctx, vdl_plan *plan);
  * "front.select: lineitem.l_shipdate:2 lineitem.lineitem_orders:4; dim3: orders.o_orderdate:2".  "" when none does.
  * The text stays valid until the next call for this plan. */
 int  vdl_plan_image_columns(const vdl_plan *plan, const char **list);
+/* Likewise the columns read from their step images, "table.column:s" per scan role, e.g.
+ * "front.select: lineitem.lineitem_orders:s; front.take: lineitem.lineitem_orders:s".  A column listed here under a role is
+ * not listed under that role by vdl_plan_image_columns.  Kernels that read a step image carry ",stp" in the names
+ * vdl_plan_jit_note lists. */
+int  vdl_plan_step_columns(const vdl_plan *plan, const char **list);
 
 /* Execute: binds Loads to the catalog, runs all kernels, copies the MaterializeCompact
  * outputs to the host and synchronises. */

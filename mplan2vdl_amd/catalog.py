@@ -124,7 +124,8 @@ def _fk_graph(cfg):
 def synth_columns(meta_dir, cfg, vdl_text, scale=2e-4, seed=1, extra=(), clustered=()):
     """{column key path: numpy array} for every Load of `vdl_text` (and every path in `extra`).
     clustered: join-index columns (e.g. "lineitem.lineitem_orders") whose rows come in the dimension's order, as dbgen writes
-    lineitem clustered by order -- the same random draw, sorted: keys derived through it (l_orderkey) are then non-decreasing."""
+    lineitem clustered by order -- a random draw in which every dimension row occurs, sorted: the index never decreases and goes up
+    by at most 1 from row to row, and keys derived through it (l_orderkey) are non-decreasing."""
     codes = _per_column_codes(meta_dir)
     patterns = _like_patterns(vdl_text)
     info = {name: ci for name, ci in cfg.colinfo.to_list()}
@@ -176,7 +177,13 @@ def synth_columns(meta_dir, cfg, vdl_text, scale=2e-4, seed=1, extra=(), cluster
         else:
             v = _rng(seed, "%s.%s" % key).integers(0, rows[dim], n)
             if "%s.%s" % key in clustered:
-                v = np.sort(v)
+                # as dbgen writes it no parent is without children: the first rows[dim] draws are replaced by one of each parent (fewer
+                # rows than parents: the draw's gaps are closed instead), so the sorted index goes up by 0 or 1 from row to row
+                if n >= rows[dim]:
+                    v[:rows[dim]] = np.arange(rows[dim])
+                    v = np.sort(v)
+                else:
+                    v = np.unique(v, return_inverse=True)[1]
         memo[key] = np.asarray(v, dtype=np.int64)
         return memo[key]
 

@@ -157,5 +157,24 @@ inline void compose_packed(const Packed &pk, int64_t a, int64_t s, int64_t *a2, 
     compose(im, a, s, a2, s2);
 }
 
+// ---- step images ---------------------------------------------------------------------------------------------------------
+// A column that never decreases and whose consecutive rows differ by 0 or 1 -- the join index of a table clustered by its parent:
+// lineitem by order -- is fully described by its first value, one bit per row ("this row starts a new parent") and one anchor per
+// 64 rows.  With G = ceil(n / 64) groups:
+//   heads[g]  (uint64)  bit i is 1 iff row r = 64 g + i has r >= 1 and v[r] != v[r - 1]
+//   anchor[g] (uint32)  v[64 g - 1] - base for g >= 1, anchor[0] = 0              (base = v[0])
+//   v[r] = base + anchor[r >> 6] + popcount(heads[r >> 6] & (~0 >> (63 - (r & 63))))
+// 12 bytes per 64 rows.  Both arrays are padded to whole tiles of the projection scans (`tile` rows, a multiple of 64: a tile load
+// never runs off the end) with head words 0 and anchors v[n - 1] - base: rows past n decode to v[n - 1].  The anchors follow the
+// padded head words in one buffer.  1 <= n < 2^32, so that every anchor fits its 32 bits.  Read by the scans with derived columns
+// (fused fronts, dimension scans, semi-join scans), which decode it with the tile: always to the column's own values.
+constexpr int kStepGroup = 64;
+struct Steps {
+    bool present = false;
+    int64_t base = 0;
+};
+inline bool steps_rows_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 32); }
+inline int64_t step_groups(int64_t n) { return (n + kStepGroup - 1) / kStepGroup; }
+
 }  // namespace img
 }  // namespace vdl

@@ -146,6 +146,13 @@ std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols,
         if (((cols.image & which) >> k) & 1u) t += (t.empty() ? "" : " ") + sc[(size_t)k].name + ":" + std::to_string(cols.width[k]);
     return t;
 }
+// ... and from their step images, "name:s ...": its entry in vdl_plan_step_columns
+std::string step_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which) {
+    std::string t;
+    for (int k = 0; k < cols.ncol && (size_t)k < sc.size(); k++)
+        if (((cols.steps & which) >> k) & 1u) t += (t.empty() ? "" : " ") + sc[(size_t)k].name + ":s";
+    return t;
+}
 
 template <typename PlanT>
 // packed: 0 = byte images only; 1 = the filter columns from their bit-packed images (the packed form), 2 = every table column that has one
@@ -351,7 +358,8 @@ void patch_prelude(const vdl_plan *p, const std::vector<ScanColumn> &sc, MScanCo
 // decode.  One whose values the select pass needs per row (`per_row`: the sources of lookups and differences, plus what the caller
 // names -- the position of a semi-join) and that is not a pure narrowing is decoded with the tile (MsArgs::decode, one add) and
 // keeps the plan's filters; every other one has its filter and formula tests rewritten into the encoded domain.  (The take side of a
-// front decodes everything it loads: bind_front.)
+// front decodes everything it loads: bind_front.)  A step image (vdl_column_image.h Steps) goes before the byte image: it decodes to
+// the column's own values wherever it is loaded, so every use is legal and the plan's filters and formula tests stay.
 static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vector<ScanColumn> &sc, MScanCols &cols, MScanDesc &d, std::vector<char> &wanted,
                           uint32_t per_row = 0) {
     cols.ncol = (int)sc.size();
@@ -371,7 +379,13 @@ static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vecto
             if (n >= 0 && col.n != n) throw Error(VDL_ERR_SHAPE, "columns of table '" + table + "' have different lengths in the catalog");
             n = col.n;
             cols.ptr[k] = col.dev; cols.width[k] = col.width;
-            if (c->images && col.image_buf && img::usable_in_vscan(col.image, (per_row >> k) & 1u)) {
+            if (c->images && c->step_images && col.steps.present && (col.steps_buf || c->device < 0)) {
+                cols.steps |= 1u << k;
+                cols.ptr[k] = col.steps_buf ? col.steps_buf->p : nullptr;
+                d.ibase[k] = col.steps.base;
+                // (its values are base .. base + n - 1 at most: where they fit 32 signed bits the kernels make the sum in 32)
+                cols.width[k] = col.steps.base >= INT32_MIN && col.steps.base <= (int64_t)INT32_MAX - col.n ? 4 : 8;
+            } else if (c->images && col.image_buf && img::usable_in_vscan(col.image, (per_row >> k) & 1u)) {
                 ims[k] = col.image;
                 cols.image |= 1u << k;
                 cols.ptr[k] = col.image_buf->p; cols.width[k] = col.image.width;
@@ -410,14 +424,14 @@ static PassSource select_pass(const MScanCols &cols, const MScanDesc &d, bool rt
     jit::Shape sh;
     sh.nc = cols.ncol; sh.u = 4; sh.vec = project_select_vec(cols); sh.der = true; sh.rt_bounds = rt;
     return {jit::scan_source(jit::SELECT, mscan_args(cols), d, sh),
-            std::string(jit::entry_name(jit::SELECT)) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + (rt ? ",rtb" : "") + ">", jit::entry_name(jit::SELECT)};
+            std::string(jit::entry_name(jit::SELECT)) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + (cols.steps ? ",stp" : "") + (rt ? ",rtb" : "") + ">", jit::entry_name(jit::SELECT)};
 }
 // the one-pass front: two descriptors in one kernel (jit::front_source)
 static PassSource one_pass_front(const MScanCols &scols, const MScanDesc &sd, const MScanCols &tcols, const MScanDesc &td, bool rt) {
     jit::Shape sh;
     sh.nc = scols.ncol; sh.u = 4; sh.vec = project_select_vec(scols); sh.der = true; sh.rt_bounds = rt;
     return {jit::front_source(mscan_args(scols), sd, mscan_args(tcols), td, sh, tcols.ncol),
-            std::string(jit::entry_name(jit::FRONT)) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ((scols.image | tcols.image) ? ",img" : "") + (rt ? ",rtb" : "") + ">",
+            std::string(jit::entry_name(jit::FRONT)) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ((scols.image | tcols.image) ? ",img" : "") + ((scols.steps | tcols.steps) ? ",stp" : "") + (rt ? ",rtb" : "") + ">",
             jit::entry_name(jit::FRONT)};
 }
 // Compiles the pass and writes its line of the note: "role: entry<shape[,img]>, N B of code; ".  A run loads the kernel and falls back
@@ -516,6 +530,7 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         const uint32_t pos = semi && it.index_col >= 0 && it.index_col < 32 ? 1u << it.index_col : 0u;      // (the semi-join's positions)
         const int64_t n = bind_vcols(c, it.table, it.cols, cols, *d, unused, pos);
         p->image_roles[(semi ? "semi" : "dim") + std::to_string(k)] = image_text(it.cols, cols);
+        p->step_roles[(semi ? "semi" : "dim") + std::to_string(k)] = step_text(it.cols, cols);
         patch_prelude(p, it.cols, cols, *d);
         if (semi) {
             // the set of rows of another table that a selected row of this one points at: one scan, atomic ORs
@@ -797,7 +812,7 @@ static void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b) {
         scols.ptr[j] = cols.ptr[k]; scols.width[j] = cols.width[k]; scols.filtered[j] = cols.filtered[k];
         scols.lo[j] = cols.lo[k]; scols.hi[j] = cols.hi[k]; scols.kind[j] = cols.kind[k];
         sdesc->flo[j] = d.flo[k]; sdesc->fhi[j] = d.fhi[k]; sdesc->dkind[j] = d.dkind[k]; sdesc->dn[j] = d.dn[k]; sdesc->dtests[j] = d.dtests[k];
-        scols.image |= ((cols.image >> k) & 1u) << j; scols.decode |= ((cols.decode >> k) & 1u) << j;
+        scols.image |= ((cols.image >> k) & 1u) << j; scols.decode |= ((cols.decode >> k) & 1u) << j; scols.steps |= ((cols.steps >> k) & 1u) << j;
         sdesc->ibase[j] = d.ibase[k]; sdesc->iscale[j] = d.iscale[k];
         if (d.dkind[k] == VC_FORM) {                          // its steps stay where they are in the pool; the tests' columns are
             sdesc->dsrc[j] = d.dsrc[k]; sdesc->dsrc2[j] = d.dsrc2[k];      // renumbered (monotonic: they stay sorted by column)
@@ -856,6 +871,8 @@ static void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b) {
     for (int k = 0; k < cols.ncol; k++) if (renum[(size_t)k] >= 0) deciding |= 1u << k;
     p->image_roles["front.select"] = image_text(J.cols, cols, deciding);
     p->image_roles["front.take"] = image_text(J.cols, cols, d.take);
+    p->step_roles["front.select"] = step_text(J.cols, cols, deciding);
+    p->step_roles["front.take"] = step_text(J.cols, cols, d.take);
 }
 // the prelude's tables of this run, in both passes' arguments
 static void patch_front(const vdl_plan *p, FrontBound &b) {
@@ -1135,6 +1152,28 @@ static void build_image(vdl_ctx *c, Column &col) {
     col.packed_buf = pbuf;
 }
 
+// The column's step image (vdl_column_image.h Steps), in one pass; none when the column does not qualify -- some step is not 0 or 1,
+// or it has no rows or 2^32 and more.  Replaces whatever step image the column had.
+static void build_steps(vdl_ctx *c, Column &col) {
+    col.steps = img::Steps{};
+    col.steps_buf.reset();
+    if (!img::steps_rows_ok(col.n)) return;
+    const int64_t padded = project_step_groups(col.n);
+    BufP buf = dev_alloc(c, (size_t)padded * 12), out = dev_alloc(c, 2 * sizeof(int64_t));
+    HIP_CHECK(hipMemsetAsync(out->p, 0, 2 * sizeof(int64_t), c->stream));
+    HIP_CHECK(launch_image_steps(col.dev, col.width, col.n, padded, buf->p, (unsigned long long *)out->p, c->stream));
+    int64_t w2[2] = {};
+    c->fetch_to_host(out->p, 2, w2, c->stream);
+    if (w2[0] != 0) return;
+    col.steps.present = true;
+    col.steps.base = w2[1];
+    col.steps_buf = buf;
+}
+static bool step_images_by_default() {
+    const char *e = getenv("VDL_STEP_IMAGES");
+    return e && *e && *e != '0';
+}
+
 static void check_width(int w) {
     if (w != 1 && w != 2 && w != 4 && w != 8) throw Error(VDL_ERR_ARG, "elem_bytes must be 1, 2, 4 or 8");
 }
@@ -1192,7 +1231,65 @@ int vdl_encode_column(vdl_ctx *c, const char *name) {
         auto it = c->cols.find(name);
         if (it == c->cols.end()) throw Error(VDL_ERR_COLUMN, std::string("no column '") + name + "'");
         build_image(c, it->second);
+        if (step_images_by_default()) build_steps(c, it->second);      // (VDL_STEP_IMAGES=1: how unmodified callers reach the step images)
         c->catalog_version++;
+    });
+}
+
+int vdl_encode_steps(vdl_ctx *c, const char *name) {
+    if (!c || !name) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        need_device(c);
+        auto it = c->cols.find(name);
+        if (it == c->cols.end()) throw Error(VDL_ERR_COLUMN, std::string("no column '") + name + "'");
+        build_steps(c, it->second);
+        c->catalog_version++;
+    });
+}
+
+int vdl_column_steps_info(const vdl_ctx *c, const char *name, int *present, int64_t *base, int64_t *groups) {
+    if (!c || !name) return VDL_ERR_ARG;
+    auto it = c->cols.find(name);
+    if (it == c->cols.end()) return VDL_ERR_COLUMN;
+    const img::Steps &st = it->second.steps;
+    if (present) *present = st.present ? 1 : 0;
+    if (base) *base = st.present ? st.base : 0;
+    if (groups) *groups = st.present ? img::step_groups(it->second.n) : 0;
+    return VDL_OK;
+}
+
+int vdl_download_steps_image(vdl_ctx *c, const char *name, uint64_t *heads, uint32_t *anchors, int64_t groups) {
+    if (!c || !name || !heads || !anchors) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        need_device(c);
+        const Column &col = find_col(c, name);
+        if (!col.steps.present || !col.steps_buf) throw Error(VDL_ERR_ARG, std::string("column '") + name + "' has no step image");
+        if (groups != img::step_groups(col.n)) throw Error(VDL_ERR_ARG, "the number of groups does not match the step image");
+        const char *image = (const char *)col.steps_buf->p;
+        HIP_CHECK(hipMemcpyAsync(heads, image, (size_t)groups * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipMemcpyAsync(anchors, image + (size_t)project_step_groups(col.n) * 8, (size_t)groups * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int vdl_declare_steps_image(vdl_ctx *c, const char *name, int64_t base) {
+    if (!c || !name) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        if (c->device >= 0) throw Error(VDL_ERR_ARG, "step images are declared only on a context without a device (a device builds them)");
+        auto it = c->cols.find(name);
+        if (it == c->cols.end()) throw Error(VDL_ERR_COLUMN, std::string("no column '") + name + "'");
+        if (!img::steps_rows_ok(it->second.n)) throw Error(VDL_ERR_ARG, "a step image needs 1 <= rows < 2^32");
+        it->second.steps.present = true; it->second.steps.base = base;
+        it->second.steps_buf.reset();
+        c->catalog_version++;
+    });
+}
+
+int vdl_set_step_images(vdl_ctx *c, int on) {
+    if (!c) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        if (c->step_images != (on != 0)) c->catalog_version++;      // bound plans re-bind
+        c->step_images = on != 0;
     });
 }
 
@@ -1341,6 +1438,14 @@ int vdl_plan_image_columns(const vdl_plan *p, const char **list) {
     *list = p->image_list.c_str();
     return VDL_OK;
 }
+int vdl_plan_step_columns(const vdl_plan *p, const char **list) {
+    if (!p || !list) return VDL_ERR_ARG;
+    p->step_list.clear();
+    for (const auto &r : p->step_roles)
+        if (!r.second.empty()) p->step_list += (p->step_list.empty() ? "" : "; ") + r.first + ": " + r.second;
+    *list = p->step_list.c_str();
+    return VDL_OK;
+}
 // Builds (hiprtc; no GPU needed) the specialised kernel of every multi-aggregate scan of the plan against the columns
 // registered now, without loading or running anything: the note lists each kernel with its code size, or why it failed.
 int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
@@ -1362,6 +1467,7 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
                 bind_vcols(c, it.table, it.cols, cols, *d, unused, pos);
                 const std::string role = (semi ? "semi" : "dim") + std::to_string(k);
                 p->image_roles[role] = image_text(it.cols, cols);
+                p->step_roles[role] = step_text(it.cols, cols);
                 d->bitmap_only = semi ? 2 : 1;
                 if (semi) { d->pmin = it.modulus; d->nout = 1; d->out_col[0] = it.index_col; }
                 build_pass(c, p, role, select_pass(cols, *d, p->jit_rt_bounds), true);

@@ -98,6 +98,11 @@ struct Column {
     // scan.  Goes with the column like the byte image.  (packed_buf null with bits > 0: declared on a context without a device)
     img::Packed packed;
     BufP packed_buf;
+    // the step image (img::Steps) of a column that never decreases and steps by at most 1: built only when asked for
+    // (vdl_encode_steps), read by the scans with derived columns.  Goes with the column like the other images.  (steps_buf null with
+    // steps.present: declared on a context without a device)
+    img::Steps steps;
+    BufP steps_buf;
 };
 
 // device-side vector of the general path
@@ -192,6 +197,7 @@ struct vdl_ctx {
     std::map<std::string, Column> cols;
     uint64_t catalog_version = 1;      // bumped on every catalog change: plans re-bind only when it moved
     bool images = true;                // aggregate scans read the columns' images where the rules allow (vdl_set_column_images)
+    bool step_images = true;           // ... and fronts, dimension and semi-join scans the step images (vdl_set_step_images)
     const std::map<std::string, Column> *overlay = nullptr;     // columns that stand in for catalog entries during one run (vdl_comm.cpp: sharded_replicate)
     uint64_t overlay_epoch = 0;                                  // moves whenever the overlay is set or cleared
     // what bindings and kernels specialised for column addresses / widths / lengths are keyed by: the catalog's state AND the overlay's
@@ -296,6 +302,9 @@ struct vdl_plan {
     // images, "name:width ..." (vdl_plan_image_columns); roles without one hold ""
     std::map<std::string, std::string> image_roles;
     mutable std::string image_list;          // what vdl_plan_image_columns handed out last
+    // likewise the columns read from their step images, "name:s ..." (vdl_plan_step_columns): such a column is not in image_roles
+    std::map<std::string, std::string> step_roles;
+    mutable std::string step_list;
     std::vector<BufP> prelude_buf;           // fused join scans: dimension bitmaps / LIKE tables of the current run (FusedPlan::prelude)
     std::vector<int64_t> prelude_n;
     std::vector<int64_t> prelude_rows;       // SEMI_BITMAP items: rows of the (local) source table the set was built from
@@ -463,6 +472,7 @@ template <typename PlanT>
 int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0, int packed = 0);
 bool use_kscan(const ScanPlan &sp);
 std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
+std::string step_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
 // sharded entry points refuse a plan with an order set
 inline void refuse_order_sharded(const vdl_plan *p) {
     if (p->order.set)

@@ -1,6 +1,7 @@
 // vdl_image.hip -- the two passes that build a column's frame-of-reference image (the rules: vdl_column_image.h): one reduction
 // of min, max and the decimal trailing zeros every value shares with the first, then one pass that writes e = (v - base) / scale
-// in the image's width.  Both run when a column is created (ingest), never inside a query.
+// in the image's width.  Both run when a column is created (ingest), never inside a query.  Also the pass that packs a byte image
+// to its bit length, and the one pass that builds a step image (k_image_steps).
 #include "vdl_device.h"
 
 namespace vdl {
@@ -89,7 +90,55 @@ __global__ __launch_bounds__(256) void k_image_pack(const T *img, int64_t n, int
     }
 }
 
+// The step image (vdl_column_image.h, Steps) in one pass: a wave takes 64 rows, a lane its row and the row before it (its
+// neighbour's by a shuffle; lane 0 loads the last row of the group before), and the ballot of "differs from the row before" is the
+// group's head word.  The anchor is what lane 0 holds of the row before, less the base.  A step other than 0 or 1 raises out[0];
+// out[1] = v[0], the base.  Groups at and past `groups` are the padding: no head bits, the anchor of the last row.  Rows of the last
+// group past n read row n - 1 and set no bit.  (heads: `padded` words, the anchors behind them; out[0] zeroed by the caller)
+__global__ __launch_bounds__(256) void k_image_steps(const void *col, int w, int64_t n, int64_t groups, int64_t padded, uint64_t *heads, uint32_t *anchor,
+                                                     unsigned long long *out) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x / 64);
+    const int64_t base = load_w(col, w, 0);
+    if (blockIdx.x == 0 && threadIdx.x == 0) out[1] = (unsigned long long)base;
+    bool raised = false;                                    // (a wave raises the flag once: a column like l_orderkey, where every group holds
+                                                            // a wrong step, had every wave of every group queue at that one word -- 106 ms at SF100)
+    for (int64_t g = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64; g < padded; g += waves) {
+        uint64_t head = 0;
+        int64_t before = 0;                                 // lane 0: the row before the group's first
+        if (g < groups) {
+            const int64_t r = g * 64 + lane;
+            const bool in = r < n;
+            const int64_t v = load_w(col, w, in ? r : n - 1);
+            int64_t prev = __shfl_up(v, 1, 64);
+            if (lane == 0) prev = g > 0 ? load_w(col, w, r - 1) : v;
+            before = prev;
+            const bool same = v == prev, step = v > prev && (uint64_t)v - (uint64_t)prev == 1ull;
+            head = __ballot(in && !same);
+            if (!raised && __ballot(in && !same && !step) != 0ull) {
+                if (lane == 0) atomicOr(&out[0], 1ull);
+                raised = true;
+            }
+        } else if (lane == 0) {
+            before = load_w(col, w, n - 1);
+        }
+        if (lane == 0) {
+            heads[g] = head;
+            anchor[g] = g > 0 ? (uint32_t)((uint64_t)before - (uint64_t)base) : 0u;
+        }
+    }
+}
+
 }  // namespace
+
+hipError_t launch_image_steps(const void *col, int elem_bytes, int64_t n, int64_t padded_groups, void *image, unsigned long long *out2, hipStream_t s) {
+    (void)hipGetLastError();
+    const int64_t groups = (n + 63) / 64;
+    if (n <= 0 || padded_groups < groups) return hipErrorInvalidValue;
+    const int grid = (int)std::min<int64_t>((padded_groups + 3) / 4, 256 * 16);
+    k_image_steps<<<grid, 256, 0, s>>>(col, elem_bytes, n, groups, padded_groups, (uint64_t *)image, (uint32_t *)((uint64_t *)image + padded_groups), out2);
+    return launch_status();
+}
 
 hipError_t launch_image_pack(const void *img, int img_bytes, int64_t n, int64_t emin, int bits, void *out, hipStream_t s) {
     (void)hipGetLastError();

@@ -253,6 +253,7 @@ static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, con
     o << "    a.ncol = " << C.ncol << "; a.widths = " << C.widths << "ull; a.filtered = " << C.filtered << "u; a.derived = " << C.derived
       << "u; a.lazy = " << C.lazy << "u; a.stages = " << C.stages << "ull; a.queued = " << C.queued << "; a.decode = " << C.decode << "u;\n";
     if (C.packed) o << "    a.packed = " << C.packed << "u; a.pbits = " << C.pbits << "ull;\n";
+    if (C.steps) o << "    a.steps = " << C.steps << "u;\n";
     o << "    return a;\n}\n";
     o << "constexpr MScanDesc jit_desc" << suffix << "() {\n    MScanDesc d{};\n";
     o << "    d.nagg = " << D.nagg << "; d.nkey = " << D.nkey << "; d.replicas = " << D.replicas << "; d.pmin = " << lit(D.pmin) << "; d.pcount = " << lit(D.pcount) << ";\n";
@@ -260,6 +261,7 @@ static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, con
     for (int k = 0; k < C.ncol; k++) {
         if ((C.filtered >> k) & 1u) o << "    d.flo[" << k << "] = " << lit(lo_of(k, D.flo[k], D.fhi[k])) << "; d.fhi[" << k << "] = " << lit(hi_of(k, D.flo[k], D.fhi[k])) << ";\n";
         if ((C.decode >> k) & 1u) o << "    d.ibase[" << k << "] = " << lit(D.ibase[k]) << "; d.iscale[" << k << "] = " << lit(D.iscale[k]) << ";\n";
+        if ((C.steps >> k) & 1u) o << "    d.ibase[" << k << "] = " << lit(D.ibase[k]) << ";\n";      // (a step image's base)
         if ((C.derived >> k) & 1u) {
             o << "    d.dkind[" << k << "] = " << D.dkind[k] << "; d.dsrc[" << k << "] = " << D.dsrc[k] << "; d.dsrc2[" << k << "] = " << D.dsrc2[k]
               << "; d.dtests[" << k << "] = " << D.dtests[k] << ";\n";

@@ -68,6 +68,8 @@ size_t mscan_lds_bytes(const MScanDesc &d, bool grouped);
 // Projection scans (ProjPlan, vdl_fuse.h).  launch_project_select: a selection over a table's rows as a bitmap (d.bitmap_only = 1:
 // a dimension scan, out_ptr[0] = the bitmap) or as bits set in a semi-join set (d.bitmap_only = 2).
 int64_t project_tiles(int64_t n);
+// groups (64 rows) of a step image of n rows, padded to whole tiles of the projection scans (vdl_column_image.h Steps)
+int64_t project_step_groups(int64_t n);
 hipError_t launch_project_select(const MScanCols &cols, const MScanDesc *dev_desc, int num_cus, hipStream_t s, hipFunction_t jit_fn = nullptr);
 bool project_select_vec(const MScanCols &cols);          // the 16-byte-load form applies (alignment of the deciding columns)
 // the fused front in ONE pass (vdl_mscan_body.h: project_front_body): scols / dev_sdesc = the deciding columns as the select pass saw
@@ -88,6 +90,9 @@ hipError_t launch_image_stats(const void *col, int elem_bytes, int64_t n, unsign
 hipError_t launch_image_encode(const void *col, int elem_bytes, int64_t n, int64_t base, int64_t scale, void *img, int img_bytes, hipStream_t s);
 // the bit-packed image (vdl_column_image.h Packed) of a byte image: img::packed_dwords(n, bits) dwords at `out`
 hipError_t launch_image_pack(const void *img, int img_bytes, int64_t n, int64_t emin, int bits, void *out, hipStream_t s);
+// the step image (vdl_column_image.h Steps): `padded_groups` head words (project_step_groups(n)) and as many anchors behind them at
+// `image`; out2[0] (zeroed by the caller) is raised when some step is not 0 or 1, out2[1] = v[0]
+hipError_t launch_image_steps(const void *col, int elem_bytes, int64_t n, int64_t padded_groups, void *image, unsigned long long *out2, hipStream_t s);
 
 // ---- per-operator kernels -----------------------------------------------------------------
 // validity bitmaps: bit (i & 63) of word (i >> 6); nullptr = every slot holds a value.

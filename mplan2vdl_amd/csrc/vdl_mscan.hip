@@ -32,6 +32,7 @@ static MsArgs ms_args(const MScanCols &cols) {
     MsArgs a;
     a.ncol = cols.ncol; a.n = cols.n; a.row0 = cols.row0; a.rowid_base = cols.rowid_global ? 0 : cols.row0;
     a.decode = cols.decode;
+    a.steps = cols.steps;
     a.packed = cols.packed;
     for (int c = 0; c < cols.ncol; c++) {
         if ((cols.packed >> c) & 1u) a.pbits |= (uint64_t)cols.pbits[c] << (6 * c);
@@ -247,6 +248,7 @@ hipError_t launch_mscan_batch(const MScanCols &cols, const MScanDesc &d, const M
 }
 
 int64_t project_tiles(int64_t n) { return (n + kProjTile - 1) / kProjTile; }
+int64_t project_step_groups(int64_t n) { return step_groups_padded(n); }
 
 bool project_select_vec(const MScanCols &cols) {
     bool vec = true;

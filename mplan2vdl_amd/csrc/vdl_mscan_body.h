@@ -22,6 +22,11 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kMsBlock = 256;
+#ifndef VDL_PROJ_U
+#define VDL_PROJ_U 4                          // row pairs per lane and tile of the projection scan (variant builds: -DVDL_PROJ_U=2|8)
+#endif
+constexpr int kProjU = VDL_PROJ_U;
+constexpr int kProjTile = kMsBlock * 2 * kProjU;
 enum { R_SUM = 0, R_MIN = 1, R_MAX = 2 };
 
 __device__ __forceinline__ int rk_of(int kind) { return kind == AGG_SUM ? R_SUM : kind == AGG_MAX ? R_MAX : R_MIN; }
@@ -94,6 +99,43 @@ __device__ __forceinline__ uint32_t unpack_bits(const uint32_t (&w)[32], int j, 
 __device__ __forceinline__ int64_t img_decode(int64_t e, int64_t base, int64_t scale) {
     return (int64_t)((uint64_t)base + (uint64_t)scale * (uint64_t)e);
 }
+// Step images (vdl_column_image.h Steps): `p` = the head words, one per 64 rows, padded to whole tiles of the projection scans, the
+// 32-bit anchors behind them.  Row r is base + anchor[r >> 6] + the head bits of its group up to and including its own.
+__host__ __device__ inline int64_t step_groups_padded(int64_t n) { return (n + kProjTile - 1) / kProjTile * (kProjTile / 64); }
+__device__ __forceinline__ const uint32_t *step_anchors(const void *p, int64_t n) { return (const uint32_t *)((const uint64_t *)p + step_groups_padded(n)); }
+// `w` is the width the binder gives the column: 4 when every value of the image fits 32 signed bits (base .. base + n - 1 does) -- the
+// sum is then made in 32 bits and the compiler knows the upper half, as it does of a 4-byte load -- else 8.
+__device__ __forceinline__ int64_t step_sum(int64_t base, uint32_t anchor, uint64_t masked, int w) {
+    if (w <= 4) return (int64_t)(int32_t)((uint32_t)base + anchor + (uint32_t)__popcll(masked));
+    return (int64_t)((uint64_t)base + (uint64_t)anchor + (uint64_t)__popcll(masked));
+}
+// one row anywhere (a survivor of the take side): two loads
+__device__ __forceinline__ int64_t step_load(const void *p, int64_t n, int64_t base, int w, int64_t r) {
+    return step_sum(base, step_anchors(p, n)[r >> 6], ((const uint64_t *)p)[r >> 6] & (~0ull >> (63 - (int)(r & 63))), w);
+}
+// A lane's rows of a tile, (base + u * 2 * kMsBlock, + 1) for u < U with base even: a pair lies in one group -- its head word and its
+// anchor, the same address for the 32 lanes of half a wave (24 bytes per wave and row slice where a 4-byte column asks for 512) --
+// and a population count per row gives both values.  The sub-iterations start a whole number of groups apart: one address each
+// for the words and the anchors, the rest immediate offsets, and one pair of masks for all of them.  Every load goes out before
+// the first count.  The partial last tile takes this path too: the image is padded to whole tiles, rows past n decode to row n - 1.
+template <int U>
+__device__ __forceinline__ void step_tile(const void *p, int64_t n, int64_t base, int64_t sb, int w, int64_t (&v)[2 * U]) {
+    static_assert((kMsBlock * 2) % 64 == 0, "a tile's sub-iterations start whole groups apart");
+    constexpr int GU = kMsBlock * 2 / 64;
+    const uint64_t *hp = (const uint64_t *)p + (base >> 6);
+    const uint32_t *ap = step_anchors(p, n) + (base >> 6);
+    uint64_t h[U];
+    uint32_t a[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) { h[u] = hp[u * GU]; a[u] = ap[u * GU]; }
+    const int i = (int)(base & 63);
+    const uint64_t m0 = ~0ull >> (63 - i), m1 = ~0ull >> (62 - i);
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        v[2 * u] = step_sum(sb, a[u], h[u] & m0, w);
+        v[2 * u + 1] = step_sum(sb, a[u], h[u] & m1, w);
+    }
+}
 template <bool NT, typename V>
 __device__ __forceinline__ V stream_load(const char *p) {
     if (NT) return __builtin_nontemporal_load((const V *)p);
@@ -165,15 +207,18 @@ __device__ __forceinline__ void key_combine(int op, int swap, int64_t (&acc)[RW]
 }
 
 
+// (sbase: the bases of the columns of C.steps, MScanDesc::ibase -- the projection scans pass it; aggregate scans bind no step image)
 template <int NC, int U, bool VEC, bool NT>
-__device__ __forceinline__ void load_tile(const MsArgs &C, const MsArgs &Cr, int64_t base, int64_t (&v)[NC][2 * U], uint32_t skip = 0) {
+__device__ __forceinline__ void load_tile(const MsArgs &C, const MsArgs &Cr, int64_t base, int64_t (&v)[NC][2 * U], uint32_t skip = 0, const int64_t *sbase = nullptr) {
     constexpr int BS = kMsBlock;
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         if (c < C.ncol && !(((C.derived | skip) >> c) & 1u)) {      // wave-uniform
             const char *p = (const char *)Cr.ptr[c];
             const int w = C.width(c);
-            if (!VEC) {
+            if (sbase && ((C.steps >> c) & 1u)) {                   // wave-uniform
+                step_tile<U>(p, Cr.n, base, sbase[c], w, v[c]);
+            } else if (!VEC) {
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     v[c][2 * u] = load_scalar(p, w, base + (int64_t)u * (BS * 2));
@@ -1013,11 +1058,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
 // then the survivors' columns as packed vectors -- is project_front_body below.  (Until round 4 the front was this pass leaving
 // counts and 16-bit positions per tile, a prefix sum, and a take pass with one wave per tile.)
 // Row order inside a tile is (sub-iteration u, wave, lane, row of the lane's pair).
-#ifndef VDL_PROJ_U
-#define VDL_PROJ_U 4                          // row pairs per lane and tile of the projection scan (variant builds: -DVDL_PROJ_U=2|8)
-#endif
-constexpr int kProjU = VDL_PROJ_U;
-constexpr int kProjTile = kMsBlock * 2 * kProjU;
+// (kProjU, kProjTile: the tile of these scans, defined at the top -- the step images are padded to it)
 static_assert(kProjTile <= 65536, "positions inside a tile fit 16 bits");
 
 template <int NC, int U, bool VEC, bool NT>
@@ -1029,11 +1070,12 @@ __device__ __forceinline__ void project_select_body(const MsArgs &C, const MsArg
         int64_t v[NC][ROWS];
         const int64_t base = tile * TILE + (int64_t)tid * 2;
         if (tile < full) {
-            load_tile<NC, U, VEC, NT>(C, Cr, base, v, C.lazy);
+            load_tile<NC, U, VEC, NT>(C, Cr, base, v, C.lazy, D.ibase);
         } else {                                           // the partial last tile: clamped scalar loads
 #pragma unroll
             for (int c = 0; c < NC; c++) {
                 if (c < C.ncol && !(((C.derived | C.lazy) >> c) & 1u)) {
+                    if ((C.steps >> c) & 1u) { step_tile<U>(Cr.ptr[c], Cr.n, base, D.ibase[c], C.width(c), v[c]); continue; }      // (padded to whole tiles)
 #pragma unroll
                     for (int r = 0; r < ROWS; r++) {
                         const int64_t i = base + (int64_t)(r >> 1) * (BS * 2) + (r & 1);
@@ -1158,11 +1200,12 @@ __device__ __forceinline__ void project_front_body(const MsArgs &Cs, const MsArg
             int64_t v[NCS][ROWS];
             const int64_t base = tile * TILE + (int64_t)tid * 2;
             if (tile < full) {
-                load_tile<NCS, U, VEC, NT>(Cs, Csr, base, v, Cs.lazy);
+                load_tile<NCS, U, VEC, NT>(Cs, Csr, base, v, Cs.lazy, Ds.ibase);
             } else {                                       // the partial last tile: clamped scalar loads
 #pragma unroll
                 for (int c = 0; c < NCS; c++) {
                     if (c < Cs.ncol && !(((Cs.derived | Cs.lazy) >> c) & 1u)) {
+                        if ((Cs.steps >> c) & 1u) { step_tile<U>(Csr.ptr[c], Csr.n, base, Ds.ibase[c], Cs.width(c), v[c]); continue; }      // (padded to whole tiles)
 #pragma unroll
                         for (int r = 0; r < ROWS; r++) {
                             const int64_t i = base + (int64_t)(r >> 1) * (BS * 2) + (r & 1);
@@ -1276,6 +1319,7 @@ __device__ __forceinline__ void project_front_body(const MsArgs &Cs, const MsArg
                     vt[c][0] = 0;
                     if (c < Ct.ncol && ((Dt.take >> c) & 1u) && !((Ct.derived >> c) & 1u)) {
                         if (((Dt.carry >> c) & 1u) && k < kFrontCarry) vt[c][0] = cst[__builtin_popcount(Dt.carry & ((1u << c) - 1u))][k];
+                        else if ((Ct.steps >> c) & 1u) vt[c][0] = step_load(Ctr.ptr[c], Ctr.n, Dt.ibase[c], Ct.width(c), row);      // a step image at a random row: two loads
                         else {
                             vt[c][0] = load_scalar(Ctr.ptr[c], Ct.width(c), row);
                             if ((Ct.decode >> c) & 1u) vt[c][0] = img_decode(vt[c][0], Dt.ibase[c], Dt.iscale[c]);

@@ -104,6 +104,7 @@ struct MScanCols {                           // host-side description of a scan'
     uint32_t decode = 0;                     // bit c: ... and decoded by the kernel (MsArgs::decode)
     uint32_t packed = 0;                     // bit c: read from its bit-packed image (MsArgs::packed), pbits[c] bits per row
     int pbits[kMaxVCols] = {};
+    uint32_t steps = 0;                      // bit c: read from its step image (MsArgs::steps); width[c] = 4 when all its values fit 32 signed bits, else 8
 };
 struct MAggDesc {
     int kind = 0;                            // AGG_SUM / AGG_MIN / AGG_MAX / AGG_FIRST
@@ -124,7 +125,7 @@ struct MScanDesc {                           // lives in device memory, read wit
     FormStep form[kMaxFormPool];
     int64_t dn[kMaxVCols] = {};              // derived columns: entries of the table looked up
     // projection scans (fronts, dimension and semi-join scans): column c read from its image is ibase[c] + iscale[c] * e (wrapping); read
-    // only for the columns of MsArgs::decode
+    // only for the columns of MsArgs::decode; for a column of MsArgs::steps ibase[c] is its step image's base
     int64_t ibase[kMaxVCols] = {}, iscale[kMaxVCols] = {};
     // projection scan (k_project): what to write for the surviving rows
     int nout = 0, out_col[kMaxProjOuts] = {};     // out_col[o] >= 0: that column; -2 - e: the row expression e (below)
@@ -172,6 +173,11 @@ struct MsBatch {
 // bounds now sit in the device descriptor and are read where a column is actually filtered.)
 struct MsArgs {
     int ncol = 0;
+    // projection scans, bit c: read from its step image (vdl_column_image.h Steps): ptr[c] = the head words, the anchors behind them,
+    // MScanDesc::ibase[c] the image's base, width(c) = 4 when base .. base + n - 1 fits 32 signed bits, else 8.  Decoded where it is
+    // loaded, on either side, always to the column's own values: filters and formula tests stay as planned, and `decode` does not
+    // name it.  (It sits in what was padding ahead of `widths`: every other argument stays where the kernels read it.)
+    uint32_t steps = 0;
     uint64_t widths = 0;                     // 4 bits per column: bytes
     uint32_t filtered = 0;                   // bit c: column c has a range filter (MScanDesc::flo / fhi)
     uint32_t derived = 0;                    // bit c: column c is derived from earlier columns (MScanDesc::dkind ...), ptr[c] = its table

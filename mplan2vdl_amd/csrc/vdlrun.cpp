@@ -16,6 +16,11 @@
 // --encode builds the frame-of-reference image of every column it uploads or generates (vdl_encode_column; each rank of its own
 // rows), so that the scans read the narrow copies; after the run one line "vdlrun: images: <vdl_plan_image_columns>" goes to
 // stderr (rank 0's).  The reply on stdout is the same as without it.
+//   ... | vdlrun --encode-steps ...                                             join indices read through their step images
+// --encode-steps tries a step image (vdl_encode_steps) on every column it uploads or generates: a column that never decreases and
+// steps by at most 1 -- a clustered join index -- gets one, and fronts, dimension and semi-join scans read it.  After the run one
+// line "vdlrun: step images: <vdl_plan_step_columns>" goes to stderr beside the images line; it is also printed when --encode runs
+// under VDL_STEP_IMAGES=1, which makes vdl_encode_column try a step image too.
 //   ... | vdlrun --order-by revenue:desc,o_orderdate__orders__o_orderdate --limit 10 ...      ORDER BY / LIMIT on the device
 // --order-by FIELD[:asc|:desc],... names outputs by their full field name or their tmpN key, --limit N keeps the first N rows
 // (vdl_plan_set_order): the reply has the same shape with shorter, ordered lists, so resolve.py decodes it untouched.  Not with
@@ -56,7 +61,7 @@ const GenSpec kLineitem[] = {
 struct ColFile { int width; int64_t rows; };
 
 int load_data_dir(vdl_ctx *ctx, const std::string &dir, const std::string &program, const std::string &shard_table = "", int rank = 0, int world = 1,
-                  int64_t *row0_out = nullptr, bool encode = false) {
+                  int64_t *row0_out = nullptr, bool encode = false, bool encode_steps = false) {
     std::map<std::string, ColFile> listed;
     std::ifstream manifest(dir + "/columns.csv");
     if (!manifest) { std::fprintf(stderr, "vdlrun: cannot read %s/columns.csv\n", dir.c_str()); return 1; }
@@ -96,6 +101,10 @@ int load_data_dir(vdl_ctx *ctx, const std::string &dir, const std::string &progr
         if (rc) { std::fprintf(stderr, "vdlrun: vdl_upload_column(%s) failed (%d): %s\n", name.c_str(), rc, vdl_last_error(ctx)); return 1; }
         if (encode && (rc = vdl_encode_column(ctx, name.c_str()))) {
             std::fprintf(stderr, "vdlrun: vdl_encode_column(%s) failed (%d): %s\n", name.c_str(), rc, vdl_last_error(ctx));
+            return 1;
+        }
+        if (encode_steps && (rc = vdl_encode_steps(ctx, name.c_str()))) {
+            std::fprintf(stderr, "vdlrun: vdl_encode_steps(%s) failed (%d): %s\n", name.c_str(), rc, vdl_last_error(ctx));
             return 1;
         }
         listed.erase(it);                                  // a column loaded twice by the program is uploaded once
@@ -177,7 +186,7 @@ bool read_reply(const std::string &path, Reply &r) {
 struct Options {
     int64_t rows = 60175;           // SF0.01 lineitem, /root/reference/tests/tpchnoorder/bounds.csv:59
     uint64_t seed = 0x5EED0006ULL;
-    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0;
+    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0;
     std::string data_dir, shard = "lineitem";
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
@@ -238,7 +247,7 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
     if (o.describe) { std::fputs(vdl_plan_describe(plan), stdout); return 0; }
     int64_t row0 = 0;
     if (!o.data_dir.empty()) {
-        if (load_data_dir(ctx, o.data_dir, loads, o.shard, rank, world, &row0, o.encode != 0)) return 1;
+        if (load_data_dir(ctx, o.data_dir, loads, o.shard, rank, world, &row0, o.encode != 0, o.encode_steps != 0)) return 1;
     } else {
         row0 = o.rows * rank / world;
         const int64_t mine = o.rows * (rank + 1) / world - row0;
@@ -246,6 +255,8 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
             if ((rc = vdl_generate_column(ctx, g.name, g.width, row0, mine, o.seed, g.lo, g.hi, g.mul, g.add))) return die(ctx, "vdl_generate_column", rc);
         if (o.encode)
             for (const GenSpec &g : kLineitem) if ((rc = vdl_encode_column(ctx, g.name))) return die(ctx, "vdl_encode_column", rc);
+        if (o.encode_steps)
+            for (const GenSpec &g : kLineitem) if ((rc = vdl_encode_steps(ctx, g.name))) return die(ctx, "vdl_encode_steps", rc);
     }
     if (comm_dir.empty() && plans.size() > 1) {
         if ((rc = vdl_run_batch(ctx, plans.data(), (int)plans.size()))) return die(ctx, "vdl_run_batch", rc);
@@ -286,6 +297,12 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
         vdl_plan_image_columns(plan, &list);
         std::fprintf(stderr, "vdlrun: images: %s\n", list);
     }
+    const char *by_env = std::getenv("VDL_STEP_IMAGES");
+    if ((o.encode_steps || (o.encode && by_env && *by_env && *by_env != '0')) && rank == 0) {
+        const char *list = "";
+        vdl_plan_step_columns(plan, &list);
+        std::fprintf(stderr, "vdlrun: step images: %s\n", list);
+    }
     for (vdl_plan *one : plans) vdl_plan_free(one);
     vdl_close(ctx);
     return 0;
@@ -309,12 +326,13 @@ int main(int argc, char **argv) {
         else if (a == "--no-fuse") o.fuse = 0;
         else if (a == "--jit") o.jit = 1;
         else if (a == "--encode") o.encode = 1;
+        else if (a == "--encode-steps") o.encode_steps = 1;
         else if (a == "--jit-tune") o.jit = 2;
         else if (a == "--jit-share") o.jit_share = 1;      // filter bounds at run time: queries that differ in literals alone share the specialised code
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc],... ] [--limit N] [--batch FILE ...] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc],... ] [--limit N] [--batch FILE ...] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }

@@ -114,13 +114,14 @@ def q3_tables(n_orders, seed=SEED):
     return t
 
 
-def register_q3_columns(engine, n_orders, li_rows=None, device="cuda", seed=SEED, copartition=False):
+def register_q3_columns(engine, n_orders, li_rows=None, device="cuda", seed=SEED, copartition=False, steps=False):
     """The Q3 catalog of `q3_tables` built in place on the GPU (counter-based generator + arithmetic join indices):
     customer / orders in full, lineitem rows [li_rows[0], li_rows[1]) (default: all 4 * n_orders).
     copartition=True keeps only the orders rows the lineitem shard references (lineitem is clustered by order, so
     that is one contiguous range) and rebases the join index to it: the co-located placement of a sharded star
     schema, under which no rank repeats the orders-side work of another.
     The registered join index and l_orderkey are encoded (Engine.encode) like the generated columns.
+    steps=True also builds the join index's step image (Engine.encode_steps): it is row // 4, rebased or not.
     Returns the tensors that back the registered columns (keep them alive while the engine uses them)."""
     import torch
 
@@ -150,6 +151,8 @@ def register_q3_columns(engine, n_orders, li_rows=None, device="cuda", seed=SEED
     # front reads the join index narrow; the tensors are not written again
     engine.encode("lineitem.lineitem_orders")
     engine.encode("lineitem.l_orderkey")
+    if steps:
+        engine.encode_steps("lineitem.lineitem_orders")
     return keep
 
 

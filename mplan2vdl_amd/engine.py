@@ -97,6 +97,13 @@ class Plan:
         self._e._check(self._e._L.vdl_plan_image_columns(self._h, ctypes.byref(text)))
         return _lib.parse_image_columns((text.value or b"").decode())
 
+    def step_columns(self):
+        """{role: [catalog column, ...]} of the scans that read a column from its step image, as bound at the last run or jit_check
+        (vdl.h: vdl_plan_step_columns); such a column is not in image_columns() under that role.  {} when none does."""
+        text = ctypes.c_char_p()
+        self._e._check(self._e._L.vdl_plan_step_columns(self._h, ctypes.byref(text)))
+        return _lib.parse_step_columns((text.value or b"").decode())
+
     def set_trace(self, enabled):
         """Keep a host copy of every statement's vector (statement-by-statement runs only): see `traced()`."""
         self._e._check(self._e._L.vdl_plan_set_trace(self._h, int(bool(enabled))))
@@ -472,6 +479,33 @@ class Engine:
     def set_column_images(self, enabled):
         """False: scans read the catalog columns and ignore their images (tests, A/B runs in one process)"""
         self._check(self._L.vdl_set_column_images(self._c, 1 if enabled else 0))
+
+    def encode_steps(self, name):
+        """Try to build the step image of a catalog column (vdl_encode_steps): a column that never decreases and steps by at most
+        1 gets one, any other column none.  For a borrowed column the caller promises not to write it afterwards."""
+        self._check(self._L.vdl_encode_steps(self._c, name.encode()))
+
+    def steps_info(self, name):
+        """(present, base, groups) of a column's step image; (False, 0, 0) = none"""
+        p, b, g = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._L.vdl_column_steps_info(self._c, name.encode(), ctypes.byref(p), ctypes.byref(b), ctypes.byref(g)))
+        return bool(p.value), b.value, g.value
+
+    def download_steps(self, name):
+        """the step image (vdl_download_steps_image): (heads as uint64, anchors as uint32), one entry per 64 rows"""
+        groups = self.steps_info(name)[2]
+        heads, anchors = np.empty(groups, dtype=np.uint64), np.empty(groups, dtype=np.uint32)
+        self._check(self._L.vdl_download_steps_image(self._c, name.encode(), heads.ctypes.data_as(ctypes.c_void_p),
+                                                     anchors.ctypes.data_as(ctypes.c_void_p), groups))
+        return heads, anchors
+
+    def declare_steps(self, name, base=0):
+        """a context without a device: the column has a step image (jit_check builds the scans that decode it)"""
+        self._check(self._L.vdl_declare_steps_image(self._c, name.encode(), int(base)))
+
+    def set_step_images(self, enabled):
+        """False: scans leave the step images unbound (A/B runs in one process)"""
+        self._check(self._L.vdl_set_step_images(self._c, 1 if enabled else 0))
 
     def drop(self, name):
         self._keep.pop(name, None)
