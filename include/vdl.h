@@ -260,8 +260,9 @@ int  vdl_timing(const vdl_plan *plan, int k, const char **label, double *usec);
  *   - rows equal on every key stay in the order of the unordered result (ties are broken by the row's position, ascending):
  *     the order is total and equals numpy's lexsort with the position as the last key;
  *   - a key is ordered by the int64 the engine holds for it.  For decimals and dates that is the SQL order.  A string field
- *     is its dictionary code (a heap offset, dictionary.csv): ordering by one groups equal strings but is NOT alphabetical --
- *     ordering by the text belongs to the decoding side (resolve.py);
+ *     is its dictionary code (a heap offset, dictionary.csv): ordered as an int64 it groups equal strings but is NOT alphabetical.
+ *     vdl_plan_set_order_text declares such a key as text over its heap column, and the key is then ordered by the strings
+ *     themselves, on the device, through the heap's collation index (below);
  *   - limit 0 = all rows; limit L > 0 = the first min(L, m) rows of that order.  No keys and L > 0 = the first L rows in program
  *     order.  No keys and limit 0 clears the order: the plan runs as if none had ever been set.
  * A key names an output by its full field name (the `name` of vdl_output, e.g. "o_orderdate__orders__o_orderdate") or by its
@@ -279,6 +280,53 @@ const char *vdl_plan_order_note(const vdl_plan *plan);
 /* The host formulation of exactly that order, device-free: index_out[r] = position of the row of rank r, for r < min(limit or m, m).
  * keys[k] points to m int64.  What the engine itself uses for results that lie on the host. */
 int  vdl_order_host(int n_keys, const int64_t *const *keys, const int *descending, int64_t m, int64_t limit, int64_t *index_out);
+
+/* ---- text keys: alphabetical order from a collation index ------------------------------------------------------------
+ * A string heap is an ordinary catalog column of one byte per slot ("part.p_brand.heap"): NUL-terminated strings at the offsets
+ * dictionary.csv names, no alignment promised.  Its collation index maps every offset at which a string starts to that string's
+ * dense rank in text order:
+ *   - text order is strcmp order on UNSIGNED bytes (0x80 sorts after 0x7f), a string before its extensions; the heap's end
+ *     terminates a last string without NUL;
+ *   - an offset whose byte is NUL is the empty string, rank 0;
+ *   - an offset whose byte is not NUL and whose predecessor is NUL (or offset 0) starts a string: rank = 1 + the number of DISTINCT
+ *     non-empty strings of the heap that sort strictly before it.  Equal strings stored at different offsets share a rank: they tie,
+ *     and the next key, then the position, decides, as SQL requires;
+ *   - every other code -- negative, at or past the heap's end, inside a string -- names no string of the heap.
+ * The index is one int32 per g heap bytes, g the largest power of two <= 8 that divides every start (4 * heap_n / 8 bytes for the
+ * 8-aligned heaps MonetDB writes, never more than 4 bytes per heap byte).  It belongs to the context and goes with its column (drop,
+ * re-registration, a new upload).  It is built by vdl_build_collation, or by the first run whose order needs it; that run then
+ * carries a timing "timeInMicrosecondsForCollation_<heap>" of its own (the build is not part of timeInMicrosecondsForOrder; with
+ * vdl_plan_set_profiling also "timeInMicrosecondsForCollation{Mark,Starts,Words,Sort,Ranks,Table}_<heap>", the build's steps).
+ * Heaps of 2^31 bytes or more, and heaps with a string longer than 256 bytes: VDL_ERR_UNSUPPORTED, the message naming heap and
+ * length.  A column that is not one byte wide: VDL_ERR_ARG.
+ * vdl_collation_info: present = 0 (and zeros) when the column has no index; otherwise the strings that start in the heap, how many
+ * of them are distinct, and the longest one's bytes.  Any out pointer may be null.
+ *
+ * vdl_plan_set_order_text marks ONE key of the order currently set (named as in vdl_plan_set_order) as text over heap_column;
+ * heap_column NULL clears the mark.  VDL_ERR_ARG if `field` is no key of the current order; no device and no run needed.  (An
+ * output is a key at most once -- vdl_plan_set_order refuses a field given twice, under either of its names -- so one mark per field
+ * is all there is to set.)
+ * vdl_plan_set_order clears all marks.  At run time the order word of a text key is rank ^ flip like any key's: the codes are
+ * translated by one kernel per text key inside the order step, the selection / sort / gather run on the ranks as on any int64
+ * key, and results a fused plan assembles on the host get their ranks from the same device index.  The heap must be registered
+ * when the plan runs (VDL_ERR_ARG naming it otherwise).  A run that meets a code that names no string of the heap fails with
+ * VDL_ERR_SHAPE, the message naming key, heap, how many such rows there were and the first of them: nothing is ordered by garbage.
+ * With vdl_plan_set_profiling the translate launches are also timed alone, "timeInMicrosecondsForOrderTextKeys" (they lie inside
+ * timeInMicrosecondsForOrder).  vdl_plan_order_note ends in " text_keys=<n>" when n > 0 keys were text.  vdl_run_batch applies such an order as vdl_run does;
+ * sharded entry points refuse the plan like any ordered plan. */
+int  vdl_build_collation(vdl_ctx *ctx, const char *heap_column);
+int  vdl_collation_info(const vdl_ctx *ctx, const char *heap_column, int *present, int64_t *strings, int64_t *distinct, int *max_bytes);
+int  vdl_plan_set_order_text(vdl_plan *plan, const char *field, const char *heap_column);
+/* The host formulation of exactly those ranks, device-free (a sort under strcmp-on-unsigned): ranks_out[i] for codes[i], i < m;
+ * a code that names no string gets -1, *n_bad counts them and *first_bad is the first such i (-1: none).  n_bad / first_bad may be
+ * null. */
+int  vdl_collate_host(const int8_t *heap, int64_t heap_n, const int64_t *codes, int64_t m, int64_t *ranks_out, int64_t *n_bad,
+                      int64_t *first_bad);
+/* A TEST AID, not a query path: the same through the device index of a registered heap column (built now if the column has none),
+ * codes and ranks in HOST memory, one translate launch in between.  Bad codes are reported as by vdl_collate_host, not refused.
+ * It exists so that the index can be compared with vdl_collate_host code by code; an ordered run never calls it. */
+int  vdl_collate_device(vdl_ctx *ctx, const char *heap_column, const int64_t *codes, int64_t m, int64_t *ranks_out, int64_t *n_bad,
+                        int64_t *first_bad);
 
 
 /* Debugging aid for parity work.  With tracing on, a vdl_run that goes statement by statement (plan not fused, or

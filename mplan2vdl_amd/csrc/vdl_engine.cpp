@@ -734,13 +734,71 @@ int64_t order_resolve(const vdl_plan *p, std::vector<size_t> &keys) {
     }
     return m;
 }
-void order_outputs_on_host(vdl_plan *p) {
-    const auto t0 = std::chrono::steady_clock::now();
+int order_sort_key(vdl_ctx *c, hipStream_t s, const int64_t *key, uint64_t flip, int64_t m, uint64_t *stw, BufP &perm) {
+    HIP_CHECK(hipMemsetAsync(stw, 0, 2 * sizeof(uint64_t), s));
+    HIP_CHECK(launch_order_minmax(key, flip, nullptr, m, stw, s));
+    int64_t mm[2];
+    c->fetch_to_host(stw, 2, mm, s);
+    const uint64_t umin = ~(uint64_t)mm[0], range = (uint64_t)mm[1] - umin;
+    if (range == 0) return 0;
+    const bool split = range >= ((uint64_t)1 << 62);
+    int sorts = 0;
+    for (int half = split ? 1 : 0; half <= (split ? 2 : 0); half++) {
+        const uint64_t top = half == 0 ? range : half == 1 ? 0xffffffffull : range >> 32;
+        BufP t = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+        HIP_CHECK(launch_order_sortkey(key, flip, perm ? (const int64_t *)perm->p : nullptr, m, umin, half, (int64_t *)t->p, s));
+        // (at least two radix passes, so that the slots come out in rank order the way every GROUP BY's Partition leaves them)
+        const int64_t pcount = (int64_t)std::max<uint64_t>(top + 1, 512), max_bucket = top + 1 >= 512 ? (int64_t)top : -1;
+        BufP scr = dev_alloc(c, partition_scratch_bytes(m, pcount));
+        BufP nvalid = dev_alloc(c, sizeof(int64_t));
+        BufP ka = dev_alloc(c, sizeof(int64_t) * (size_t)m), sa = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+        BufP kb = dev_alloc(c, sizeof(int64_t) * (size_t)m), sb = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+        BufP order = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+        Src ts; ts.p = t->p; ts.kind = SRC_I64;
+        HIP_CHECK(launch_partition(ts, nullptr, m, 0, pcount, scr->p, (uint64_t *)ka->p, (int64_t *)sa->p, (uint64_t *)kb->p, (int64_t *)sb->p,
+                                   (int64_t *)nvalid->p, nullptr, s, max_bucket, (int64_t *)order->p, nullptr));
+        if (perm) {
+            BufP both = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+            HIP_CHECK(launch_order_compose((const int64_t *)perm->p, (const int64_t *)order->p, m, (int64_t *)both->p, s));
+            perm = both;
+        } else perm = order;
+        sorts++;
+    }
+    return sorts;
+}
+void order_outputs_on_host(vdl_ctx *c, vdl_plan *p) {
     std::vector<size_t> keys;
     const int64_t m = order_resolve(p, keys);
     const int64_t L = p->order.limit > 0 ? std::min<int64_t>(p->order.limit, m) : m;
+    // text keys: an index that has to be built is built (and timed under its own label) before the step's clock starts
+    const int n_text = p->order.n_text();
+    for (size_t k = 0; n_text > 0 && k < keys.size(); k++)
+        if (!p->order.text[k].empty()) collation_ensure(c, p->order.text[k], p, "order key '" + p->outs[keys[k]].name + "'");
+    const auto t0 = std::chrono::steady_clock::now();
     std::vector<const int64_t *> kp;
     for (size_t k : keys) kp.push_back(p->outs[k].ptr());
+    // ... and the handful of codes goes to the device index and comes back as ranks: one definition of the text order
+    std::vector<std::vector<int64_t>> ranks(keys.size());
+    if (n_text > 0 && m > 0) {
+        hipStream_t s = c->stream;
+        std::vector<BufP> codes(keys.size());
+        std::vector<const int64_t *> dev(keys.size(), nullptr);
+        for (size_t k = 0; k < keys.size(); k++) {
+            if (p->order.text[k].empty()) continue;
+            codes[k] = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+            HIP_CHECK(hipMemcpyAsync(codes[k]->p, kp[k], sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, s));
+            dev[k] = (const int64_t *)codes[k]->p;
+        }
+        HIP_CHECK(hipStreamSynchronize(s));                            // (pageable sources)
+        const std::vector<BufP> out = order_text_ranks(c, p, dev, m, s);
+        for (size_t k = 0; k < keys.size(); k++) {
+            if (!out[k]) continue;
+            ranks[k].resize((size_t)m);
+            HIP_CHECK(hipMemcpyAsync(ranks[k].data(), out[k]->p, sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, s));
+            kp[k] = ranks[k].data();
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
     std::vector<int64_t> index((size_t)L);
     const int rc = vdl_order_host((int)kp.size(), kp.data(), p->order.desc.data(), m, p->order.limit, index.data());
     if (rc != VDL_OK) throw Error(rc, "vdl_order_host failed");
@@ -752,7 +810,8 @@ void order_outputs_on_host(vdl_plan *p) {
         o.big = nullptr; o.big_n = 0;
     }
     p->order_note = "host m=" + std::to_string(m) + " rows=" + std::to_string(L);
-    // (no device work: the entry is the host's own time for the step)
+    if (n_text > 0) p->order_note += " text_keys=" + std::to_string(n_text);
+    // (no device work but a text key's translation: the entry is the host's own time for the step)
     p->timings.push_back({"timeInMicrosecondsForOrder", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count()});
 }
 
@@ -1524,11 +1583,25 @@ int vdl_plan_set_order(vdl_plan *p, int n_keys, const char *const *fields, const
         spec.nodes.push_back(node);
         spec.desc.push_back(descending[k] != 0);
     }
+    spec.text.assign(spec.nodes.size(), std::string());      // a new order carries no text marks (vdl_plan_set_order_text)
     spec.limit = limit;
     spec.set = n_keys > 0 || limit > 0;
     p->order = spec;
     p->order_note.clear();
     return VDL_OK;
+}
+int vdl_plan_set_order_text(vdl_plan *p, const char *field, const char *heap_column) {
+    if (!p) return VDL_ERR_ARG;
+    auto fail = [&](const std::string &why) { if (p->ctx) p->ctx->err = "vdl_plan_set_order_text: " + why; return (int)VDL_ERR_ARG; };
+    const std::string f = field ? field : "";
+    if (heap_column && !*heap_column) return fail("empty heap column name (NULL clears the mark)");
+    for (size_t k = 0; k < p->order.nodes.size(); k++) {
+        const int id = p->order.nodes[k];
+        if (p->prog.at(id).field != f && "tmp" + std::to_string(id) != f) continue;
+        p->order.text[k] = heap_column ? heap_column : "";
+        return VDL_OK;
+    }
+    return fail("'" + f + "' is not a key of the order set on this plan" + (p->order.nodes.empty() ? " (no order with keys is set)" : ""));
 }
 const char *vdl_plan_order_note(const vdl_plan *p) { return p ? p->order_note.c_str() : ""; }
 
@@ -1580,7 +1653,7 @@ int vdl_run(vdl_ctx *c, vdl_plan *p) {
                 run_fused_local(c, p, (int64_t *)p->words->p, true);
                 finalize_begin(c, p, (const int64_t *)p->words->p, 0);
                 finalize_end(c, p, 0);
-                if (p->order.set) order_outputs_on_host(p);     // a fused plan's outputs are assembled on the host: a handful of rows
+                if (p->order.set) order_outputs_on_host(c, p);     // a fused plan's outputs are assembled on the host: a handful of rows
                 return;
             } catch (const NeedGeneralPath &e) {
                 p->fallback_note = e.what();          // exact for any data: rerun statement by statement
@@ -1692,7 +1765,7 @@ void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
             try {
                 finalize_end(c, p, 0);
                 p->batch_words = false;
-                if (p->order.set) order_outputs_on_host(p);
+                if (p->order.set) order_outputs_on_host(c, p);
             } catch (const Error &e) {
                 p->batch_words = false;
                 throw Error(e.code, "plan " + std::to_string(ms[(size_t)q]->index) + ": " + e.what());

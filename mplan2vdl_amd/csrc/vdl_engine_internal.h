@@ -85,6 +85,14 @@ struct DevBuf {
 };
 using BufP = std::shared_ptr<DevBuf>;
 
+// table[offset >> gshift]: 0 = the byte is NUL (the empty string), -1 = no string starts there, else the rank (1 = the smallest string)
+struct Collation {
+    BufP table;                     // int32, collate_table_slots(heap_n, gshift) of them
+    int gshift = 3;                 // the largest power of two <= 8 that divides every start
+    int64_t heap_n = 0, strings = 0, distinct = 0;
+    int max_bytes = 0;
+};
+
 struct Column {
     const void *dev = nullptr;
     int width = 0;
@@ -103,6 +111,9 @@ struct Column {
     // steps.present: declared on a context without a device)
     img::Steps steps;
     BufP steps_buf;
+    // a heap column's collation index (vdl_collate.hip): heap offset -> dense rank of the string that starts there in text order.  Built
+    // by vdl_build_collation or by the first run whose order names the heap for a text key; goes with the column like the images
+    std::shared_ptr<Collation> collation;
 };
 
 // device-side vector of the general path
@@ -264,7 +275,9 @@ struct vdl_plan {
         bool set = false;
         std::vector<int> nodes;          // the key outputs: ids of their MaterializeCompact statements
         std::vector<int> desc;
+        std::vector<std::string> text;   // per key: the heap column whose text order the key's codes stand for (vdl_plan_set_order_text), "" = ordered as int64
         int64_t limit = 0;
+        int n_text() const { int k = 0; for (const std::string &h : text) k += h.empty() ? 0 : 1; return k; }
     } order;
     std::string order_note;              // what the order step of the last run did
     hipEvent_t order_ev[2] = {nullptr, nullptr};
@@ -480,7 +493,21 @@ inline void refuse_order_sharded(const vdl_plan *p) {
                                          "per-rank top-N results is not built; run it on one GPU with vdl_run, or clear the order");
 }
 // the order step for results that lie on the host (vdl_engine.cpp): checks the outputs' lengths, vdl_order_host + a permute of every output
-void order_outputs_on_host(vdl_plan *p);
+// (text keys: their ranks come from the device index through one small launch and a fetch, so `c` needs its device then)
+void order_outputs_on_host(vdl_ctx *c, vdl_plan *p);
+// One key's stable sort of the full order: the rows, standing in the order `perm` (null = as they are), re-ordered by u = key ^ flip
+// through the one-sweep Partition on u - min(u); `perm` becomes the new order, or stays when the key is constant.  stw: two device
+// words.  Returns the Partitions run (a range of 2^62 or more is sorted as two 32-bit halves, low half first: the Partition's domain
+// is 63 bits).  What order_sort does per key and the collation build per word of text.
+int order_sort_key(vdl_ctx *c, hipStream_t s, const int64_t *key, uint64_t flip, int64_t m, uint64_t *stw, BufP &perm);      // vdl_engine.cpp
+// ---- collation (vdl_collate.cpp) ----
+// the index of heap column `heap`, built now if the column has none.  p (may be null): a build is timed into p->timings under
+// "timeInMicrosecondsForCollation_<heap>".  who: what to name in the VDL_ERR_ARG when the column is not registered
+std::shared_ptr<Collation> collation_ensure(vdl_ctx *c, const std::string &heap, vdl_plan *p, const std::string &who);
+// The plan's text keys translated: out[k] = m int64 ranks for key k (null for a key that is no text key); codes[k] = that key's m
+// codes ON THE DEVICE.  The indexes must exist (collation_ensure).  One launch per text key and ONE fetch of the verdicts;
+// VDL_ERR_SHAPE naming key, heap, count and first row when a code names no string of its heap.
+std::vector<BufP> order_text_ranks(vdl_ctx *c, vdl_plan *p, const std::vector<const int64_t *> &codes, int64_t m, hipStream_t s);
 // the outputs' common length and the key outputs' ordinals, checked (VDL_ERR_SHAPE naming outputs and lengths)
 int64_t order_resolve(const vdl_plan *p, std::vector<size_t> &keys);
 size_t exchange_fold_count(const vdl_plan *p, const std::string &table);      // vdl_exchange.cpp: global folds beside the Partition (sharded runs)

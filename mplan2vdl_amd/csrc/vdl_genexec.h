@@ -1735,36 +1735,7 @@ struct GenExec {
         uint64_t *stw = (uint64_t *)st->p;
         BufP perm;
         int sorts = 0;
-        for (int k = K.n - 1; k >= 0; k--) {
-            HIP_CHECK(hipMemsetAsync(stw, 0, 2 * sizeof(uint64_t), s));
-            HIP_CHECK(launch_order_minmax(K.key[k], K.flip[k], nullptr, m, stw, s));
-            int64_t mm[2];
-            fetch_words(stw, 2, mm);
-            const uint64_t umin = ~(uint64_t)mm[0], range = (uint64_t)mm[1] - umin;
-            if (range == 0) continue;
-            // the Partition's domain is 63 bits: a wider range is sorted as two 32-bit halves, low half first
-            const bool split = range >= ((uint64_t)1 << 62);
-            for (int half = split ? 1 : 0; half <= (split ? 2 : 0); half++) {
-                const uint64_t top = half == 0 ? range : half == 1 ? 0xffffffffull : range >> 32;
-                BufP t = dev_alloc(c, sizeof(int64_t) * (size_t)m);
-                HIP_CHECK(launch_order_sortkey(K.key[k], K.flip[k], perm ? (const int64_t *)perm->p : nullptr, m, umin, half, (int64_t *)t->p, s));
-                // (at least two radix passes, so that the slots come out in rank order the way every GROUP BY's Partition leaves them)
-                const int64_t pcount = (int64_t)std::max<uint64_t>(top + 1, 512), max_bucket = top + 1 >= 512 ? (int64_t)top : -1;
-                BufP scr = dev_alloc(c, partition_scratch_bytes(m, pcount));
-                BufP nvalid = dev_alloc(c, sizeof(int64_t));
-                BufP ka = dev_alloc(c, sizeof(int64_t) * (size_t)m), sa = dev_alloc(c, sizeof(int64_t) * (size_t)m);
-                BufP kb = dev_alloc(c, sizeof(int64_t) * (size_t)m), sb = dev_alloc(c, sizeof(int64_t) * (size_t)m);
-                BufP order = dev_alloc(c, sizeof(int64_t) * (size_t)m);
-                HIP_CHECK(launch_partition(i64_src(t), nullptr, m, 0, pcount, scr->p, (uint64_t *)ka->p, (int64_t *)sa->p, (uint64_t *)kb->p, (int64_t *)sb->p,
-                                           (int64_t *)nvalid->p, nullptr, s, max_bucket, (int64_t *)order->p, nullptr));
-                if (perm) {
-                    BufP both = dev_alloc(c, sizeof(int64_t) * (size_t)m);
-                    HIP_CHECK(launch_order_compose((const int64_t *)perm->p, (const int64_t *)order->p, m, (int64_t *)both->p, s));
-                    perm = both;
-                } else perm = order;
-                sorts++;
-            }
-        }
+        for (int k = K.n - 1; k >= 0; k--) sorts += order_sort_key(c, s, K.key[k], K.flip[k], m, stw, perm);
         note = "sort m=" + std::to_string(m) + " rows=@ partitions=" + std::to_string(sorts);
         return perm;
     }
@@ -1776,7 +1747,7 @@ struct GenExec {
         const int64_t L = p->order.limit > 0 ? std::min<int64_t>(p->order.limit, m) : m;
         bool on_device = false;
         for (const Output &o : p->outs) on_device |= o.dev != nullptr;
-        if (!on_device) { order_outputs_on_host(p); return; }          // (m = 0 included: nothing was kept)
+        if (!on_device) { order_outputs_on_host(c, p); return; }          // (m = 0 included: nothing was kept)
         kept.resize(p->outs.size());
         for (size_t k = 0; k < p->outs.size(); k++) {                  // a result a statement assembled on the host joins the others
             Output &o = p->outs[k];
@@ -1786,11 +1757,20 @@ struct GenExec {
             HIP_CHECK(hipStreamSynchronize(s));                        // (pageable source)
             o.dev = (const int64_t *)kept[k]->p;
         }
+        // text keys: an index that has to be built is built (and timed) before the order step's own events
+        const int n_text = p->order.n_text();
+        for (size_t k = 0; n_text > 0 && k < keys.size(); k++)
+            if (!p->order.text[k].empty()) collation_ensure(c, p->order.text[k], p, "order key '" + p->outs[keys[k]].name + "'");
         if (!p->order_ev[1]) { HIP_CHECK(hipEventCreate(&p->order_ev[0])); HIP_CHECK(hipEventCreate(&p->order_ev[1])); }
         HIP_CHECK(hipEventRecord(p->order_ev[0], s));
         OrdKeys K;
         K.n = (int)keys.size();
         for (int k = 0; k < K.n; k++) { K.key[k] = p->outs[keys[(size_t)k]].dev; K.flip[k] = order_flip(p->order.desc[(size_t)k]); }
+        std::vector<BufP> text_ranks;                                  // a text key is ordered by its strings' ranks: they take the codes' place
+        if (n_text > 0) {
+            text_ranks = order_text_ranks(c, p, std::vector<const int64_t *>(K.key, K.key + K.n), m, s);
+            for (int k = 0; k < K.n; k++) if (text_ranks[(size_t)k]) K.key[k] = (const int64_t *)text_ranks[(size_t)k]->p;
+        }
         BufP index;                                                    // null: the rows stay in place
         std::string note = "sort m=" + std::to_string(m) + " rows=@ partitions=0";
         if (K.n > 0 && m > 1) {
@@ -1799,6 +1779,7 @@ struct GenExec {
         }
         const size_t at = note.find('@');
         if (at != std::string::npos) note.replace(at, 1, std::to_string(L));
+        if (n_text > 0) note += " text_keys=" + std::to_string(n_text);
         p->order_note = note;
         std::vector<BufP> cut(p->outs.size());
         if (index) {

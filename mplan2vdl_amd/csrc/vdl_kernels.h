@@ -329,4 +329,23 @@ hipError_t launch_order_gather(const OrdGather &G, const int64_t *index, int64_t
 hipError_t launch_order_sortkey(const int64_t *key, uint64_t flip, const int64_t *perm, int64_t m, uint64_t umin, int half, int64_t *out, hipStream_t s);
 hipError_t launch_order_compose(const int64_t *perm, const int64_t *order, int64_t m, int64_t *out, hipStream_t s);
 
+// ---- collation index of a string heap: heap offset -> dense rank in text order (vdl_collate.hip) ---------------
+constexpr int kCollateMaxBytes = 256;                                  // the longest string an index is built for
+// the table has one int32 per 2^gshift heap bytes (gshift = 3 for heaps whose strings all start at multiples of 8): 0 = the byte is NUL
+// (the empty string), -1 = no string starts here, otherwise the rank of the string that does (1 = the smallest non-empty string)
+inline int64_t collate_table_slots(int64_t heap_n, int gshift) { return (heap_n + ((int64_t)1 << gshift) - 1) >> gshift; }
+hipError_t launch_collate_mark(const int8_t *heap, int64_t n, uint64_t *starts /* (n + 63) / 64 words */, hipStream_t s);
+// off: the d start offsets, ascending.  state (two words, zero before): [0] the longest string in bytes, [1] the OR of the offsets
+hipError_t launch_collate_lengths(const int8_t *heap, int64_t n, const int64_t *off, int64_t d, uint64_t *state, hipStream_t s);
+// words[j * d + i] = bytes [8j, 8j + 8) of string i, big-endian, zero from its NUL on; nwords * 8 >= the longest string
+hipError_t launch_collate_words(const int8_t *heap, int64_t n, const int64_t *off, int64_t d, int nwords, uint64_t *words, hipStream_t s);
+// perm: the strings in text order (null = as they stand).  flags: d + 1 words; an exclusive prefix sum over them leaves the rank of
+// sorted place r in flags[r + 1], and so the number of distinct strings in flags[d]
+hipError_t launch_collate_heads(const uint64_t *words, const int64_t *perm, int64_t d, int nwords, int64_t *flags, hipStream_t s);
+hipError_t launch_collate_table(const int8_t *heap, int64_t n, int gshift, const int64_t *off, const int64_t *perm, const int64_t *ranks /* the scanned flags */,
+                                int64_t d, int32_t *table /* collate_table_slots(n, gshift) */, hipStream_t s);
+// the order step's text key: ranks[i] of the string code[i] names, -1 for a code that names none; state (two words, zero before): [0] = such rows, [1] = ~(the first of them)
+hipError_t launch_order_textkey(const int64_t *code, int64_t m, const int8_t *heap, int64_t n, const int32_t *table, int gshift, int64_t *ranks, uint64_t *state,
+                                hipStream_t s);
+
 }  // namespace vdl

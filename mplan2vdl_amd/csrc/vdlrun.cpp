@@ -22,9 +22,10 @@
 // line "vdlrun: step images: <vdl_plan_step_columns>" goes to stderr beside the images line; it is also printed when --encode runs
 // under VDL_STEP_IMAGES=1, which makes vdl_encode_column try a step image too.
 //   ... | vdlrun --order-by revenue:desc,o_orderdate__orders__o_orderdate --limit 10 ...      ORDER BY / LIMIT on the device
-// --order-by FIELD[:asc|:desc],... names outputs by their full field name or their tmpN key, --limit N keeps the first N rows
-// (vdl_plan_set_order): the reply has the same shape with shorter, ordered lists, so resolve.py decodes it untouched.  Not with
-// --gpus: the ranks hold disjoint result rows and the merge of per-rank top-N results is not built.
+// --order-by FIELD[:asc|:desc][:text[=HEAP]],... names outputs by their full field name or their tmpN key, --limit N keeps the first N
+// rows (vdl_plan_set_order); :text orders the key by its strings (vdl_plan_set_order_text) over HEAP, or over table.col.heap for a
+// field named col__table__col, and --data uploads that heap too.  The reply has the same shape with shorter, ordered lists, so
+// resolve.py decodes it untouched.  Not with --gpus: the ranks hold disjoint result rows and the merge of per-rank top-N results is not built.
 //   ... | vdlrun --jit --batch b.vdl --batch c.vdl ...                             several programs, one pass where they can share it
 // --batch FILE (repeatable; needs --jit or --jit-tune): the program on stdin and the programs in the files run as ONE vdl_run_batch --
 // those that differ in their literals alone share one scan of the columns, the others run alone inside the same call -- and one reply
@@ -82,6 +83,7 @@ int load_data_dir(vdl_ctx *ctx, const std::string &dir, const std::string &progr
         while (!name.empty() && isspace((unsigned char)name.back())) name.pop_back();
         auto it = listed.find(name);
         if (it == listed.end()) { std::fprintf(stderr, "vdlrun: column %s is not in %s/columns.csv\n", name.c_str(), dir.c_str()); return 1; }
+        if (it->second.rows < 0) continue;                 // uploaded already
         // a column of the sharded table: this rank's row range only (string heaps "table.col.heap" are not row-aligned: whole)
         int64_t lo = 0, hi = it->second.rows;
         const bool is_heap = name.size() > 5 && name.compare(name.size() - 5, 5, ".heap") == 0;
@@ -190,12 +192,14 @@ struct Options {
     std::string data_dir, shard = "lineitem";
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
+    std::vector<std::string> order_heaps;       // per key: the heap of a :text key, "" otherwise
     long long limit = 0;
     std::vector<std::string> batch_files;       // --batch
     std::vector<std::string> batch_texts;       // ... and what they hold
 };
 
-// "a:desc,b,c:asc" -> fields and directions; false = malformed (empty list or field, unknown direction)
+// "a:desc,b,c:asc:text,d:text=t.c.heap" -> fields, directions and text heaps ("" = no text key); false = malformed (empty list or
+// field, unknown or repeated modifier, a text key whose heap is neither given nor derivable from the field's name)
 bool parse_order_by(const std::string &list, Options &o) {
     size_t at = 0;
     if (list.empty()) return false;
@@ -203,16 +207,33 @@ bool parse_order_by(const std::string &list, Options &o) {
         const size_t comma = list.find(',', at);
         std::string item = list.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
         int desc = 0;
-        const size_t colon = item.find(':');
-        if (colon != std::string::npos) {
-            const std::string dir = item.substr(colon + 1);
-            if (dir == "desc") desc = 1;
-            else if (dir != "asc") return false;
-            item.resize(colon);
+        bool have_dir = false, text = false;
+        std::string heap;
+        size_t colon = item.find(':');
+        const std::string field = item.substr(0, colon);
+        while (colon != std::string::npos) {
+            const size_t next = item.find(':', colon + 1);
+            const std::string mod = item.substr(colon + 1, next == std::string::npos ? std::string::npos : next - colon - 1);
+            if ((mod == "asc" || mod == "desc") && !have_dir) { have_dir = true; desc = mod == "desc"; }
+            else if (mod == "text" && !text) text = true;
+            else if (mod.compare(0, 5, "text=") == 0 && mod.size() > 5 && !text) { text = true; heap = mod.substr(5); }
+            else return false;
+            colon = next;
         }
-        if (item.empty()) return false;
-        o.order_fields.push_back(item);
+        if (field.empty()) return false;
+        if (text && heap.empty()) {
+            // col__table__col (how the compiler names a column's output) -> table.col.heap
+            const size_t a1 = field.find("__"), a2 = a1 == std::string::npos ? a1 : field.find("__", a1 + 2);
+            if (a2 == std::string::npos || a1 == 0 || a2 == a1 + 2 || a2 + 2 >= field.size() || field.find("__", a2 + 2) != std::string::npos) {
+                std::fprintf(stderr, "vdlrun: --order-by %s:text: no heap can be derived from this field (only from col__table__col, as table.col.heap); "
+                                     "name it with :text=HEAP\n", field.c_str());
+                return false;
+            }
+            heap = field.substr(a1 + 2, a2 - a1 - 2) + "." + field.substr(a2 + 2) + ".heap";
+        }
+        o.order_fields.push_back(field);
         o.order_desc.push_back(desc);
+        o.order_heaps.push_back(heap);
         if (comma == std::string::npos) return true;
         at = comma + 1;
     }
@@ -239,6 +260,8 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
             std::vector<const char *> fields;
             for (const std::string &f : o.order_fields) fields.push_back(f.c_str());
             if ((rc = vdl_plan_set_order(one, (int)fields.size(), fields.data(), o.order_desc.data(), o.limit))) return die(ctx, "vdl_plan_set_order", rc);
+            for (size_t q = 0; q < o.order_heaps.size(); q++)
+                if (!o.order_heaps[q].empty() && (rc = vdl_plan_set_order_text(one, o.order_fields[q].c_str(), o.order_heaps[q].c_str()))) return die(ctx, "vdl_plan_set_order_text", rc);
         }
         plans.push_back(one);
         if (o.describe) break;
@@ -247,6 +270,8 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
     if (o.describe) { std::fputs(vdl_plan_describe(plan), stdout); return 0; }
     int64_t row0 = 0;
     if (!o.data_dir.empty()) {
+        // the heaps of text keys are read by the order step, whether or not a program Loads them
+        for (const std::string &h : o.order_heaps) if (!h.empty()) loads += "\n0,Load," + h;
         if (load_data_dir(ctx, o.data_dir, loads, o.shard, rank, world, &row0, o.encode != 0, o.encode_steps != 0)) return 1;
     } else {
         row0 = o.rows * rank / world;
@@ -332,7 +357,7 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc],... ] [--limit N] [--batch FILE ...] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--batch FILE ...] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }

@@ -133,12 +133,30 @@ class Plan:
         """ORDER BY / LIMIT on the device: `keys` is a list of (field, descending) pairs (a bare string = ascending), a field
         being an output's full name or its "tmpN" key; `limit` 0 = all rows.  Every output of `run()` then comes back permuted
         by that one order (signed int64 keys, ties in the order of the unordered result) and cut to the limit.  No keys and
-        limit 0 clears it.  String fields order by their dictionary code, not alphabetically (include/vdl.h)."""
-        pairs = [(k, False) if isinstance(k, (str, bytes)) else (k[0], bool(k[1])) for k in keys]
-        n = len(pairs)
-        fields = (ctypes.c_char_p * max(n, 1))(*[f.encode() if isinstance(f, str) else f for f, _ in pairs])
-        desc = (ctypes.c_int * max(n, 1))(*[int(d) for _, d in pairs])
+        limit 0 clears it.  A string field is its dictionary code: ordered as a number it groups equal strings but is not
+        alphabetical.  A third element, (field, descending, heap), declares the key as text over that heap column
+        ("part.p_brand.heap"): it is then ordered by the strings themselves -- unsigned bytes, a prefix before its extensions,
+        equal strings at different offsets tie -- through the heap's collation index (`Engine.build_collation`; built by the
+        first run that needs it otherwise).  The heap must be in the catalog when the plan runs."""
+        triples = []
+        for k in keys:
+            if isinstance(k, (str, bytes)):
+                triples.append((k, False, None))
+            else:
+                triples.append((k[0], bool(k[1]), k[2] if len(k) > 2 else None))
+        n = len(triples)
+        enc = lambda t: t.encode() if isinstance(t, str) else t       # noqa: E731
+        fields = (ctypes.c_char_p * max(n, 1))(*[enc(f) for f, _, _ in triples])
+        desc = (ctypes.c_int * max(n, 1))(*[int(d) for _, d, _ in triples])
         self._e._check(self._e._L.vdl_plan_set_order(self._h, n, fields, desc, int(limit)))
+        for f, _, heap in triples:
+            if heap is not None:
+                self.set_order_text(f, heap)
+
+    def set_order_text(self, field, heap):
+        """Mark one key of the order set now as text over the heap column `heap` (vdl_plan_set_order_text); None clears the mark."""
+        enc = lambda t: t.encode() if isinstance(t, str) else t       # noqa: E731
+        self._e._check(self._e._L.vdl_plan_set_order_text(self._h, enc(field), None if heap is None else enc(heap)))
 
     def order_note(self):
         """What the order step of the last run did ("host ...", "topn ...", "sort ..."); "" when no order is set."""
@@ -294,6 +312,24 @@ def order_host(keys, descending, limit=0):
     if rc != _lib.VDL_OK:
         raise VdlError(rc, "vdl_order_host: bad argument")
     return out
+
+
+def collate_host(heap, codes):
+    """vdl_collate_host: (ranks, n_bad, first_bad) -- for every code the dense rank of the string that starts at that offset of
+    `heap` (bytes or an int8 / uint8 array) in text order: unsigned bytes, a prefix before its extensions, equal strings share a
+    rank, 0 = the empty string (a NUL byte), -1 = the code names no string of the heap (first_bad = the first such row, -1 =
+    none).  The definition the device's collation index is checked against.  Needs no GPU."""
+    L = _lib.load()
+    h = np.frombuffer(bytes(heap), dtype=np.int8) if isinstance(heap, (bytes, bytearray)) else np.ascontiguousarray(heap).view(np.int8)
+    c = np.ascontiguousarray(codes, dtype=np.int64)
+    out = np.empty(len(c), np.int64)
+    bad, first = ctypes.c_int64(), ctypes.c_int64()
+    p64 = ctypes.POINTER(ctypes.c_int64)
+    rc = L.vdl_collate_host(h.ctypes.data_as(ctypes.c_void_p) if len(h) else None, len(h), c.ctypes.data_as(p64), len(c), out.ctypes.data_as(p64),
+                            ctypes.byref(bad), ctypes.byref(first))
+    if rc != _lib.VDL_OK:
+        raise VdlError(rc, "vdl_collate_host: bad argument")
+    return out, bad.value, first.value
 
 
 class Engine:
@@ -506,6 +542,28 @@ class Engine:
     def set_step_images(self, enabled):
         """False: scans leave the step images unbound (A/B runs in one process)"""
         self._check(self._L.vdl_set_step_images(self._c, 1 if enabled else 0))
+
+    def build_collation(self, heap):
+        """Build the collation index of a heap column now (vdl_build_collation) instead of at the first run that orders by its
+        text; nothing happens when the column has one."""
+        self._check(self._L.vdl_build_collation(self._c, heap.encode()))
+
+    def collate(self, heap, codes):
+        """(ranks, n_bad, first_bad) like `collate_host`, through the device's collation index of the heap column `heap`
+        (vdl_collate_device; the index is built if the column has none)."""
+        c = np.ascontiguousarray(codes, dtype=np.int64)
+        out = np.empty(len(c), np.int64)
+        bad, first = ctypes.c_int64(), ctypes.c_int64()
+        p64 = ctypes.POINTER(ctypes.c_int64)
+        self._check(self._L.vdl_collate_device(self._c, heap.encode(), c.ctypes.data_as(p64), len(c), out.ctypes.data_as(p64), ctypes.byref(bad),
+                                               ctypes.byref(first)))
+        return out, bad.value, first.value
+
+    def collation_info(self, heap):
+        """(present, strings, distinct, max_bytes) of a heap column's collation index; (False, 0, 0, 0) = none"""
+        p, n, d, b = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+        self._check(self._L.vdl_collation_info(self._c, heap.encode(), ctypes.byref(p), ctypes.byref(n), ctypes.byref(d), ctypes.byref(b)))
+        return bool(p.value), n.value, d.value, b.value
 
     def drop(self, name):
         self._keep.pop(name, None)
