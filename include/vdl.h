@@ -270,7 +270,8 @@ int  vdl_timing(const vdl_plan *plan, int k, const char **label, double *usec);
  * the outputs are known from the program text).  At run time all outputs must have one length m (they are the columns of one
  * result), VDL_ERR_SHAPE names outputs and lengths otherwise; m = 0 is fine.  With vdl_plan_set_device_outputs the 65536 rule
  * applies to the ordered, cut outputs.  Sharded runs (vdl_run_sharded*, vdl_run_local, vdl_exchange_begin) refuse a plan with an
- * order set, VDL_ERR_UNSUPPORTED: the ranks hold disjoint result rows and the merge of per-rank top-N is not built.
+ * order set, VDL_ERR_UNSUPPORTED, unless vdl_plan_set_order_sharded (below, with the sharded entry points) has switched the merged
+ * order on.  vdl_plan_set_order replaces the whole order and so switches it off again.
  * With an order set the timings carry one more entry, "timeInMicrosecondsForOrder": device events around the order step (the
  * host's own time where the step ran on the host). */
 int  vdl_plan_set_order(vdl_plan *plan, int n_keys, const char *const *fields, const int *descending, int64_t limit);
@@ -313,7 +314,7 @@ int  vdl_order_host(int n_keys, const int64_t *const *keys, const int *descendin
  * VDL_ERR_SHAPE, the message naming key, heap, how many such rows there were and the first of them: nothing is ordered by garbage.
  * With vdl_plan_set_profiling the translate launches are also timed alone, "timeInMicrosecondsForOrderTextKeys" (they lie inside
  * timeInMicrosecondsForOrder).  vdl_plan_order_note ends in " text_keys=<n>" when n > 0 keys were text.  vdl_run_batch applies such an order as vdl_run does;
- * sharded entry points refuse the plan like any ordered plan. */
+ * sharded entry points treat the plan like any ordered plan (on the exchange route the heap must be replicated: vdl_plan_set_order_sharded). */
 int  vdl_build_collation(vdl_ctx *ctx, const char *heap_column);
 int  vdl_collation_info(const vdl_ctx *ctx, const char *heap_column, int *present, int64_t *strings, int64_t *distinct, int *max_bytes);
 int  vdl_plan_set_order_text(vdl_plan *plan, const char *field, const char *heap_column);
@@ -469,11 +470,40 @@ void vdl_comm_free(vdl_ctx *ctx);                       /* also done by vdl_clos
  *   runs move nothing, every rank ends with the full result ("replicate"; VDL_NO_REPLICATE_ROUTE=1 turns it into the refusal with the
  *   reasons).
  * vdl_plan_sharded_route tells which route a plan takes ("fold" | "set" | "exchange" | "front" | "chain" | "replicate") and whether every rank
- * ends with the whole answer (replicated = 1) or with its slice (0: concatenate the ranks' outputs in rank order). */
+ * ends with the whole answer (replicated = 1) or with its slice (0: concatenate the ranks' outputs in rank order; the exchange
+ * route only, and not when an order it can merge is switched on with vdl_plan_set_order_sharded: every rank then ends with the same
+ * ordered rows). */
 int  vdl_plan_sharded_route(vdl_ctx *ctx, vdl_plan *plan, const char **route, int *replicated);
 int  vdl_run_sharded(vdl_ctx *ctx, vdl_plan *plan);     /* results through vdl_output as after vdl_run */
 int  vdl_run_sharded_begin(vdl_ctx *ctx, vdl_plan *plan, int slot);
 int  vdl_run_sharded_end(vdl_ctx *ctx, vdl_plan *plan, int slot);
+/* ---- ORDER BY / LIMIT in a sharded run ----
+ * vdl_plan_set_order_sharded(plan, on): with on != 0, vdl_run_sharded, vdl_run_sharded_begin and vdl_run_sharded_end accept a plan
+ * with an order set, and EVERY rank ends with the same ordered, cut answer -- the one vdl_run gives for the unsharded data
+ * (vdl_plan_sharded_route then reports replicated = 1 on every route).  on = 0 (the default, and what vdl_plan_set_order leaves behind)
+ * keeps the refusal.  vdl_run_local and vdl_exchange_begin refuse either way: their callers run their own collectives, and the
+ * merge lives in vdl_run_sharded; the message says so.
+ *   - routes where every rank holds the whole result (fold, set, front, chain, replicate): the order step runs on each rank as in
+ *     vdl_run, in vdl_run_sharded_end for the pipelined pair.  No further collective; vdl_plan_order_note as after vdl_run.
+ *   - the exchange route, 0 < limit <= 4096: rank r selects its first L_r = min(limit, m_r) of its m_r result rows and writes
+ *     them as a candidate block (K order words u = key ^ flip and every output, in its sorted order); ONE all-gather of {status, L_r,
+ *     m_r} -- if the tail or the order step failed anywhere, every rank returns an error here (the failing rank its own) and no data
+ *     travels --; ONE grouped send / receive of the blocks; one kernel ranks every candidate among the `world` sorted runs by binary
+ *     search and writes the first L = min(limit, sum m_r) rows of every output.  The ranks' results concatenate in rank order, so
+ *     (rank, place in the rank's run) stands for the row's position: ties come out as in the unsharded run.  A text key's heap must
+ *     be replicated: a heap column of the sharded table is refused, VDL_ERR_UNSUPPORTED naming key and heap.  vdl_plan_order_note
+ *     = the local note + " | merge world=W candidates=N rows=L"; "timeInMicrosecondsForOrder" is the local selection,
+ *     "timeInMicrosecondsForOrderMerge" the staging and the merge kernel (device events; the collective is not in it).
+ *   - the exchange route with limit 0 or limit > 4096 would have to gather every result row: VDL_ERR_UNSUPPORTED, the message naming
+ *     the limit, the bound and the route, before any collective (and before a device is needed). */
+int  vdl_plan_set_order_sharded(vdl_plan *plan, int on);
+/* The merge rule on the host, device-free: `world` sorted runs of counts[r] candidates each, one after the other (N = sum counts);
+ * words[k * N + j] = order word k of candidate j (n_keys <= 8; unsigned, ascending).  Candidate j of run r takes the place
+ *   (index in its run) + sum over q < r of |{x in run q : x <= j}| + sum over q > r of |{x in run q : x < j}|
+ * under the lexicographic comparison of the words -- the order of (u_1, .., u_K, run, index).  The first L = min(limit or N, N) places:
+ * run_out[i], index_out[i] = the candidate at place i; *n_out = L (may be NULL). */
+int  vdl_order_merge_host(int world, int n_keys, const int64_t *counts, const uint64_t *words, int64_t limit, int64_t *run_out,
+                          int64_t *index_out, int64_t *n_out);
 /* The merge rule of the gathered partial words on the host (what the device kernel computes): `gathered` holds, per rank, a block
  * of `stride_words` int64 -- n_words words, the same words with VDL_REDUCE_FIRST entries resolved to values and, in the blocks
  * vdl_run_sharded itself gathers, ONE status word of the rank's local phase (stride_words = 2 * n_words + 1; pass 0 for bare blocks

@@ -87,6 +87,8 @@ def load():
         "vdl_output_device": (i32, [vp, i32, P(P(i64)), P(ctypes.c_size_t)]),
         "vdl_plan_set_order": (i32, [vp, i32, P(cp), P(i32), i64]),
         "vdl_plan_order_note": (cp, [vp]),
+        "vdl_plan_set_order_sharded": (i32, [vp, i32]),
+        "vdl_order_merge_host": (i32, [i32, i32, P(i64), P(ctypes.c_uint64), i64, P(i64), P(i64), P(i64)]),
         "vdl_order_host": (i32, [i32, P(P(i64)), P(i32), i64, i64, P(i64)]),
         "vdl_build_collation": (i32, [vp, cp]),
         "vdl_collation_info": (i32, [vp, cp, P(i32), P(i64), P(i64), P(i32)]),
@@ -138,7 +140,7 @@ ABI_SYMBOLS = [
     "vdl_plan_step_columns",
     "vdl_parse", "vdl_plan_free", "vdl_plan_describe", "vdl_plan_is_fused", "vdl_plan_set_fusion",
     "vdl_plan_set_profiling", "vdl_plan_set_jit", "vdl_plan_set_jit_bounds", "vdl_jit_counters", "vdl_plan_jit_note", "vdl_plan_jit_check", "vdl_plan_image_columns", "vdl_plan_set_trace", "vdl_n_traced", "vdl_traced", "vdl_run", "vdl_run_batch", "vdl_batch_jit_check", "vdl_plan_batch_note", "vdl_n_outputs", "vdl_output", "vdl_plan_set_device_outputs", "vdl_output_device", "vdl_n_timings", "vdl_timing",
-    "vdl_plan_set_order", "vdl_plan_order_note", "vdl_order_host",
+    "vdl_plan_set_order", "vdl_plan_order_note", "vdl_order_host", "vdl_plan_set_order_sharded", "vdl_order_merge_host",
     "vdl_build_collation", "vdl_collation_info", "vdl_plan_set_order_text", "vdl_collate_host", "vdl_collate_device",
     "vdl_plan_scan_stats", "vdl_plan_scan_traffic", "vdl_plan_partial_spec", "vdl_plan_sharded_route", "vdl_run_local", "vdl_finalize", "vdl_finalize_begin", "vdl_finalize_end", "vdl_plan_set_row_offset", "vdl_plan_set_sharded_table", "vdl_resolve_first", "vdl_exchange_spec", "vdl_exchange_begin", "vdl_exchange_pack",
     "vdl_exchange_finish", "vdl_comm_unique_id", "vdl_comm_init", "vdl_comm_init_host", "vdl_comm_info", "vdl_comm_free", "vdl_run_sharded",

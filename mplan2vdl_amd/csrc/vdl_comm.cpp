@@ -237,6 +237,9 @@ static ShardState &shard_state(vdl_ctx *c, vdl_plan *p, const CommState &m) {
 
 static void sharded_begin(vdl_ctx *c, vdl_plan *p, int slot) {
     need_device(c);
+    // (an order switched on for sharded runs: vdl_run_local lets the plan through, and a plan sharded through its global folds orders
+    // its outputs where it writes them, general_finalize; a fused plan's merged answer is ordered in vdl_run_sharded_end)
+    struct Inside { vdl_plan *p; Inside(vdl_plan *q) : p(q) { p->order_inside = true; } ~Inside() { p->order_inside = false; } } inside(p);
     if (slot < 0 || slot > 1) throw Error(VDL_ERR_ARG, "slot must be 0 or 1");
     CommState &m = comm_of(c);
     ShardState &st = shard_state(c, p, m);
@@ -296,12 +299,16 @@ static void sharded_check_status(vdl_plan *p, int slot) {
                                          "); the merged words are not an answer");
 }
 
+static void all_gather_rows(vdl_ctx *c, const std::vector<const int64_t *> &send, const std::vector<int64_t *> &recv, const std::vector<int64_t> &cnt, hipStream_t s);
+
 static void sharded_exchange(vdl_ctx *c, vdl_plan *p) {
     need_device(c);
     CommState &m = comm_of(c);
     int ncols = 0;
     const std::string table = p->sharded_table;
     if (table.empty()) throw Error(VDL_ERR_ARG, "vdl_run_sharded: name the row-sharded table first (vdl_plan_set_sharded_table)");
+    const bool merged_order = p->order.set && p->order.sharded && p->chain.stage == 0;
+    if (merged_order) { const std::string why = order_exchange_refusal(p); if (!why.empty()) throw Error(VDL_ERR_UNSUPPORTED, why); }
     struct AllowFolds { vdl_plan *p; AllowFolds(vdl_plan *q) : p(q) { p->ex_allow_folds = true; } ~AllowFolds() { p->ex_allow_folds = false; } } allow(p);
     if (vdl_exchange_spec(p, table.c_str(), &ncols) != VDL_OK) throw Error(VDL_ERR_UNSUPPORTED, c->err);
     // local phase; its outcome travels with the counts so that no rank is left waiting in a collective after a failure elsewhere.
@@ -387,8 +394,39 @@ static void sharded_exchange(vdl_ctx *c, vdl_plan *p) {
         all_to_all_columns(c, (const int64_t *)send->p, n_send, scnt, (int64_t *)recv->p, n_recv, rcnt, sent_cols, c->stream);
     }
     p->shard_keep = recv;                                     // the tail reads the received columns in place
-    if (vdl_exchange_finish(c, p, recv->p, n_recv) != VDL_OK) throw Error(VDL_ERR_DEVICE, c->err);
-    p->shard_keep.reset();
+    if (!merged_order) {
+        if (vdl_exchange_finish(c, p, recv->p, n_recv) != VDL_OK) throw Error(VDL_ERR_DEVICE, c->err);
+        p->shard_keep.reset();
+        return;
+    }
+    // An order switched on for sharded runs: the tail's order step keeps this rank's first rows and merges them with the other ranks'
+    // (GenExec::order_outputs_merged).  Every rank exchanges {status, candidates, result rows} exactly once per run -- from the order
+    // step when the tail got there, otherwise from here with its failure -- and the candidates only travel when every rank succeeded.
+    vdl_plan::OrderMerge om;
+    om.rank = m.rank; om.world = m.world;
+    bool met = false;
+    om.meet = [&](int64_t status, const std::string &own, int64_t cand, int64_t rows_here) {
+        met = true;
+        const std::vector<int64_t> got = gather_words(c, {status, cand, rows_here});
+        for (int r = 0; r < m.world; r++)
+            if (got[(size_t)r * 3] != VDL_OK) {
+                if (status != VDL_OK) throw Error((int)status, own);
+                throw Error(VDL_ERR_UNSUPPORTED, "sharded run: the tail or the order step failed on rank " + std::to_string(r) + " (status " +
+                                                 std::to_string(got[(size_t)r * 3]) + "; its error is reported there); no rows were merged");
+            }
+        return got;
+    };
+    om.gather = [&](const std::vector<const int64_t *> &from, const std::vector<int64_t *> &to, const std::vector<int64_t> &cnt) {
+        all_gather_rows(c, from, to, cnt, c->stream);
+    };
+    struct Restore { vdl_plan *p; ~Restore() { p->order_merge = nullptr; p->shard_keep.reset(); } } restore{p};
+    p->order_merge = &om;
+    const int frc = vdl_exchange_finish(c, p, recv->p, n_recv);
+    const std::string own = c->err;
+    if (!met) {                                               // the tail failed before its order step: say so to the peers, who stop with this rank
+        try { om.meet(frc != VDL_OK ? frc : (int64_t)VDL_ERR_DEVICE, own, 0, 0); } catch (const std::exception &) {}
+    }
+    if (frc != VDL_OK) throw Error(frc, own);
 }
 
 // A fused plan with a semi-join set (EXISTS / IN with the dimension on the left: TPC-H Q4, Vlite.hs:1212-1222) when the set's SOURCE
@@ -918,14 +956,17 @@ int vdl_plan_sharded_route(vdl_ctx *c, vdl_plan *p, const char **route, int *rep
         }
     }
     if (route) *route = name;
-    if (replicated) *replicated = std::strcmp(name, "exchange") != 0;
+    // (the exchange route under an order switched on for sharded runs merges the ranks' first rows: every rank ends with all of them)
+    const bool merged_order = p->order.set && p->order.sharded && order_exchange_refusal(p).empty();
+    if (replicated) *replicated = std::strcmp(name, "exchange") != 0 || merged_order;
     return VDL_OK;
 }
 
 int vdl_run_sharded_begin(vdl_ctx *c, vdl_plan *p, int slot) {
     if (!c || !p) return VDL_ERR_ARG;
     return guard(c, [&] {
-        refuse_order_sharded(p);
+        refuse_order_sharded(p, true);
+        p->order_note.clear();
         if (!fold_route(c, p)) throw Error(VDL_ERR_UNSUPPORTED, "vdl_run_sharded_begin serves plans whose outputs are folds (partial words); plans with a "
                                                                "Partition exchange rows and run through vdl_run_sharded");
         sharded_begin(c, p, slot);
@@ -936,12 +977,17 @@ int vdl_run_sharded_end(vdl_ctx *c, vdl_plan *p, int slot) {
     if (!c || !p) return VDL_ERR_ARG;
     const int rc = vdl_finalize_end(c, p, slot);
     const int rs = guard(c, [&] { sharded_check_status(p, slot); });      // (a failed peer outranks whatever the merged zeros gave)
-    return rs != VDL_OK ? rs : rc;
+    if (rs != VDL_OK || rc != VDL_OK) return rs != VDL_OK ? rs : rc;
+    // an order switched on for sharded runs: every rank has assembled the whole answer on the host and orders it as vdl_run does
+    // (a plan sharded through its global folds ordered its outputs when it wrote them: general_finalize)
+    if (p->order.set && p->order.sharded && p->use_fusion && p->fused.ok) return guard(c, [&] { order_outputs_on_host(c, p); });
+    return VDL_OK;
 }
 
 int vdl_run_sharded(vdl_ctx *c, vdl_plan *p) {
     if (!c || !p) return VDL_ERR_ARG;
-    if (const int rc = guard(c, [&] { refuse_order_sharded(p); })) return rc;
+    if (const int rc = guard(c, [&] { refuse_order_sharded(p, true); })) return rc;
+    p->order_note.clear();
     if (p->use_fusion && p->fused.ok) {                       // a fused plan with a semi-join set: the sets are merged across the ranks
         bool semi = false;
         for (const PreludeItem &it : p->fused.prelude) semi |= it.kind == PreludeItem::SEMI_BITMAP;
@@ -954,7 +1000,8 @@ int vdl_run_sharded(vdl_ctx *c, vdl_plan *p) {
     }
     int rc = guard(c, [&] {
         if (fold_route(c, p)) { sharded_begin(c, p, 0); return; }
-        if (c->comm && !p->sharded_table.empty()) {
+        const bool ordered = p->order.set && p->order.sharded;
+        if ((c->comm || ordered) && !p->sharded_table.empty()) {
             // rows travel by key range when the plan allows it; otherwise, if its work on the sharded table is a fused front, the
             // survivors are gathered and the rest runs on every rank (the "front" route)
             int ncols = 0;
@@ -962,7 +1009,9 @@ int vdl_run_sharded(vdl_ctx *c, vdl_plan *p) {
             p->ex_allow_folds = true;
             const bool exchange_ok = vdl_exchange_spec(p, p->sharded_table.c_str(), &ncols) == VDL_OK;
             p->ex_allow_folds = false;
-            if (!exchange_ok) {
+            // (an order the exchange route cannot merge is refused here, before a device or a communicator is asked for)
+            if (exchange_ok && ordered) { const std::string why = order_exchange_refusal(p); if (!why.empty()) throw Error(VDL_ERR_UNSUPPORTED, why); }
+            if (!exchange_ok && c->comm) {
                 const bool front = front_route_refusal(p).empty();
                 const bool chain = !front && chain_route(p);
                 if (front || chain || !getenv("VDL_NO_REPLICATE_ROUTE")) {

@@ -1604,6 +1604,30 @@ int vdl_plan_set_order_text(vdl_plan *p, const char *field, const char *heap_col
     return fail("'" + f + "' is not a key of the order set on this plan" + (p->order.nodes.empty() ? " (no order with keys is set)" : ""));
 }
 const char *vdl_plan_order_note(const vdl_plan *p) { return p ? p->order_note.c_str() : ""; }
+int vdl_plan_set_order_sharded(vdl_plan *p, int on) {
+    if (!p) return VDL_ERR_ARG;
+    p->order.sharded = on != 0;
+    return VDL_OK;
+}
+int vdl_order_merge_host(int world, int n_keys, const int64_t *counts, const uint64_t *words, int64_t limit, int64_t *run_out, int64_t *index_out, int64_t *n_out) {
+    if (world < 1 || world > kMaxExWorld || n_keys < 0 || n_keys > kOrdMaxKeys || !counts || limit < 0) return VDL_ERR_ARG;
+    OrdRuns R;
+    R.world = world; R.nk = n_keys;
+    for (int r = 0; r < world; r++) {
+        if (counts[r] < 0) return VDL_ERR_ARG;
+        R.off[r + 1] = R.off[r] + counts[r];
+    }
+    const int64_t N = R.off[world], L = limit > 0 ? std::min(limit, N) : N;
+    if ((N > 0 && n_keys > 0 && !words) || (L > 0 && (!run_out || !index_out))) return VDL_ERR_ARG;
+    int r = 0;
+    for (int64_t j = 0; j < N; j++) {
+        while (j >= R.off[r + 1]) r++;
+        const int64_t place = ord_merge_place(R, words, j);
+        if (place < L) { run_out[place] = r; index_out[place] = j - R.off[r]; }
+    }
+    if (n_out) *n_out = L;
+    return VDL_OK;
+}
 
 int vdl_plan_set_device_outputs(vdl_plan *p, int enabled) {
     if (!p) return VDL_ERR_ARG;

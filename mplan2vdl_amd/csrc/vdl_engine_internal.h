@@ -277,10 +277,24 @@ struct vdl_plan {
         std::vector<int> desc;
         std::vector<std::string> text;   // per key: the heap column whose text order the key's codes stand for (vdl_plan_set_order_text), "" = ordered as int64
         int64_t limit = 0;
+        bool sharded = false;            // vdl_plan_set_order_sharded: vdl_run_sharded* accept the plan and every rank ends with the ordered answer
         int n_text() const { int k = 0; for (const std::string &h : text) k += h.empty() ? 0 : 1; return k; }
     } order;
     std::string order_note;              // what the order step of the last run did
     hipEvent_t order_ev[2] = {nullptr, nullptr};
+    hipEvent_t merge_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // the merged order of a sharded run: around the staging, around the merge
+    // The exchange route of vdl_run_sharded with an order switched on (vdl_comm.cpp sets it around vdl_exchange_finish): the order step
+    // of the tail keeps this rank's first rows as a candidate block and meets the other ranks through these two calls.
+    //   meet(status, own error, L_r, m_r): ONE exchange of {status, candidates, result rows} per rank and run, reached by every rank
+    //       whatever its local phase did; throws on every rank when any rank failed, so that none enters `gather` alone
+    //   gather(send, recv, counts): column k of rank r (counts[r] words) lands at recv[k] + sum(counts[0..r))
+    struct OrderMerge {
+        int rank = 0, world = 1;
+        std::function<std::vector<int64_t>(int64_t, const std::string &, int64_t, int64_t)> meet;
+        std::function<void(const std::vector<const int64_t *> &, const std::vector<int64_t *> &, const std::vector<int64_t> &)> gather;
+    };
+    const OrderMerge *order_merge = nullptr;
+    bool order_inside = false;           // set by vdl_run_sharded* around its own calls of the entry points that refuse an ordered plan
     std::string description;
     std::vector<Output> outs;
     std::vector<Timing> timings;
@@ -414,6 +428,7 @@ struct vdl_plan {
         for (auto &b : out_pinned) if (b.first) (void)hipHostFree(b.first);
         for (hipEvent_t e : stmt_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : order_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : merge_ev) if (e) (void)hipEventDestroy(e);
         for (int k = 0; k < 2; k++) {
             if (ev0[k]) (void)hipEventDestroy(ev0[k]);
             if (ev1[k]) (void)hipEventDestroy(ev1[k]);
@@ -486,11 +501,26 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
 bool use_kscan(const ScanPlan &sp);
 std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
 std::string step_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
-// sharded entry points refuse a plan with an order set
-inline void refuse_order_sharded(const vdl_plan *p) {
-    if (p->order.set)
+// Sharded entry points and a plan with an order set.  merges = the entry point runs the collectives itself (vdl_run_sharded*): it
+// accepts the plan once vdl_plan_set_order_sharded has switched the merged order on.  The others (vdl_run_local, vdl_exchange_begin)
+// leave the collectives to their caller and refuse it either way -- except inside vdl_run_sharded's own calls (order_inside).
+inline void refuse_order_sharded(const vdl_plan *p, bool merges = false) {
+    if (!p->order.set) return;
+    if (!p->order.sharded)
         throw Error(VDL_ERR_UNSUPPORTED, "an order is set on this plan (vdl_plan_set_order): in a sharded run the ranks hold disjoint result rows, and the merge of "
                                          "per-rank top-N results is not built; run it on one GPU with vdl_run, or clear the order");
+    if (!merges && !p->order_inside)
+        throw Error(VDL_ERR_UNSUPPORTED, "an order is set on this plan and switched on for sharded runs (vdl_plan_set_order_sharded), but this entry point leaves the "
+                                         "collectives to its caller: the merge of the ranks' ordered rows lives in vdl_run_sharded; run the plan through "
+                                         "vdl_run_sharded, or clear the order");
+}
+// the exchange route under a switched-on order merges per-rank top-N candidates: "" = this order can be served, else why not
+inline std::string order_exchange_refusal(const vdl_plan *p) {
+    if (!p->order.set || !p->order.sharded || (p->order.limit > 0 && p->order.limit <= kOrdTopMax)) return "";
+    return "the order set on this plan has limit " + std::to_string(p->order.limit) + (p->order.limit == 0 ? " (all rows)" : "") +
+           ": on the exchange route of a sharded run the ranks hold disjoint result rows and only a limit from 1 to " + std::to_string(kOrdTopMax) +
+           " is merged (per-rank top-N candidates, one gather); a full order would have to gather every result row.  Run it on one GPU with vdl_run, or set a limit <= " +
+           std::to_string(kOrdTopMax);
 }
 // the order step for results that lie on the host (vdl_engine.cpp): checks the outputs' lengths, vdl_order_host + a permute of every output
 // (text keys: their ranks come from the device index through one small launch and a fetch, so `c` needs its device then)

@@ -67,6 +67,8 @@ void general_finalize(vdl_ctx *c, vdl_plan *p, const int64_t *dev_words) {
         over[p->cut_folds[k]] = v;
     }
     GenExec g(c, p);
+    // inside vdl_run_sharded* every rank holds the whole result here and orders it; a caller's own vdl_finalize is left as it was
+    g.ordering = p->order.set && p->order.sharded && p->order_inside;
     g.run_nodes(p->prog.outputs, &over);
 }
 
@@ -140,6 +142,7 @@ void chain_build_set(vdl_ctx *c, vdl_plan *p, size_t k, const BufP &positions, i
 void chain_run_everywhere(vdl_ctx *c, vdl_plan *p) {
     need_device(c);
     GenExec g(c, p);
+    g.ordering = p->order.set && p->order.sharded;         // the whole result on every rank: ordered as vdl_run orders it
     g.run_nodes(p->prog.outputs, &p->chain.sets);
 }
 
@@ -321,6 +324,10 @@ int vdl_exchange_finish(vdl_ctx *c, vdl_plan *p, const void *dev_recv, int64_t n
         ex.active = false;
         if (p->chain.stage == 2) over.insert(p->chain.sets.begin(), p->chain.sets.end());
         GenExec g(c, p);
+        // an order switched on for sharded runs: the chain route's second stage ends with the whole result on every rank and orders it
+        // as vdl_run does; the exchange route proper holds this rank's rows of it, and the order step merges the ranks' first rows
+        if (p->chain.stage == 2) g.ordering = p->order.set && p->order.sharded;
+        else if (p->chain.stage == 0 && p->order_merge) { g.ordering = true; g.merge = p->order_merge; }
         g.run_nodes(p->prog.outputs, &over);
         if (p->chain.stage == 1) chain_collect(g, p);
     });

@@ -1649,6 +1649,12 @@ struct GenExec {
             HIP_CHECK(hipEventElapsedTime(&ms, p->order_ev[0], p->order_ev[1]));
             p->timings.push_back({"timeInMicrosecondsForOrder", (double)ms * 1e3});
         }
+        if (merge_timed) {                                             // staging + merge: two spans with the collective between them
+            float stage_ms = 0, merge_ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&stage_ms, p->merge_ev[0], p->merge_ev[1]));
+            HIP_CHECK(hipEventElapsedTime(&merge_ms, p->merge_ev[2], p->merge_ev[3]));
+            p->timings.push_back({"timeInMicrosecondsForOrderMerge", ((double)stage_ms + (double)merge_ms) * 1e3});
+        }
     }
 
     // ---- the order step (vdl_plan_set_order): every output permuted by ONE order over the key outputs and cut to the limit --------
@@ -1741,6 +1747,7 @@ struct GenExec {
     }
 
     void order_outputs() {
+        if (merge) { order_outputs_merged(); return; }
         ordering = false;
         std::vector<size_t> keys;
         const int64_t m = order_resolve(p, keys);
@@ -1799,6 +1806,128 @@ struct GenExec {
             o.dev = nullptr; o.dev_keep = nullptr; o.big = nullptr; o.big_n = 0; o.vals.clear();
             out_override = k;
             copy_out(o, cut[k], (size_t)L);
+        }
+        out_override = SIZE_MAX;
+        kept.clear();
+    }
+
+    // ---- the same step on the exchange route of a sharded run (vdl_plan_set_order_sharded; the collectives: vdl_comm.cpp) --------
+    // This rank holds m_r result rows of the whole result, the ranks' rows one after the other.  Local: the first L_r = min(limit, m_r)
+    // rows by the selection above, kept as an index list; ONE launch writes them as a candidate block (K order words, every output).
+    // Then: {status, L_r, m_r} of every rank -- whatever failed up to here fails on every rank now, before the data travels --, one
+    // gather of the blocks, and k_ord_merge writes the first L = min(limit, sum m_r) rows of every output: the same rows on every rank.
+    const vdl_plan::OrderMerge *merge = nullptr;
+    bool merge_timed = false;
+    void order_outputs_merged() {
+        ordering = false;
+        const vdl_plan::OrderMerge &M = *merge;
+        const size_t n_out = p->outs.size();
+        int64_t m = 0, Lr = 0;
+        int nk = 0;
+        BufP block;
+        std::string note, own;
+        int64_t status = VDL_OK;
+        try {
+            std::vector<size_t> keys;
+            m = order_resolve(p, keys);
+            Lr = std::min<int64_t>(p->order.limit, m);
+            nk = (int)keys.size();
+            if (p->order.limit < 1 || p->order.limit > kOrdTopMax) throw Error(VDL_ERR_UNSUPPORTED, order_exchange_refusal(p));
+            // a text key's ranks are only comparable across the ranks when every rank holds the same heap
+            for (size_t k = 0; k < keys.size(); k++) {
+                const std::string &heap = p->order.text[k];
+                if (!heap.empty() && !p->sharded_table.empty() && heap.compare(0, p->sharded_table.size() + 1, p->sharded_table + ".") == 0)
+                    throw Error(VDL_ERR_UNSUPPORTED, "order key '" + p->outs[keys[k]].name + "' is text over heap '" + heap + "', a column of the sharded table '" +
+                                                     p->sharded_table + "': every rank holds its own rows' heap, so the ranks' collation ranks cannot be merged; "
+                                                     "text keys of a sharded run need a replicated heap");
+            }
+            kept.resize(n_out);
+            for (size_t k = 0; m > 0 && k < n_out; k++) {              // a result a statement assembled on the host joins the others
+                Output &o = p->outs[k];
+                if (o.dev) continue;
+                kept[k] = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+                HIP_CHECK(hipMemcpyAsync(kept[k]->p, o.vals.data(), sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, s));
+                HIP_CHECK(hipStreamSynchronize(s));                    // (pageable source)
+                o.dev = (const int64_t *)kept[k]->p;
+            }
+            const int n_text = p->order.n_text();
+            for (size_t k = 0; n_text > 0 && m > 0 && k < keys.size(); k++)
+                if (!p->order.text[k].empty()) collation_ensure(c, p->order.text[k], p, "order key '" + p->outs[keys[k]].name + "'");
+            if (!p->order_ev[1]) { HIP_CHECK(hipEventCreate(&p->order_ev[0])); HIP_CHECK(hipEventCreate(&p->order_ev[1])); }
+            for (hipEvent_t &e : p->merge_ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+            HIP_CHECK(hipEventRecord(p->order_ev[0], s));
+            OrdKeys K;
+            K.n = nk;
+            for (int k = 0; k < K.n; k++) { K.key[k] = p->outs[keys[(size_t)k]].dev; K.flip[k] = order_flip(p->order.desc[(size_t)k]); }
+            std::vector<BufP> text_ranks;
+            if (n_text > 0 && m > 0) {
+                text_ranks = order_text_ranks(c, p, std::vector<const int64_t *>(K.key, K.key + K.n), m, s);
+                for (int k = 0; k < K.n; k++) if (text_ranks[(size_t)k]) K.key[k] = (const int64_t *)text_ranks[(size_t)k]->p;
+            }
+            BufP index;                                                // null: the first L_r rows as they stand
+            note = "topn m=" + std::to_string(m) + " rows=" + std::to_string(Lr) + " rounds=0 candidates=" + std::to_string(Lr) + " digits_used_up=0";
+            if (K.n > 0 && m > 1) index = order_select(K, m, Lr, note);
+            if (n_text > 0) note += " text_keys=" + std::to_string(n_text);
+            HIP_CHECK(hipEventRecord(p->order_ev[1], s));
+            order_timed = true;
+            // the candidate block, column-major: the order words, then the outputs
+            HIP_CHECK(hipEventRecord(p->merge_ev[0], s));
+            block = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(((int64_t)nk + (int64_t)n_out) * Lr, 1));
+            const size_t ncols = (size_t)nk + n_out;
+            for (size_t c0 = 0; Lr > 0 && c0 < ncols; c0 += kOrdBlockCols) {
+                OrdBlock B;
+                for (size_t col = c0; col < ncols && B.n < kOrdBlockCols; col++, B.n++) {
+                    if (col < (size_t)nk) { B.src[B.n] = K.key[col]; B.flip[B.n] = K.flip[col]; }
+                    else { B.src[B.n] = p->outs[col - (size_t)nk].dev; B.flip[B.n] = 0; }
+                }
+                HIP_CHECK(launch_order_block(B, index ? (const int64_t *)index->p : nullptr, Lr, (int64_t *)block->p + (int64_t)c0 * Lr, s));
+            }
+            HIP_CHECK(hipEventRecord(p->merge_ev[1], s));
+            HIP_CHECK(hipStreamSynchronize(s));                        // the block goes to the collective; the kept outputs and the ranks may go
+        } catch (const Error &e) { status = e.code; own = e.what(); }
+        catch (const std::exception &e) { status = VDL_ERR_ARG; own = e.what(); }
+        if (status != VDL_OK) { Lr = 0; m = 0; }
+        const std::vector<int64_t> all = M.meet(status, own, Lr, m);   // throws on every rank when any rank failed
+        OrdRuns R;
+        R.world = M.world; R.nk = nk;
+        std::vector<int64_t> cnt((size_t)M.world);
+        int64_t total = 0;
+        for (int r = 0; r < M.world; r++) {
+            cnt[(size_t)r] = all[(size_t)r * 3 + 1];
+            if (cnt[(size_t)r] < 0 || cnt[(size_t)r] > kOrdTopMax || all[(size_t)r * 3 + 2] < cnt[(size_t)r])
+                throw Error(VDL_ERR_DEVICE, "sharded order: rank " + std::to_string(r) + " reports " + std::to_string(cnt[(size_t)r]) + " candidate(s) of " +
+                                            std::to_string(all[(size_t)r * 3 + 2]) + " row(s)");
+            R.off[r + 1] = R.off[r] + cnt[(size_t)r];
+            total += all[(size_t)r * 3 + 2];
+        }
+        const int64_t N = R.off[M.world], L = std::min<int64_t>(p->order.limit, total);
+        const size_t ncols = (size_t)nk + n_out;
+        BufP runs = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>((int64_t)ncols * N, 1));
+        std::vector<const int64_t *> send;
+        std::vector<int64_t *> recv;
+        for (size_t col = 0; col < ncols; col++) {
+            send.push_back((const int64_t *)block->p + (int64_t)col * Lr);
+            recv.push_back((int64_t *)runs->p + (int64_t)col * N);
+        }
+        if (ncols > 0) M.gather(send, recv, cnt);
+        HIP_CHECK(hipEventRecord(p->merge_ev[2], s));
+        std::vector<BufP> cut(n_out);
+        for (size_t k0 = 0; L > 0 && k0 < n_out; k0 += kOrdGatherMax) {
+            OrdGather G;
+            for (size_t k = k0; k < n_out && G.n < kOrdGatherMax; k++, G.n++) {
+                cut[k] = dev_alloc(c, sizeof(int64_t) * (size_t)L);
+                G.src[G.n] = (const int64_t *)runs->p + (int64_t)((size_t)nk + k) * N; G.dst[G.n] = (int64_t *)cut[k]->p;
+            }
+            HIP_CHECK(launch_order_merge(R, G, (const uint64_t *)runs->p, L, s));
+        }
+        HIP_CHECK(hipEventRecord(p->merge_ev[3], s));
+        merge_timed = true;
+        p->order_note = note + " | merge world=" + std::to_string(M.world) + " candidates=" + std::to_string(N) + " rows=" + std::to_string(L);
+        for (size_t k = 0; k < n_out; k++) {
+            Output &o = p->outs[k];
+            o.dev = nullptr; o.dev_keep = nullptr; o.big = nullptr; o.big_n = 0; o.vals.clear();
+            out_override = k;
+            if (L > 0) copy_out(o, cut[k], (size_t)L);
         }
         out_override = SIZE_MAX;
         kept.clear();

@@ -325,6 +325,50 @@ hipError_t launch_order_close(const int64_t *key, uint64_t flip, const uint64_t 
 // n <= kOrdTopMax + kOrdBoundary candidate rows `pos`: index_out[r] = the candidate of rank r < keep under (keys, position); staged: K.n * n words
 hipError_t launch_order_rank(const OrdKeys &K, const int64_t *pos, int64_t n, int64_t keep, uint64_t *staged, int64_t *index_out, hipStream_t s);
 hipError_t launch_order_gather(const OrdGather &G, const int64_t *index, int64_t n, hipStream_t s);      // dst[o][i] = src[o][index[i]], i < n
+// ---- the merged order of a sharded run (DESIGN.md section 5.9 "sharded runs"): every rank's first rows, gathered, are `world` sorted runs ----
+// Candidate block of one rank: column c < B.n of the n chosen rows, column-major -- out[c * n + i] = src[c][index[i]] ^ flip[c] (index
+// null = the rows as they stand).  The K order words (flip = the key's) stand first, every output's value (flip 0) behind them.
+constexpr int kOrdBlockCols = kOrdMaxKeys + kOrdGatherMax;
+struct OrdBlock { int n = 0; const int64_t *src[kOrdBlockCols] = {}; uint64_t flip[kOrdBlockCols] = {}; };
+hipError_t launch_order_block(const OrdBlock &B, const int64_t *index, int64_t n, int64_t *out, hipStream_t s);
+// The gathered runs: run r is candidates [off[r], off[r + 1]) of N = off[world], its order words at w[k * N + j], k < nk, ascending
+// under (u_1, .., u_K) with ties in the run's own order.
+struct OrdRuns { int world = 0, nk = 0; int64_t off[kMaxExWorld + 1] = {}; };
+// The rule, shared by the kernel and vdl_order_merge_host: candidate j of run r takes the place
+//     (j - off[r]) + sum over runs q < r of |{x in q : x <= j}| + sum over runs q > r of |{x in q : x < j}|
+// -- each count one binary search under the full comparator -- which is its rank under (u_1, .., u_K, run, place in the run): the
+// order of section 5.9 over the ranks' results one after the other.  Places are a permutation of 0 .. N-1.
+VDL_HD inline int64_t ord_merge_place(const OrdRuns &R, const uint64_t *w, int64_t j) {
+    const int64_t N = R.off[R.world];
+    uint64_t mine[kOrdMaxKeys];
+#pragma unroll
+    for (int k = 0; k < kOrdMaxKeys; k++) mine[k] = k < R.nk ? w[(int64_t)k * N + j] : 0;
+    int r = 0;
+    int64_t first = 0;                                                  // (off[] is only ever indexed by the loop counter: it stays in the kernel's arguments)
+    for (int q = 1; q < R.world; q++)
+        if (j >= R.off[q]) { r = q; first = R.off[q]; }                 // the last run that begins at or before j: the one that holds it
+    int64_t place = j - first;
+    for (int q = 0; q < R.world; q++) {
+        int64_t lo = R.off[q], hi = q == r ? lo : R.off[q + 1];
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            bool less = false, decided = false;
+#pragma unroll
+            for (int k = 0; k < kOrdMaxKeys; k++) {
+                if (k < R.nk && !decided) {
+                    const uint64_t o = w[(int64_t)k * N + mid];
+                    less = o < mine[k];
+                    decided = o != mine[k];
+                }
+            }
+            if (decided ? less : q < r) lo = mid + 1; else hi = mid;
+        }
+        place += lo - R.off[q];
+    }
+    return place;
+}
+// one lane per candidate: a candidate whose place is below `keep` writes its row of every output, dst[o][place] = src[o][j]
+hipError_t launch_order_merge(const OrdRuns &R, const OrdGather &G, const uint64_t *w, int64_t keep, hipStream_t s);
 // full order: out[i] = u(key[perm[i]]) - umin (perm null = identity) whole (half 0) / low 32 bits (1) / high 32 bits (2); out[i] = perm[order[i]]
 hipError_t launch_order_sortkey(const int64_t *key, uint64_t flip, const int64_t *perm, int64_t m, uint64_t umin, int half, int64_t *out, hipStream_t s);
 hipError_t launch_order_compose(const int64_t *perm, const int64_t *order, int64_t m, int64_t *out, hipStream_t s);

@@ -205,6 +205,31 @@ __global__ __launch_bounds__(kOrdBlock) void k_ord_gather(OrdGather G, const int
     G.dst[blockIdx.y][i] = G.src[blockIdx.y][index[i]];
 }
 
+// ---- sharded runs: the candidate block a rank contributes, and the merge of the gathered blocks ----
+// blockIdx.y = column of the block: an order word or an output, the chosen rows in the rank's sorted order
+__global__ __launch_bounds__(kOrdBlock) void k_ord_block(OrdBlock B, const int64_t *__restrict__ index, int64_t n, int64_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kOrdBlock + threadIdx.x;
+    if (i >= n) return;
+    const int c = blockIdx.y;
+    out[(int64_t)c * n + i] = (int64_t)((uint64_t)B.src[c][index ? index[i] : i] ^ B.flip[c]);
+}
+
+// The merge (ord_merge_place, vdl_kernels.h): one lane per gathered candidate, no atomics, nothing comes back to the host.  At most
+// world * kOrdTopMax candidates: a latency-bound kernel of some hundred waves whose searches read K columns of at most a few MB --
+// L2-resident after the first touch.  One wave per block spreads those waves over the CUs (128 blocks of 256 would leave half the chip
+// idle at eight ranks).  The runs' first words are NOT staged in LDS: eight runs of 4096 words are 256 KiB, more than a CU's 160 KiB,
+// and a sampled top of each search tree would save two or three of twelve dependent L2 reads per run for one more barrier and a
+// fill that every block repeats.
+constexpr int kOrdMergeBlock = 64;
+__global__ __launch_bounds__(kOrdMergeBlock) void k_ord_merge(OrdRuns R, OrdGather G, const uint64_t *__restrict__ w, int64_t keep) {
+    const int64_t N = R.off[R.world];
+    const int64_t j = (int64_t)blockIdx.x * kOrdMergeBlock + threadIdx.x;
+    if (j >= N) return;
+    const int64_t place = ord_merge_place(R, w, j);
+    if (place >= keep) return;
+    for (int o = 0; o < G.n; o++) G.dst[o][place] = G.src[o][j];
+}
+
 // full order: the sort key of the row that stands at place i so far -- u - umin whole (half 0), its low (1) or high (2) 32 bits
 __global__ __launch_bounds__(kOrdBlock) void k_ord_sortkey(const int64_t *__restrict__ key, uint64_t flip, const int64_t *__restrict__ perm, int64_t m,
                                                            uint64_t umin, int half, int64_t *__restrict__ out) {
@@ -255,6 +280,23 @@ hipError_t launch_order_gather(const OrdGather &G, const int64_t *index, int64_t
     if (n <= 0 || G.n <= 0) return hipSuccess;
     if (G.n > kOrdGatherMax) return hipErrorInvalidValue;
     k_ord_gather<<<dim3((unsigned)((n + kOrdBlock - 1) / kOrdBlock), (unsigned)G.n), kOrdBlock, 0, s>>>(G, index, n);
+    return launch_status();
+}
+hipError_t launch_order_block(const OrdBlock &B, const int64_t *index, int64_t n, int64_t *out, hipStream_t s) {
+    (void)hipGetLastError();
+    if (n <= 0 || B.n <= 0) return hipSuccess;
+    if (B.n > kOrdBlockCols || !out) return hipErrorInvalidValue;
+    k_ord_block<<<dim3((unsigned)((n + kOrdBlock - 1) / kOrdBlock), (unsigned)B.n), kOrdBlock, 0, s>>>(B, index, n, out);
+    return launch_status();
+}
+hipError_t launch_order_merge(const OrdRuns &R, const OrdGather &G, const uint64_t *w, int64_t keep, hipStream_t s) {
+    (void)hipGetLastError();
+    if (R.world < 1 || R.world > kMaxExWorld || R.nk < 0 || R.nk > kOrdMaxKeys || G.n < 0 || G.n > kOrdGatherMax || R.off[0] != 0) return hipErrorInvalidValue;
+    for (int r = 0; r < R.world; r++) if (R.off[r + 1] < R.off[r]) return hipErrorInvalidValue;
+    const int64_t N = R.off[R.world];
+    if (N <= 0 || keep <= 0 || G.n == 0) return hipSuccess;
+    if (!w && R.nk > 0) return hipErrorInvalidValue;
+    k_ord_merge<<<(unsigned)((N + kOrdMergeBlock - 1) / kOrdMergeBlock), kOrdMergeBlock, 0, s>>>(R, G, w, keep);
     return launch_status();
 }
 hipError_t launch_order_sortkey(const int64_t *key, uint64_t flip, const int64_t *perm, int64_t m, uint64_t umin, int half, int64_t *out, hipStream_t s) {

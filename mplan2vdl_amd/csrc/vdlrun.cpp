@@ -25,7 +25,9 @@
 // --order-by FIELD[:asc|:desc][:text[=HEAP]],... names outputs by their full field name or their tmpN key, --limit N keeps the first N
 // rows (vdl_plan_set_order); :text orders the key by its strings (vdl_plan_set_order_text) over HEAP, or over table.col.heap for a
 // field named col__table__col, and --data uploads that heap too.  The reply has the same shape with shorter, ordered lists, so
-// resolve.py decodes it untouched.  Not with --gpus: the ranks hold disjoint result rows and the merge of per-rank top-N results is not built.
+// resolve.py decodes it untouched.  With --gpus only together with --order-sharded (vdl_plan_set_order_sharded): the ranks then run, every
+// rank ends with the whole ordered answer -- on the exchange route the ranks' first rows are merged on the device, --limit 1 .. 4096 --,
+// the rank replies are marked replicated and ONE of them is printed.  Without it --gpus refuses an order before any rank starts.
 //   ... | vdlrun --jit --batch b.vdl --batch c.vdl ...                             several programs, one pass where they can share it
 // --batch FILE (repeatable; needs --jit or --jit-tune): the program on stdin and the programs in the files run as ONE vdl_run_batch --
 // those that differ in their literals alone share one scan of the columns, the others run alone inside the same call -- and one reply
@@ -188,7 +190,7 @@ bool read_reply(const std::string &path, Reply &r) {
 struct Options {
     int64_t rows = 60175;           // SF0.01 lineitem, /root/reference/tests/tpchnoorder/bounds.csv:59
     uint64_t seed = 0x5EED0006ULL;
-    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0;
+    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0;
     std::string data_dir, shard = "lineitem";
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
@@ -262,6 +264,7 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
             if ((rc = vdl_plan_set_order(one, (int)fields.size(), fields.data(), o.order_desc.data(), o.limit))) return die(ctx, "vdl_plan_set_order", rc);
             for (size_t q = 0; q < o.order_heaps.size(); q++)
                 if (!o.order_heaps[q].empty() && (rc = vdl_plan_set_order_text(one, o.order_fields[q].c_str(), o.order_heaps[q].c_str()))) return die(ctx, "vdl_plan_set_order_text", rc);
+            if (o.order_sharded) vdl_plan_set_order_sharded(one, 1);
         }
         plans.push_back(one);
         if (o.describe) break;
@@ -346,6 +349,7 @@ int main(int argc, char **argv) {
         else if (a == "--shard" && i + 1 < argc) o.shard = argv[++i];
         else if (a == "--batch" && i + 1 < argc) o.batch_files.push_back(argv[++i]);
         else if (a == "--order-by" && i + 1 < argc && parse_order_by(argv[i + 1], o)) i++;
+        else if (a == "--order-sharded") o.order_sharded = 1;
         else if (a == "--limit" && i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]) &&
                  std::strlen(argv[i + 1]) <= 18) o.limit = std::atoll(argv[++i]);
         else if (a == "--no-fuse") o.fuse = 0;
@@ -357,7 +361,7 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--batch FILE ...] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }
@@ -369,7 +373,7 @@ int main(int argc, char **argv) {
     std::string text((std::istreambuf_iterator<char>(std::cin)), std::istreambuf_iterator<char>());
     bool sharded = false;
     for (int i = 1; i < argc; i++) sharded = sharded || std::string(argv[i]) == "--gpus";
-    if (sharded && !o.describe && (!o.order_fields.empty() || o.limit > 0)) {
+    if (sharded && !o.describe && !o.order_sharded && (!o.order_fields.empty() || o.limit > 0)) {
         std::fprintf(stderr, "vdlrun: --order-by / --limit are not served with --gpus: the ranks hold disjoint result rows and the merge of per-rank "
                              "top-N results is not built; run the ordered query on one GPU\n");
         return 3;

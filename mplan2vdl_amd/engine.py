@@ -129,7 +129,7 @@ class Plan:
         to the plan until its next run."""
         self._e._check(self._e._L.vdl_plan_set_device_outputs(self._h, int(bool(enabled))))
 
-    def set_order(self, keys, limit=0):
+    def set_order(self, keys, limit=0, sharded=False):
         """ORDER BY / LIMIT on the device: `keys` is a list of (field, descending) pairs (a bare string = ascending), a field
         being an output's full name or its "tmpN" key; `limit` 0 = all rows.  Every output of `run()` then comes back permuted
         by that one order (signed int64 keys, ties in the order of the unordered result) and cut to the limit.  No keys and
@@ -137,7 +137,10 @@ class Plan:
         alphabetical.  A third element, (field, descending, heap), declares the key as text over that heap column
         ("part.p_brand.heap"): it is then ordered by the strings themselves -- unsigned bytes, a prefix before its extensions,
         equal strings at different offsets tie -- through the heap's collation index (`Engine.build_collation`; built by the
-        first run that needs it otherwise).  The heap must be in the catalog when the plan runs."""
+        first run that needs it otherwise).  The heap must be in the catalog when the plan runs.
+        `sharded=True` switches the merged order of sharded runs on (vdl_plan_set_order_sharded): `run_sharded` and the
+        `run_sharded_begin` / `_end` pair then accept the plan and every rank ends with the same ordered answer; on the exchange
+        route the limit must be 1..4096.  Every call passes it down, so a later plain set_order(..) switches it off again."""
         triples = []
         for k in keys:
             if isinstance(k, (str, bytes)):
@@ -149,6 +152,7 @@ class Plan:
         fields = (ctypes.c_char_p * max(n, 1))(*[enc(f) for f, _, _ in triples])
         desc = (ctypes.c_int * max(n, 1))(*[int(d) for _, d, _ in triples])
         self._e._check(self._e._L.vdl_plan_set_order(self._h, n, fields, desc, int(limit)))
+        self._e._check(self._e._L.vdl_plan_set_order_sharded(self._h, int(bool(sharded))))
         for f, _, heap in triples:
             if heap is not None:
                 self.set_order_text(f, heap)
@@ -250,7 +254,8 @@ class Plan:
     # ---- multi-GPU behind the C ABI (Engine.comm_init_*): the collectives happen inside libvdl ----
     def run_sharded(self, as_numpy=False):
         """Local phase over this rank's rows, collectives, finalisation (vdl_run_sharded).  Fold plans: every rank gets the
-        full result; plans with a Partition: this rank's slice (the ranks' slices concatenate in rank order)."""
+        full result; plans with a Partition: this rank's slice (the ranks' slices concatenate in rank order) -- or, with
+        set_order(.., sharded=True), the same ordered and cut rows on every rank."""
         self._e._check(self._e._L.vdl_run_sharded(self._e._c, self._h))
         return self._collect(as_numpy)
 
@@ -312,6 +317,28 @@ def order_host(keys, descending, limit=0):
     if rc != _lib.VDL_OK:
         raise VdlError(rc, "vdl_order_host: bad argument")
     return out
+
+
+def order_merge_host(counts, words, limit=0):
+    """vdl_order_merge_host: the merge of a sharded run's ordered candidates, device-free.  `counts[r]` candidates of rank r, one
+    run after the other; `words` a list of K uint64 arrays over all N = sum(counts) candidates (order words u = key ^ flip), each
+    run ascending under them with ties in its own order.  Returns (run, index) int64 arrays of the first min(limit or N, N) rows
+    of the order (u_1, .., u_K, run, index)."""
+    L = _lib.load()
+    cnt = np.ascontiguousarray(counts, dtype=np.int64)
+    n = int(cnt.sum())
+    cols = [np.ascontiguousarray(w, dtype=np.uint64) for w in words]
+    if any(len(c) != n for c in cols):
+        raise ValueError("every word column holds sum(counts) values")
+    w = np.ascontiguousarray(np.concatenate(cols)) if cols else np.zeros(0, np.uint64)
+    keep = min(limit, n) if limit > 0 else n
+    run, idx, got = np.empty(keep, np.int64), np.empty(keep, np.int64), ctypes.c_int64()
+    p64 = ctypes.POINTER(ctypes.c_int64)
+    rc = L.vdl_order_merge_host(len(cnt), len(cols), cnt.ctypes.data_as(p64), w.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(limit),
+                                run.ctypes.data_as(p64), idx.ctypes.data_as(p64), ctypes.byref(got))
+    if rc != _lib.VDL_OK or got.value != keep:
+        raise VdlError(rc, "vdl_order_merge_host: bad argument")
+    return run, idx
 
 
 def collate_host(heap, codes):
