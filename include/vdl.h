@@ -230,10 +230,28 @@ int  vdl_run(vdl_ctx *ctx, vdl_plan *plan);
  * vdl_batch_jit_check: like vdl_plan_jit_check, groups the plans and builds the batch kernels against the columns registered now
  * without a device, and fills the notes.
  * With vdl_plan_set_profiling every plan of a batch carries ONE timing, "timeInMicrosecondsForBatchedScan_<kernel>": the whole batch
- * kernel's time, under a label of its own so that it is never read as a per-query figure. */
+ * kernel's time, under a label of its own so that it is never read as a per-query figure.
+ *
+ * Grouped batches (opt-in: vdl_set_batch_grouped(ctx, 1), or VDL_BATCH_GROUPED=1 in the environment when the context opens; off, every
+ * grouped plan runs alone as above).  A plan whose ONE scan is a grouped scan over table columns (no second scan, no derived columns, no
+ * prelude, not known to be empty) shares a batch with plans of the same columns and the same generated code under run-time bounds --
+ * pivots, key and aggregates are part of that code; grouped and global plans never mix.  A row's group and aggregate terms do not depend
+ * on anybody's bounds, only the SET of plans it passes does: the kernel keeps one table per non-empty set (2^K - 1 pass-class tables per
+ * replica) in LDS, issues per row the 1 + aggregates atomics the unbatched scan issues, and folds the classes into the plans' tables once
+ * per block.  With words = pivots x (1 + aggregates), a batch of K plans needs R x (((2^K - 1) x words) | 1) + 256 + aggregates + 1 words
+ * within 8192 (64 KiB), R the largest power of two <= 8 that fits; the widest K of 4, 3, 2 is taken whose R is at least min(the
+ * replicas the scan has alone, 2).  TPC-H Q1 (32 pivots, 8 words each): K = 4 at R = 2.  A scan whose table leaves no room for three
+ * tables runs alone ("its group table leaves no room in LDS for a second plan's classes").  Only the eager tile form is batched (tuned:
+ * at 2, 3, 4 row pairs per lane); the name carries ",grouped" and ",batch<K>,rtb>".  When the rows ONE plan keeps carry group keys
+ * outside the pivots, that plan alone is rerun inside the call, on the general path at once -- its note becomes "alone: rerun after batch <b>:
+ * <reason>" -- and the other slots keep their answers.  VDL_BATCH_WIDTH=k (k >= 2) caps the width of every batch, grouped or global.
+ * vdl_plan_batch_code_bytes: the code size of the batch kernel that served the plan in the last vdl_run_batch / vdl_batch_jit_check,
+ * 0 when none did. */
 int  vdl_run_batch(vdl_ctx *ctx, vdl_plan *const *plans, int n);
 const char *vdl_plan_batch_note(const vdl_plan *plan);
 int  vdl_batch_jit_check(vdl_ctx *ctx, vdl_plan *const *plans, int n);
+int  vdl_set_batch_grouped(vdl_ctx *ctx, int on);
+int64_t vdl_plan_batch_code_bytes(const vdl_plan *plan);
 
 int  vdl_n_outputs(const vdl_plan *plan);
 /* k-th output in program order: `name` is the output field (resolve.py:64-78 splits it on

@@ -1075,6 +1075,7 @@ int vdl_open(vdl_ctx **out, int device) {
     vdl_ctx *c = new vdl_ctx();
     int rc = guard(c, [&] {
         c->device = device;
+        { const char *g = getenv("VDL_BATCH_GROUPED"); c->batch_grouped = g && *g && *g != '0'; }
         if (device >= 0) {
             int count = 0;
             if (hipGetDeviceCount(&count) != hipSuccess || device >= count)
@@ -1664,13 +1665,17 @@ int vdl_plan_set_profiling(vdl_plan *p, int enabled) {
     return VDL_OK;
 }
 
-int vdl_run(vdl_ctx *c, vdl_plan *p) {
+// abandoned: the fused plan is known not to hold for this data (a grouped batch found keys outside the pivots: run_batches) -- the
+// general path at once, with that reason, instead of a fused pass that would find the same rows
+static int run_plan(vdl_ctx *c, vdl_plan *p, const std::string *abandoned) {
     if (!c || !p) return VDL_ERR_ARG;
     return guard(c, [&] {
         need_device(c);
         p->order_note.clear();
         p->batch_note.clear();
-        if (p->use_fusion && p->fused.ok) {
+        p->batch_code_bytes = 0;
+        if (abandoned) p->fallback_note = *abandoned;
+        else if (p->use_fusion && p->fused.ok) {
             const int64_t nw = plan_words(p, nullptr, nullptr);
             if (!p->words || p->words_cap < nw) { p->words = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(nw, 1)); p->words_cap = nw; }
             try {
@@ -1699,11 +1704,14 @@ int vdl_run(vdl_ctx *c, vdl_plan *p) {
     });
 }
 
+int vdl_run(vdl_ctx *c, vdl_plan *p) { return run_plan(c, p, nullptr); }
+
 // ---- batched runs: plans that differ in their literals alone share one pass over the columns -----------
 namespace {
 // Groups the plans (vdl_specialise.cpp says which may share a scan and why not), cuts every group into batches of at most
-// batch_cap plans and runs each batch as one scan; every other plan runs alone through vdl_run.  check_only (vdl_batch_jit_check):
-// the grouping, the builds and the notes, nothing loaded or run.
+// batch_cap plans (grouped scans: batch_group_cap) and runs each batch as one scan; every other plan runs alone through vdl_run.
+// A plan of a grouped batch whose rows carry keys outside the pivots is rerun alone inside the call; its partners keep their answers.
+// check_only (vdl_batch_jit_check): the grouping, the builds and the notes, nothing loaded or run.
 void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
     std::vector<BatchMember> members;
     members.reserve((size_t)n);
@@ -1711,7 +1719,8 @@ void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
     for (int i = 0; i < n; i++) {
         vdl_plan *p = plans[i];
         p->batch_note.clear();
-        alone[(size_t)i] = batch_alone_reason(p);
+        p->batch_code_bytes = 0;
+        alone[(size_t)i] = batch_alone_reason(p, c->batch_grouped);
         if (!alone[(size_t)i].empty()) continue;
         BatchMember m;
         m.index = i;
@@ -1734,7 +1743,8 @@ void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
             alone[(size_t)g[0]->index] = same_cols ? "its filter shapes differ from every other plan's" : members.size() > 1 ? "no other plan scans the same columns" : "no other plan of the call can share a scan";
             continue;
         }
-        const size_t cap = (size_t)batch_cap(g[0]->desc->nagg);
+        const size_t cap = g[0]->grouped ? (size_t)batch_group_cap(*g[0]->desc, g[0]->replicas_alone) : (size_t)batch_cap_asked(g[0]->desc->nagg);
+        if (cap < 2 && g[0]->grouped) { for (BatchMember *m : g) alone[(size_t)m->index] = "its group table leaves no room in LDS for a second plan's classes"; continue; }
         if (cap < 2) { for (BatchMember *m : g) alone[(size_t)m->index] = "a scan of " + std::to_string(m->desc->nagg) + " aggregates leaves no room for a second plan's accumulators"; continue; }
         for (size_t at = 0; at < g.size(); at += cap) {
             const size_t k = std::min(cap, g.size() - at);
@@ -1756,47 +1766,68 @@ void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
             tune = tune && p->jit_tune;
             profiling = profiling || p->profiling;
             if (check_only) continue;
-            const int64_t nw = ms[(size_t)q]->desc->nagg + 1;
+            const MScanDesc &d = *ms[(size_t)q]->desc;
+            const bool grouped = ms[(size_t)q]->grouped;
+            const int64_t nw = grouped ? d.pcount * (d.nagg + 1) + 1 : d.nagg + 1;
             if (!p->words || p->words_cap < nw) { p->words = dev_alloc(c, sizeof(int64_t) * (size_t)nw); p->words_cap = nw; }
             outs[q] = (int64_t *)p->words->p;
             p->order_note.clear();
             if (!p->bound || p->bound_version != c->binding_version()) {
-                // finalize_begin / finalize_end read the plan's word layout: one global scan, its words first.  The plan stays unbound -- its
-                // own kernels are built when it is run alone
+                // finalize_begin / finalize_end read the plan's word layout: one global scan, its words first -- or one grouped scan, whose
+                // pivots and aggregate count they take from its descriptor.  The plan stays unbound -- its own kernels are built when it is
+                // run alone
                 p->bound = false;
                 p->reduce_ops.clear();
                 p->n_words = plan_words(p, &p->reduce_ops, nullptr);
-                p->word_offset.assign(1, 0);
-                p->gword_offset.clear();
+                p->word_offset.assign(grouped ? 0 : 1, 0);
+                p->gword_offset.assign(grouped ? 1 : 0, 0);
+                if (grouped) p->mdesc.assign(1, d);
                 p->batch_words = true;
             }
         }
         Events ev;
         if (profiling && !check_only) { HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); }
         std::string name;
+        size_t code_bytes = 0;
         try {
-            name = batch_scan(c, ms, tune, check_only, outs, ev.a, ev.b);
+            name = batch_scan(c, ms, tune, check_only, outs, ev.a, ev.b, &code_bytes);
         } catch (const Error &e) {
             throw Error(e.code, "plan " + std::to_string(ms[0]->index) + " (batch " + std::to_string(b) + "): " + e.what());
         }
-        for (int q = 0; q < K; q++)
+        for (int q = 0; q < K; q++) {
             ms[(size_t)q]->p->batch_note = "batch " + std::to_string(b) + ": slot " + std::to_string(q) + " of " + std::to_string(K) + ", " + name;
+            ms[(size_t)q]->p->batch_code_bytes = code_bytes;
+        }
         if (check_only) continue;
         for (int q = 0; q < K; q++) finalize_begin(c, ms[(size_t)q]->p, (const int64_t *)ms[(size_t)q]->p->words->p, 0);
         float ms_scan = 0;
+        // (read once, whichever slots finalise: a slot that is rerun alone must not leave its partners a time of 0)
+        if (ev.a) { HIP_CHECK(hipEventSynchronize(ev.b)); HIP_CHECK(hipEventElapsedTime(&ms_scan, ev.a, ev.b)); }
+        std::vector<std::pair<int, std::string>> rerun;             // slots whose rows carry keys outside the pivots, with finalize_end's words
         for (int q = 0; q < K; q++) {
             vdl_plan *p = ms[(size_t)q]->p;
             try {
                 finalize_end(c, p, 0);
                 p->batch_words = false;
                 if (p->order.set) order_outputs_on_host(c, p);
+            } catch (const NeedGeneralPath &e) {
+                p->batch_words = false;
+                rerun.push_back({q, e.what()});
+                continue;
             } catch (const Error &e) {
                 p->batch_words = false;
                 throw Error(e.code, "plan " + std::to_string(ms[(size_t)q]->index) + ": " + e.what());
             }
-            if (ev.a && q == 0) HIP_CHECK(hipEventElapsedTime(&ms_scan, ev.a, ev.b));       // (the copies behind the scan are done: so is the scan)
             // the whole batch kernel's time, under a label of its own: never a per-query figure
             if (ev.a && p->profiling) p->timings.push_back({"timeInMicrosecondsForBatchedScan_" + name, (double)ms_scan * 1e3});
+        }
+        // (after every slot's finalisation: the others keep their answers and notes.  The batch has shown that the plan's fused scan
+        // meets keys outside its pivots: the rerun takes the general path at once, as vdl_run does after its own fused pass says so)
+        for (const auto &r : rerun) {
+            vdl_plan *p = ms[(size_t)r.first]->p;
+            const int rc = run_plan(c, p, &r.second);
+            if (rc != VDL_OK) throw Error(rc, "plan " + std::to_string(ms[(size_t)r.first]->index) + ": " + c->err);
+            p->batch_note = "alone: rerun after batch " + std::to_string(b) + ": " + r.second;
         }
     }
     for (int i = 0; i < n; i++) {
@@ -1832,6 +1863,12 @@ int vdl_batch_jit_check(vdl_ctx *c, vdl_plan *const *plans, int n) {
     return guard(c, [&] { run_batches(c, plans, n, true); });
 }
 const char *vdl_plan_batch_note(const vdl_plan *p) { return p ? p->batch_note.c_str() : ""; }
+int64_t vdl_plan_batch_code_bytes(const vdl_plan *p) { return p ? (int64_t)p->batch_code_bytes : 0; }
+int vdl_set_batch_grouped(vdl_ctx *c, int on) {
+    if (!c) return VDL_ERR_ARG;
+    c->batch_grouped = on != 0;
+    return VDL_OK;
+}
 
 int vdl_n_outputs(const vdl_plan *p) { return p ? (int)p->outs.size() : 0; }
 int vdl_output(const vdl_plan *p, int k, const char **name, const char **tmp, const int64_t **vals, size_t *n) {

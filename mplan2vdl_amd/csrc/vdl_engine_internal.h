@@ -217,6 +217,7 @@ struct vdl_ctx {
     std::shared_ptr<CommState> comm;       // vdl_comm_init / vdl_comm_init_host
     // batched scans (vdl_run_batch) by shape, columns and width: the loaded kernel with its grid, the descriptors and partials on the device
     std::map<std::string, std::shared_ptr<BatchEntry>> batches;
+    bool batch_grouped = false;        // vdl_run_batch also batches plans whose one scan is grouped (vdl_set_batch_grouped, VDL_BATCH_GROUPED=1)
     std::string err;
     // a few words of PINNED host memory for the round trips of the executors (survivor counts, sortedness verdicts): a copy
     // into pageable memory is staged by the runtime and cost 20-30 us of idle GPU each (Q3 at SF10: three of them per query)
@@ -324,6 +325,7 @@ struct vdl_plan {
     std::vector<char> kscan;                 // [scan] runs on the single-aggregate k_scan (decided when the plan is bound / tuned)
     std::string jit_note;                    // what was specialised, or why not
     std::string batch_note;                  // what the last vdl_run_batch / vdl_batch_jit_check did with this plan ("" after a plain vdl_run)
+    size_t batch_code_bytes = 0;             // the code size of the batch kernel that served the plan in that call, 0 = none did
     bool batch_words = false;                // vdl_run_batch: n_words / word_offset are set for a finalisation although the plan is not bound
     // by scan role ("scan<k>", "front.select", "front.take", "dim<k>", "semi<k>"): the catalog columns the scan bound last read from their
     // images, "name:width ..." (vdl_plan_image_columns); roles without one hold ""

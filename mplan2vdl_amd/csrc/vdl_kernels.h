@@ -60,7 +60,12 @@ hipError_t launch_mscan(const MScanCols &cols, const MScanDesc &d, const MScanDe
 // A batched scan (vdl_run_batch): `fn` is the kernel specialised for k plans that share `cols` (vdl_jit.cpp, Shape::batch), b.d[q] slot
 // q's descriptor on the device, b.partials room for grid x k x (1 + nagg) words; the finish step folds the blocks' partials and leaves slot
 // q's 1 + nagg words at outs[q].  d: any slot's descriptor on the host (the aggregates' kinds are the same in all of them).
-hipError_t launch_mscan_batch(const MScanCols &cols, const MScanDesc &d, const MsBatch &b, int k, int grid, int64_t *const *outs, hipStream_t s, hipFunction_t fn);
+// grouped: a grouped batch (2 .. kMaxBatchGrouped plans; d.replicas = the replicas the kernel was built for): launched with
+// mscan_batch_lds_bytes of dynamic LDS, b.partials room for grid x k x (pcount * (1 + nagg) + 1) words; slot q's pcount * (1 + nagg) + 1 words
+// end up at outs[q] as launch_mscan leaves them, FoldChoose resolved.
+hipError_t launch_mscan_batch(const MScanCols &cols, const MScanDesc &d, const MsBatch &b, int k, int grid, int64_t *const *outs, hipStream_t s, hipFunction_t fn,
+                              bool grouped = false);
+size_t mscan_batch_lds_bytes(const MScanDesc &d, int k);
 // for the specialiser: the by-value arguments, the chosen variant's shape, the dynamic LDS of a launch
 MsArgs mscan_args(const MScanCols &cols);
 void mscan_variant_shape(const ScanLaunch &cfg, int *nc, int *u, bool *vec, bool *grouped, bool *der);

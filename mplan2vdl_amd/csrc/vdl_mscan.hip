@@ -69,20 +69,22 @@ __global__ __launch_bounds__(256) void k_mscan_finish(const MScanDesc *__restric
     if (lane == 0) out[i] = x;
 }
 
-// the finish step of a batched scan: out[q][w] = fold over blocks of partials[b][q][w]; one wave per word
+// the finish step of a batched scan: out[q][i] = fold over blocks of partials[b][q][i]; one wave per word.  A slot holds `slot` words:
+// w = 1 + nagg of a global scan, pcount * w + 1 of a grouped one -- word i reduces as word i % w does, the last (the rows outside the
+// pivots) by sum
 struct MsBatchFinish {
     const int64_t *partials;
     int64_t *out[kMaxBatch];
-    int k, w;
+    int k, w, slot, grouped;
     int rk[kMaxGroupAggs + 1];
 };
 __global__ __launch_bounds__(256) void k_mscan_batch_finish(const MsBatchFinish f, int nblocks) {
     const int lane = threadIdx.x & (kWave - 1);
     const int i = (int)blockIdx.x * (int)(blockDim.x / kWave) + (int)(threadIdx.x / kWave);
-    const int words = f.k * f.w;
+    const int words = f.k * f.slot;
     if (i >= words) return;
-    const int q = i / f.w, w = i % f.w;
-    const int rk = f.rk[w];
+    const int q = i / f.slot, w = i % f.slot;
+    const int rk = f.grouped && w == f.slot - 1 ? (int)R_SUM : f.rk[w % f.w];
     int64_t x = r_identity(rk);
     for (int b = lane; b < nblocks; b += kWave) x = r_combine(rk, x, f.partials[(int64_t)b * words + i]);
     x = wave_reduce(x, rk);
@@ -225,25 +227,38 @@ hipError_t launch_mscan(const MScanCols &cols, const MScanDesc &d, const MScanDe
     return hipGetLastError();
 }
 
-hipError_t launch_mscan_batch(const MScanCols &cols, const MScanDesc &d, const MsBatch &b, int k, int grid, int64_t *const *outs, hipStream_t s, hipFunction_t fn) {
+size_t mscan_batch_lds_bytes(const MScanDesc &d, int k) {
+    return ((size_t)((((int64_t)(1 << k) - 1) * d.pcount * (d.nagg + 1)) | 1) * (size_t)d.replicas + (size_t)kMsBlock + (size_t)(d.nagg + 1)) * sizeof(int64_t);
+}
+hipError_t launch_mscan_batch(const MScanCols &cols, const MScanDesc &d, const MsBatch &b, int k, int grid, int64_t *const *outs, hipStream_t s, hipFunction_t fn,
+                              bool grouped) {
     (void)hipGetLastError();
-    if (k < 2 || k > kMaxBatch || k * (d.nagg + 1) > kMaxBatchWords || grid < 1 || !fn) return hipErrorInvalidValue;
+    if (grid < 1 || !fn) return hipErrorInvalidValue;
+    if (grouped ? k < 2 || k > kMaxBatchGrouped || d.pcount < 1 || d.pcount * (d.nagg + 1) >= (1 << 20) || mscan_batch_lds_bytes(d, k) > (size_t)kGroupLdsWords * sizeof(int64_t)
+                : k < 2 || k > kMaxBatch || k * (d.nagg + 1) > kMaxBatchWords) return hipErrorInvalidValue;
     int nblocks = 0;
     if (cols.n > 0) {
         MsArgs a = ms_args(cols);
         MsBatch bb = b;
         void *params[] = {&a, &bb};
-        const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, (unsigned)kMsBlock, 1, 1, 0, s, params, nullptr);
+        const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, (unsigned)kMsBlock, 1, 1, grouped ? (unsigned)mscan_batch_lds_bytes(d, k) : 0u, s, params, nullptr);
         if (e != hipSuccess) return e;
         nblocks = grid;
     }
     MsBatchFinish f;
     f.partials = b.partials;
     f.k = k; f.w = d.nagg + 1;
+    f.grouped = grouped ? 1 : 0;
+    f.slot = grouped ? (int)(d.pcount * f.w + 1) : f.w;
     for (int q = 0; q < kMaxBatch; q++) f.out[q] = q < k ? outs[q] : nullptr;
     f.rk[0] = R_SUM;
     for (int j = 0; j < kMaxGroupAggs; j++) f.rk[j + 1] = j >= d.nagg || d.agg[j].kind == AGG_SUM ? R_SUM : d.agg[j].kind == AGG_MAX ? R_MAX : R_MIN;      // (rk_of, on the host)
-    k_mscan_batch_finish<<<(k * f.w + 3) / 4, 256, 0, s>>>(f, nblocks);
+    k_mscan_batch_finish<<<(k * f.slot + 3) / 4, 256, 0, s>>>(f, nblocks);
+    // FoldChoose: every slot's smallest row ids become that row's values, slot by slot, as after an unbatched grouped scan
+    bool first = false;
+    for (int j = 0; j < d.nagg; j++) first = first || d.agg[j].kind == AGG_FIRST;
+    if (grouped && first)
+        for (int q = 0; q < k; q++) k_mscan_first<<<(int)((d.pcount + 255) / 256), 256, 0, s>>>(ms_args(cols), b.d[q], 0, outs[q]);
     return hipGetLastError();
 }
 

@@ -538,6 +538,67 @@ __device__ __forceinline__ void eval_term(const MAggDesc &d, const int64_t (&v)[
     }
 }
 
+// the group key of the lane's rows (vdl_fuse.h KeyStep, or its canonical composite form): what a grouped scan and a grouped batch
+// (VDL_BATCH) address their tables by; everything read from D is wave-uniform
+template <int NC, int RW>
+__device__ __forceinline__ void group_key(const MScanDesc &D, const int64_t (&v)[NC][RW], int64_t (&acc)[RW]) {
+    int64_t tmp[RW];
+#pragma unroll
+    for (int r = 0; r < RW; r++) { acc[r] = 0; tmp[r] = 0; }
+    const int ncomp = D.ncomp;
+    if (ncomp > 0) {
+        // the composite key in straight-line code: no step records, no operator dispatch (interpreting Q1's nine
+        // steps was a quarter of the kernel)
+#pragma unroll
+        for (int k = 0; k < kMaxKeyComps; k++) {
+            if (k < ncomp) {                           // wave-uniform
+                const KeyComp kc = D.comp[k];
+                int64_t x[RW];
+#pragma unroll
+                for (int r = 0; r < RW; r++) x[r] = 0;
+#pragma unroll
+                for (int c = 0; c < NC; c++) {
+                    if (c == kc.col) {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) x[r] = v[c][r];
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < RW; r++)
+                    acc[r] |= (int64_t)(((uint64_t)(x[r] >> kc.rsh) - (uint64_t)kc.sub) << kc.lsh);
+            }
+        }
+        if (D.key_masked) {
+            const int64_t mk = D.key_mask;
+#pragma unroll
+            for (int r = 0; r < RW; r++) acc[r] &= mk;
+        }
+    } else
+    VDL_SPEC_UNROLL
+    for (int s = 0; s < D.nkey; s++) {
+        const KeyStep st = D.key[s];               // wave-uniform
+        if (st.kind == KeyStep::LOAD) {
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                if (c == st.col) {
+                    if (st.target) {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) tmp[r] = v[c][r];
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) acc[r] = v[c][r];
+                    }
+                }
+            }
+        } else if (st.kind == KeyStep::OPK) {
+            if (st.target) key_rows<RW>(st.bin, st.const_left, tmp, st.k);
+            else key_rows<RW>(st.bin, st.const_left, acc, st.k);
+        } else {
+            key_combine<RW>(st.bin, st.const_left, acc, tmp);
+        }
+    }
+}
+
 // LDS use: global form (1 + nagg) * 256 lane slots; grouped form replicas * (pcount * (1 + nagg) | 1) + 256 + nagg + 1 trash words
 // C / D: what is known when the plan is bound (column kinds and widths, filters, key, conditions, aggregates); Cr / Dr: what
 // is only known at launch (column bases, row counts, lookup-table sizes, the partials area).  The precompiled kernels pass the
@@ -580,8 +641,9 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
     // computed once; the filters and the accumulation run once per slot, against that slot's descriptor (B.d[q]: scalar loads), into
     // that slot's own count and accumulators -- VDL_BATCH x (1 + VDL_BATCH_NAGG) 64-bit values per lane, in registers (the host
     // caps the product at kMaxBatchWords), not in LDS lane slots: nothing is launched with dynamic LDS.
-    static_assert(!GROUPED && !DER && !STAGED, "batched scans are global aggregate scans over table columns that read nothing late");
-    static_assert(VDL_BATCH >= 2 && VDL_BATCH <= kMaxBatch && VDL_BATCH * (1 + VDL_BATCH_NAGG) <= kMaxBatchWords, "the slots' accumulators fit their registers");
+    static_assert(!DER && !STAGED, "batched scans are aggregate scans over table columns that read nothing late");
+    static_assert(GROUPED ? VDL_BATCH >= 2 && VDL_BATCH <= kMaxBatchGrouped
+                          : VDL_BATCH >= 2 && VDL_BATCH <= kMaxBatch && VDL_BATCH * (1 + VDL_BATCH_NAGG) <= kMaxBatchWords, "the slots' accumulators fit their registers");
     constexpr int KB = VDL_BATCH, NA = VDL_BATCH_NAGG, NA1 = NA > 0 ? NA : 1;
     int64_t bcnt[KB], bacc[KB][NA1];
 #pragma unroll
@@ -589,6 +651,30 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
         bcnt[q] = 0;
 #pragma unroll
         for (int j = 0; j < NA; j++) bacc[q][j] = r_identity(rk_of(D.agg[j].kind));
+    }
+    // The GROUPED batch: a row's group and its aggregate terms do not depend on anybody's bounds either -- only the SET of slots whose
+    // filters it passes does.  Every non-empty set (class m = sum of pq << q, 2^K - 1 of them) has a table of its own, laid out as the
+    // unbatched grouped table, class m - 1 at m - 1 times `words` inside a replica: a row issues the 1 + nagg atomics the unbatched form
+    // issues, whatever K is, and the classes are folded into the slots' tables once per block (the epilogue).  The empty class and the
+    // rows outside the pivots go to the lane's trash row; the latter are counted per slot, in registers.
+    constexpr int NCLS = (1 << KB) - 1;
+    const int64_t bstride = ((int64_t)NCLS * words) | 1;   // a replica: odd, as rstride
+    int boob[KB];
+#pragma unroll
+    for (int q = 0; q < KB; q++) boob[q] = 0;
+    if (GROUPED) {
+        for (int r = 0; r < R; r++)
+            for (int64_t i = tid; i < (int64_t)NCLS * words; i += BS) {
+                const int w = (int)(i % W);
+                int rk = R_SUM;
+#pragma unroll
+                for (int j = 0; j < NA; j++) if (w == j + 1) rk = rk_of(D.agg[j].kind);
+                lds[(int64_t)r * bstride + i] = r_identity(rk);
+            }
+        mytab = lds + (int64_t)(tid % R) * bstride;
+        trash = (int)((int64_t)R * bstride + (int64_t)tid - (int64_t)(tid % R) * bstride);      // (the lanes' trash rows: as in the unbatched form)
+        for (int64_t i = tid; i < BS + W; i += BS) lds[(int64_t)R * bstride + i] = 0;
+        __syncthreads();
     }
 #else
     if (GROUPED) {
@@ -632,7 +718,50 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
         // (the stages arrive as generated straight-line code -- VDL_STAGED_PRE / _POST, vdl_jit.cpp: written as loops over
         // columns and stages with the stage numbers read from C, the compiler no longer folded the descriptor: 235 KB of code)
 #ifdef VDL_BATCH
-        {
+        if (GROUPED) {
+            int64_t acc[RW];
+            group_key<NC, RW>(D, v, acc);
+            int m[RW], off[RW];
+#pragma unroll
+            for (int r = 0; r < RW; r++) m[r] = 0;
+#pragma unroll
+            for (int q = 0; q < KB; q++) {
+                bool pq[RW];
+                eval_pass_narrow<NC, RW>(C, D, *B.d[q], v, pq);
+#pragma unroll
+                for (int r = 0; r < RW; r++) m[r] |= (int)pq[r] << q;
+            }
+#pragma unroll
+            for (int r = 0; r < RW; r++) {
+                const int64_t b = (int64_t)((uint64_t)acc[r] - (uint64_t)D.pmin);
+                const bool in = b >= 0 && b < G;
+#pragma unroll
+                for (int q = 0; q < KB; q++) boob[q] += (!in && ((m[r] >> q) & 1)) ? 1 : 0;
+                // the class's table inside the lane's replica, or the lane's trash row (no slot wants the row, or no pivot holds it)
+                off[r] = (in && m[r]) ? (m[r] - 1) * (int)words + (int)b * W : trash;
+                atomicAdd((unsigned long long *)&mytab[off[r]], 1ull);
+            }
+            // (the loop as the unbatched form writes it, over the descriptor's own count: written over the constant NA, Q1's descriptor no
+            // longer folded -- 125 KB of code, the descriptor in scratch memory -- where this form gives 10 KB)
+            VDL_SPEC_UNROLL
+            for (int j = 0; j < nagg; j++) {
+                const int rk = rk_of(D.agg[j].kind);
+                int64_t t[RW];
+                eval_term<NC, RW>(D.agg[j], v, rowid, t);
+                if (rk == R_SUM) {
+#pragma unroll
+                    for (int r = 0; r < RW; r++) atomicAdd((unsigned long long *)&mytab[off[r] + 1 + j], (unsigned long long)t[r]);
+                } else if (rk == R_MAX) {
+#pragma unroll
+                    for (int r = 0; r < RW; r++) atomicMax((long long *)&mytab[off[r] + 1 + j], (long long)t[r]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < RW; r++) atomicMin((long long *)&mytab[off[r] + 1 + j], (long long)t[r]);
+                }
+            }
+            (void)rows_left; (void)tile0; (void)tile_rows; (void)staged; (void)alive; (void)pass;
+            return;
+        } else {
             int64_t t[NA1][RW];
 #pragma unroll
             for (int j = 0; j < NA; j++) eval_term<NC, RW>(D.agg[j], v, rowid, t[j]);
@@ -691,62 +820,8 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
         }
         int off[RW];
         if (GROUPED) {
-            // group key: two-accumulator program (vdl_fuse.h KeyStep)
-            int64_t acc[RW], tmp[RW];
-#pragma unroll
-            for (int r = 0; r < RW; r++) { acc[r] = 0; tmp[r] = 0; }
-            const int ncomp = D.ncomp;
-            if (ncomp > 0) {
-                // the composite key in straight-line code: no step records, no operator dispatch (interpreting Q1's nine
-                // steps was a quarter of the kernel)
-#pragma unroll
-                for (int k = 0; k < kMaxKeyComps; k++) {
-                    if (k < ncomp) {                           // wave-uniform
-                        const KeyComp kc = D.comp[k];
-                        int64_t x[RW];
-#pragma unroll
-                        for (int r = 0; r < RW; r++) x[r] = 0;
-#pragma unroll
-                        for (int c = 0; c < NC; c++) {
-                            if (c == kc.col) {
-#pragma unroll
-                                for (int r = 0; r < RW; r++) x[r] = v[c][r];
-                            }
-                        }
-#pragma unroll
-                        for (int r = 0; r < RW; r++)
-                            acc[r] |= (int64_t)(((uint64_t)(x[r] >> kc.rsh) - (uint64_t)kc.sub) << kc.lsh);
-                    }
-                }
-                if (D.key_masked) {
-                    const int64_t mk = D.key_mask;
-#pragma unroll
-                    for (int r = 0; r < RW; r++) acc[r] &= mk;
-                }
-            } else
-            VDL_SPEC_UNROLL
-            for (int s = 0; s < D.nkey; s++) {
-                const KeyStep st = D.key[s];               // wave-uniform
-                if (st.kind == KeyStep::LOAD) {
-#pragma unroll
-                    for (int c = 0; c < NC; c++) {
-                        if (c == st.col) {
-                            if (st.target) {
-#pragma unroll
-                                for (int r = 0; r < RW; r++) tmp[r] = v[c][r];
-                            } else {
-#pragma unroll
-                                for (int r = 0; r < RW; r++) acc[r] = v[c][r];
-                            }
-                        }
-                    }
-                } else if (st.kind == KeyStep::OPK) {
-                    if (st.target) key_rows<RW>(st.bin, st.const_left, tmp, st.k);
-                    else key_rows<RW>(st.bin, st.const_left, acc, st.k);
-                } else {
-                    key_combine<RW>(st.bin, st.const_left, acc, tmp);
-                }
-            }
+            int64_t acc[RW];
+            group_key<NC, RW>(D, v, acc);
 #pragma unroll
             for (int r = 0; r < RW; r++) {
                 const int64_t b = (int64_t)((uint64_t)acc[r] - (uint64_t)D.pmin);
@@ -986,7 +1061,40 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
     __shared__ int64_t red[kMsBlock / kWave];
     const int lane = tid & (kWave - 1), wave = tid / kWave;
 #ifdef VDL_BATCH
-    {
+    if (GROUPED) {
+        // the block's partials, [slot][words + 1]: slot q's table is the fold, word by word and by the word's own reduction, over the
+        // replicas and over the classes that contain q; its last word the slot's rows outside the pivots.  K unbatched grouped partials.
+        int64_t *dst = B.partials + (int64_t)blockIdx.x * KB * (words + 1);
+        for (int64_t i = tid; i < KB * words; i += BS) {
+            const int q = (int)(i / words);
+            const int64_t wi = i % words;
+            const int w = (int)(wi % W);
+            int rk = R_SUM;
+#pragma unroll
+            for (int j = 0; j < NA; j++) if (w == j + 1) rk = rk_of(D.agg[j].kind);
+            int64_t x = r_identity(rk);
+            for (int m = 1; m <= NCLS; m++) {
+                if (!((m >> q) & 1)) continue;
+                for (int r = 0; r < R; r++) x = r_combine(rk, x, lds[(int64_t)r * bstride + (int64_t)(m - 1) * words + wi]);
+            }
+            dst[(int64_t)q * (words + 1) + wi] = x;
+        }
+        // (the waves' counts meet in the trash area: every atomic into it lies before the barrier above)
+        int64_t *meet = lds + (int64_t)R * bstride;
+#pragma unroll
+        for (int q = 0; q < KB; q++) {
+            const int64_t x = wave_reduce((int64_t)boob[q], R_SUM);
+            if (lane == 0) meet[wave * KB + q] = x;
+        }
+        __syncthreads();
+        if (tid < KB) {
+            int64_t x = 0;
+            for (int k = 0; k < kMsBlock / kWave; k++) x += meet[k * KB + tid];
+            dst[(int64_t)tid * (words + 1) + words] = x;
+        }
+        (void)red; (void)cnt; (void)oob; (void)rstride; (void)bcnt; (void)bacc;
+        return;
+    } else {
         // the block's partials, [slot][count, aggregates]: every value folded over the wave, then over the block's waves by the lane
         // that writes it
         constexpr int WB = NA + 1;
@@ -1010,7 +1118,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
             for (int k = 1; k < kMsBlock / kWave; k++) y = r_combine(rk, y, bred[k][tid]);
             B.partials[(int64_t)blockIdx.x * (KB * WB) + tid] = y;
         }
-        (void)red; (void)cnt; (void)oob; (void)mytab; (void)trash; (void)rstride; (void)R;
+        (void)red; (void)cnt; (void)oob; (void)mytab; (void)trash; (void)rstride; (void)R; (void)bstride; (void)boob;
         return;
     }
 #endif

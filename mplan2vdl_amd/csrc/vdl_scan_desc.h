@@ -162,6 +162,10 @@ constexpr int kMaxCarry = 2;
 // launch descriptor: wave-uniform scalar loads -- and one partials area for all of them, [grid][slots][1 + nagg] words.
 constexpr int kMaxBatch = 8;
 constexpr int kMaxBatchWords = 32;           // slots x (1 + nagg): a lane keeps that many 64-bit accumulators in registers
+// A GROUPED batch keeps one table per non-empty set of slots in LDS (2^K - 1 pass-class tables per replica, vdl_mscan_body.h), its
+// partials area is [grid][slots][pcount * (1 + nagg) + 1] words: K unbatched grouped partials side by side.
+constexpr int kMaxBatchGrouped = 4;
+constexpr int kGroupLdsWords = 8192;         // 64 KiB: what a block gets without raising its dynamic-LDS attribute, two blocks per CU
 struct MsBatch {
     const MScanDesc *d[kMaxBatch] = {};
     int64_t *partials = nullptr;

@@ -494,12 +494,22 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
 
 // ---- batched runs ------------------------------------------------------------------------------------------------------------
 // Which plans share a scan is decided here, next to bind_form: the conditions are the packed form's (one global aggregate scan over
-// table columns) plus "the same columns" and "the same generated code under run-time bounds".
-std::string batch_alone_reason(const vdl_plan *p) {
+// table columns) plus "the same columns" and "the same generated code under run-time bounds".  With vdl_set_batch_grouped a plan
+// whose one scan is a grouped scan over table columns shares a grouped batch by the same rules; a batch never mixes the two kinds
+// (their shape keys differ).
+std::string batch_alone_reason(const vdl_plan *p, bool grouped_on) {
     if (!p->use_fusion || !p->fused.ok) return "the plan is not fused";
     if (!p->use_jit) return "specialisation is off";
     const FusedPlan &F = p->fused;
-    if (!F.gscans.empty()) return "grouped scans are not batched";
+    if (!F.gscans.empty() && !grouped_on) return "grouped scans are not batched";
+    if (!F.gscans.empty()) {
+        if (F.gscans.size() + F.scans.size() != 1) return "the plan has " + std::to_string(F.gscans.size() + F.scans.size()) + " scans, a batch shares exactly one";
+        if (!F.prelude.empty()) return "scans with lookup tables or semi-join sets are not batched";
+        for (const ScanColumn &sc : F.gscans[0].cols)
+            if (sc.kind != VC_DIRECT) return "scans with derived columns are not batched";
+        if (F.gscans[0].never) return "its filters can hold for no row: there is nothing to scan";
+        return "";
+    }
     if (F.scans.size() != 1) return "the plan has " + std::to_string(F.scans.size()) + " scans, a batch shares exactly one";
     if (!F.prelude.empty()) return "scans with lookup tables or semi-join sets are not batched";
     for (const ScanColumn &sc : F.scans[0].cols)
@@ -508,11 +518,35 @@ std::string batch_alone_reason(const vdl_plan *p) {
     return "";
 }
 int batch_cap(int nagg) { return std::min(kMaxBatch, kMaxBatchWords / (1 + std::max(nagg, 0))); }
+// VDL_BATCH_WIDTH=k (tests, A/B runs): no batch of either kind is wider than k
+static int batch_width_asked() {
+    const char *w = getenv("VDL_BATCH_WIDTH");
+    return w && atoi(w) >= 2 ? atoi(w) : kMaxBatch;
+}
+int batch_cap_asked(int nagg) { return std::min(batch_cap(nagg), batch_width_asked()); }
+// A grouped batch of K plans keeps 2^K - 1 class tables per replica in LDS: R x (((2^K - 1) x words) | 1) + 256 + nagg + 1 trash words within
+// kGroupLdsWords, R the largest power of two <= 8 that fits.  More slots mean fewer replicas, and the replicas are what keeps the lanes of a
+// wave off each other's words when a few groups hold most rows: a width is taken only while it leaves min(the replicas the scan has
+// alone, kBatchGroupMinReplicas).  (the constant: see DESIGN.md section 5.12 for what was measured)
+constexpr int kBatchGroupMinReplicas = 2;
+int batch_group_replicas(const MScanDesc &d, int k) {
+    const int64_t words = d.pcount * (d.nagg + 1), tables = (((int64_t)1 << k) - 1) * words;
+    for (int r = 8; r >= 1; r >>= 1)
+        if ((int64_t)r * (tables | 1) + 256 + d.nagg + 1 <= kGroupLdsWords) return r;
+    return 0;
+}
+int batch_group_cap(const MScanDesc &d, int replicas_alone) {
+    for (int k = std::min(kMaxBatchGrouped, batch_width_asked()); k >= 2; k--) {
+        const int r = batch_group_replicas(d, k);
+        if (r >= 1 && r >= std::min(replicas_alone, kBatchGroupMinReplicas)) return k;
+    }
+    return 0;
+}
 
 // the shape of a batch's kernel in form f: the scan's own shape, with the bounds at run time whatever the plans' own setting
 static jit::Shape batch_shape(const BatchMember &m, const ScanForm &f, int k) {
     jit::Shape sh = jit_shape(m.cols, m.cfg, f, true);
-    sh.grouped = false;
+    sh.grouped = m.grouped;
     sh.der = false;
     sh.batch = k;
     return sh;
@@ -521,8 +555,11 @@ void batch_bind(vdl_ctx *c, vdl_plan *p, BatchMember &m) {
     m.p = p;
     m.desc = std::make_shared<MScanDesc>();
     int64_t bpr = 0;
-    bind_mscan(c, p->fused.scans[0], m.cols, *m.desc, &bpr, p->row_offset);
-    m.cfg = mscan_launch_config(m.cols, *m.desc, false, c->num_cus);
+    m.grouped = !p->fused.gscans.empty();
+    if (m.grouped) bind_mscan(c, p->fused.gscans[0], m.cols, *m.desc, &bpr, p->row_offset);
+    else bind_mscan(c, p->fused.scans[0], m.cols, *m.desc, &bpr, p->row_offset);
+    m.cfg = mscan_launch_config(m.cols, *m.desc, m.grouped, c->num_cus);      // (grouped: the key's canonical form and the replicas the scan has alone)
+    m.replicas_alone = m.desc->replicas;
     if (m.cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no multi-aggregate scan kernel variant for this shape");
     std::ostringstream k;
     k << m.cols.ncol << ":" << m.cols.n << ":" << m.cols.row0 << ":" << m.cols.image;
@@ -540,6 +577,7 @@ struct vdl::eng::BatchEntry {
     ScanForm form;                             // (u: the row pairs per lane / per slice it was built at)
     std::string name, entry;
     size_t code_bytes = 0;
+    bool grouped = false;                      // a grouped batch: dynamic LDS for its class tables, [grid][slots][words + 1] partials
     BufP descs, partials;
     size_t partial_words = 0;
     std::vector<unsigned char> shadow;         // what `descs` holds: uploaded again only when some slot's descriptor changed
@@ -556,7 +594,7 @@ static bool batch_bind_form(vdl_ctx *c, const std::vector<BatchMember *> &ms, co
     const size_t K = ms.size();
     bound.assign(K, BoundForm{});
     for (size_t q = 0; q < K; q++) {
-        if (!bind_form(c, ms[q]->p, 0, false, f, sh.u, ms[q]->cols, *ms[q]->desc, bound[q], why)) return false;
+        if (!bind_form(c, ms[q]->p, 0, ms[q]->grouped, f, sh.u, ms[q]->cols, *ms[q]->desc, bound[q], why)) return false;
         const MsArgs &a = bound[q].args, &a0 = bound[0].args;
         const std::string name = jit::entry_name(jit::MSCAN, a, *bound[q].desc, sh);
         if (q == 0) entry = name;
@@ -576,6 +614,7 @@ static bool batch_build(vdl_ctx *c, const ScanForm &f, const jit::Shape &sh, con
     if (code.size() > (size_t)96 << 10) { why = "the descriptor did not fold (" + std::to_string(code.size()) + " B of code)"; return false; }
     out = BatchEntry{};
     out.form = f; out.form.u = sh.u;
+    out.grouped = sh.grouped;
     out.code_bytes = code.size();
     out.entry = entry;
     out.name = jit_name(sh, bound[0].cols->image != 0);
@@ -584,7 +623,8 @@ static bool batch_build(vdl_ctx *c, const ScanForm &f, const jit::Shape &sh, con
     out.k = jit::load(code, why, entry);
     if (!out.k) return false;
     int per_cu = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, out.k->fn, 256, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 2; }
+    const size_t lds = sh.grouped ? mscan_batch_lds_bytes(desc, sh.batch) : 0;
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, out.k->fn, 256, lds) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 2; }
     if (per_cu > 8) per_cu = 8;
     int64_t grid = (int64_t)c->num_cus * per_cu;
     // (the packed form: one wave per stripe of 2048 rows at a time, four per block)
@@ -618,17 +658,22 @@ static void batch_launch(vdl_ctx *c, BatchEntry &e, const std::vector<BoundForm>
         e.shadow.swap(want);                                   // (the source of the copy stays put until the next upload)
         HIP_CHECK(hipMemcpyAsync(e.descs->p, e.shadow.data(), e.shadow.size(), hipMemcpyHostToDevice, c->stream));
     }
-    const size_t words = (size_t)e.grid * (size_t)K * (size_t)W;
+    const size_t words = (size_t)e.grid * (size_t)K * (e.grouped ? (size_t)(bound[0].desc->pcount * W + 1) : (size_t)W);
     if (!e.partials || e.partial_words < words) { e.partials = dev_alloc(c, sizeof(int64_t) * words); e.partial_words = words; }
     MsBatch b;
     for (int q = 0; q < K; q++) b.d[q] = (const MScanDesc *)e.descs->p + q;
     b.partials = (int64_t *)e.partials->p;
-    HIP_CHECK(launch_mscan_batch(*bound[0].cols, *bound[0].desc, b, K, e.grid, outs, c->stream, e.k->fn));
+    HIP_CHECK(launch_mscan_batch(*bound[0].cols, *bound[0].desc, b, K, e.grid, outs, c->stream, e.k->fn, e.grouped));
 }
 
-std::string batch_scan(vdl_ctx *c, const std::vector<BatchMember *> &ms, bool tune, bool check_only, int64_t *const *outs, hipEvent_t ev0, hipEvent_t ev1) {
+std::string batch_scan(vdl_ctx *c, const std::vector<BatchMember *> &ms, bool tune, bool check_only, int64_t *const *outs, hipEvent_t ev0, hipEvent_t ev1,
+                       size_t *code_bytes) {
     const int K = (int)ms.size();
-    if (K < 2 || K > batch_cap(ms[0]->desc->nagg)) throw Error(VDL_ERR_ARG, "a batch of " + std::to_string(K) + " plans does not fit the kernel");
+    const bool grouped = ms[0]->grouped;
+    if (K < 2 || (grouped ? K > kMaxBatchGrouped || batch_group_replicas(*ms[0]->desc, K) < 1 : K > batch_cap(ms[0]->desc->nagg)))
+        throw Error(VDL_ERR_ARG, "a batch of " + std::to_string(K) + " plans does not fit the kernel");
+    // (a grouped batch is generated for the replicas its width leaves: part of every slot's descriptor from here on)
+    if (grouped) for (BatchMember *m : ms) m->desc->replicas = batch_group_replicas(*m->desc, K);
     // VDL_JIT_PIN="u=2,late=6" leaves the tuner one candidate as it does for a plan's own scan: late=6 the packed form, any other value eager
     int pin_u = 0, pin_late = 0;
     const char *pin = tune ? getenv("VDL_JIT_PIN") : nullptr;
@@ -636,7 +681,7 @@ std::string batch_scan(vdl_ctx *c, const std::vector<BatchMember *> &ms, bool tu
         if (const char *q = strstr(pin, "u=")) pin_u = atoi(q + 2);
         if (const char *q = strstr(pin, "late=")) pin_late = atoi(q + 5);
     }
-    const char *env_u = getenv("VDL_JIT_U");
+    const char *env_u = getenv(grouped ? "VDL_JIT_GROUP_U" : "VDL_JIT_U");
     const std::string key = ms[0]->shape_key + "|" + ms[0]->cols_key + "|" + std::to_string(K) + (tune ? "|tuned|" : "||") + (pin ? pin : "") + "|" + (env_u ? env_u : "") +
                             (c->images ? "|img" : "|") + (check_only ? "|check" : "");
     std::vector<BoundForm> bound;
@@ -653,7 +698,9 @@ std::string batch_scan(vdl_ctx *c, const std::vector<BatchMember *> &ms, bool tu
         // shape has it; tuned the eager form at 2, 3, 4 and the every-column packed form at 2, 4, by the tuner's rule; the staged, queue
         // and packed-late forms are not batched
         std::vector<std::pair<int, int>> cands = {{0, 0}};
-        if (tune && pin_u > 0) cands = {{pin_u, pin_late == 6 ? 6 : 0}};
+        // (a grouped batch has the eager tile form alone)
+        if (tune && pin_u > 0) cands = {{pin_u, pin_late == 6 && !grouped ? 6 : 0}};
+        else if (tune && !check_only && grouped) cands = {{2, 0}, {3, 0}, {4, 0}};
         else if (tune && !check_only) cands = {{2, 0}, {3, 0}, {4, 0}, {2, 6}, {4, 6}};
         TimingEvents ev;
         if (cands.size() > 1) { HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); }
@@ -693,6 +740,7 @@ std::string batch_scan(vdl_ctx *c, const std::vector<BatchMember *> &ms, bool tu
         batch_launch(c, *e, bound, outs);
         if (ev1) HIP_CHECK(hipEventRecord(ev1, c->stream));
     }
+    if (code_bytes) *code_bytes = e->code_bytes;
     return e->name;
 }
 

@@ -33,6 +33,8 @@
 // those that differ in their literals alone share one scan of the columns, the others run alone inside the same call -- and one reply
 // is printed per line, stdin's first.  The options (--order-by included) apply to every program.  One line per program "vdlrun:
 // batch: <vdl_plan_batch_note>" goes to stderr.  Not with --gpus: a sharded run takes one plan.
+// --batch-grouped: programs whose one scan is a GROUP BY over table columns share a grouped batch too (vdl_set_batch_grouped); without it
+// they run alone, as "grouped scans are not batched".
 #include <signal.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -190,7 +192,7 @@ bool read_reply(const std::string &path, Reply &r) {
 struct Options {
     int64_t rows = 60175;           // SF0.01 lineitem, /root/reference/tests/tpchnoorder/bounds.csv:59
     uint64_t seed = 0x5EED0006ULL;
-    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0;
+    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0;
     std::string data_dir, shard = "lineitem";
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
@@ -247,6 +249,7 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
     vdl_ctx *ctx = nullptr;
     int rc = vdl_open(&ctx, o.describe ? -1 : (world > 1 || !comm_dir.empty() ? rank : o.device));
     if (rc) return die(ctx, "vdl_open", rc);
+    if (o.batch_grouped) vdl_set_batch_grouped(ctx, 1);
     std::vector<vdl_plan *> plans;
     std::string loads = text;                                  // every program's text: what --data looks for Loads in
     for (size_t k = 0; k <= o.batch_texts.size(); k++) {
@@ -348,6 +351,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpus" && i + 1 < argc) o.gpus = std::atoi(argv[++i]);
         else if (a == "--shard" && i + 1 < argc) o.shard = argv[++i];
         else if (a == "--batch" && i + 1 < argc) o.batch_files.push_back(argv[++i]);
+        else if (a == "--batch-grouped") o.batch_grouped = 1;
         else if (a == "--order-by" && i + 1 < argc && parse_order_by(argv[i + 1], o)) i++;
         else if (a == "--order-sharded") o.order_sharded = 1;
         else if (a == "--limit" && i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]) &&
@@ -361,7 +365,7 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }

@@ -194,6 +194,10 @@ class Plan:
         "alone: <reason>"; "" after a plain run() (vdl.h: vdl_plan_batch_note)."""
         return (self._e._L.vdl_plan_batch_note(self._h) or b"").decode()
 
+    def batch_code_bytes(self):
+        """The code size of the batch kernel that served this plan in the last Engine.run_batch / batch_jit_check; 0 when it ran alone."""
+        return int(self._e._L.vdl_plan_batch_code_bytes(self._h))
+
     def execute(self):
         """vdl_run only: the outputs stay in the plan (borrowed until the next run); `collect()` converts them."""
         self._e._check(self._e._L.vdl_run(self._e._c, self._h))
@@ -617,6 +621,11 @@ class Engine:
         plans, arr = self._handles(plans)
         self._check(self._L.vdl_run_batch(self._c, arr, len(plans)))
         return [p._collect(as_numpy) for p in plans]
+
+    def set_batch_grouped(self, on):
+        """True: run_batch also batches plans whose one scan is a GROUP BY over table columns (vdl.h: vdl_set_batch_grouped; off by
+        default, VDL_BATCH_GROUPED=1 switches it on when the context opens)."""
+        self._check(self._L.vdl_set_batch_grouped(self._c, 1 if on else 0))
 
     def batch_jit_check(self, plans):
         """Group the plans and build the batch kernels against the registered columns without a device (vdl_batch_jit_check); the notes."""
