@@ -81,6 +81,20 @@ bool use_kscan(const ScanPlan &sp) {
     return sp.aggs.size() == 1 && sp.cols.size() <= 4;
 }
 
+// A comparison of two columns is planned as a range of their difference (vdl_fuse.cpp mk_cmp_diff: a > b as a - b in [1, max]), read
+// for its sign and its zero.  The wrap-around difference (VC_SUB) has them right while a - b stays inside int64: certain when both
+// operands are table columns, or lookups of columns, stored in fewer than 8 bytes (TPC-H compares int32 dates this way: those scans
+// are what they were).  Over anything wider the bound scan computes the saturated difference instead (VC_SUBS), whose sign and zero
+// are those of the exact one for any operands.  (A Subtract the program wrote itself means its wrap-around value and carries no mark.)
+static int bound_kind(vdl_ctx *c, const std::vector<ScanColumn> &sc, const ScanColumn &s) {
+    if (s.kind != VC_SUB || !s.order_diff) return s.kind;
+    for (int src : {s.idx, s.idx2}) {
+        const ScanColumn *o = src >= 0 && (size_t)src < sc.size() ? &sc[(size_t)src] : nullptr;
+        if (!(o && (o->kind == VC_DIRECT || o->kind == VC_GATHER) && find_col(c, o->name).width < 8)) return VC_SUBS;
+    }
+    return VC_SUB;
+}
+
 // formula columns (VC_FORM) into the descriptor's pool, in the kernels' layout (MScanDesc::form): the range tests sorted by
 // column, then the postfix program with every test replaced by a reference to its result bit
 static void bind_forms(const std::vector<ScanColumn> &sc, MScanDesc &d) {
@@ -167,10 +181,10 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
     img::Image ims[kMaxVCols];
     for (int k = 0; k < cols.ncol; k++) {
         const ScanColumn &sc = sp.cols[(size_t)k];
-        cols.kind[k] = sc.kind;
+        cols.kind[k] = bound_kind(c, sp.cols, sc);
         cols.lo[k] = sc.lo; cols.hi[k] = sc.hi;
         cols.filtered[k] = (cols.lo[k] != INT64_MIN || cols.hi[k] != INT64_MAX) ? 1 : 0;
-        d.dkind[k] = sc.kind; d.dsrc[k] = sc.idx; d.dsrc2[k] = sc.idx2;
+        d.dkind[k] = cols.kind[k]; d.dsrc[k] = sc.idx; d.dsrc2[k] = sc.idx2;
         if (sc.kind == VC_DIRECT) {
             const Column &col = find_col(c, sc.name);
             if (n >= 0 && col.n != n)
@@ -369,11 +383,11 @@ static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vecto
     img::Image ims[kMaxVCols];
     for (int k = 0; k < cols.ncol; k++) {
         const ScanColumn &s = sc[(size_t)k];
-        cols.kind[k] = s.kind;
+        cols.kind[k] = bound_kind(c, sc, s);
         cols.lo[k] = s.lo; cols.hi[k] = s.hi;
         cols.filtered[k] = (s.lo != INT64_MIN || s.hi != INT64_MAX) ? 1 : 0;
         d.flo[k] = s.lo; d.fhi[k] = s.hi;
-        d.dkind[k] = s.kind; d.dsrc[k] = s.idx; d.dsrc2[k] = s.idx2;
+        d.dkind[k] = cols.kind[k]; d.dsrc[k] = s.idx; d.dsrc2[k] = s.idx2;
         if (s.kind == VC_DIRECT) {
             const Column &col = find_col(c, s.name);
             if (n >= 0 && col.n != n) throw Error(VDL_ERR_SHAPE, "columns of table '" + table + "' have different lengths in the catalog");

@@ -31,6 +31,7 @@ struct Row {
     int dsel = 0;
     int64_t c0 = 0, c1 = 0;  // CONST: value; IOTA: from, step
     int bin = -1;
+    bool ord = false;        // BIN Subtract made by leaf_cmp for a comparison of two atoms (mk_cmp_diff): read for its sign and its zero
     RowP l, r;
 };
 
@@ -64,7 +65,7 @@ void row_key(const RowP &e, std::string &o) {
     case Row::COL: o += e->col; break;
     case Row::CONST: o += "#" + std::to_string(e->c0); break;
     case Row::IOTA: o += "iota(" + std::to_string(e->c0) + "," + std::to_string(e->c1) + ")"; break;
-    case Row::BIN: o += kBinNames[e->bin]; o += "("; row_key(e->l, o); o += ","; row_key(e->r, o); o += ")"; break;
+    case Row::BIN: o += kBinNames[e->bin]; o += e->ord ? "?(" : "("; row_key(e->l, o); o += ","; row_key(e->r, o); o += ")"; break;
     case Row::VIA: o += "via(" + e->dim + ":" + std::to_string(e->dsel) + ";"; row_key(e->l, o); o += ";"; row_key(e->r, o); o += ")"; break;
     case Row::LIKE: o += "like(" + e->col + ";" + e->pat + ";"; row_key(e->l, o); o += ")"; break;
     }
@@ -163,6 +164,15 @@ static void clause_and(Clause &out, const RowP &atom, const IvSet &set) {
     if (it == out.cols.end()) out.cols[key] = iv_norm(set); else it->second = iv_and(it->second, set);
 }
 
+// The difference a comparison of two atoms is turned into.  Its SIGN and its ZERO are what the ranges [1, max], [0, max], [0, 0] test, and
+// the wrap-around difference the scans compute (VC_SUB) has the wrong sign once a - b leaves int64.  So the atom is marked (and keyed
+// apart from a Subtract the program wrote itself, whose wrap-around value IS its meaning): the binder reads it as the saturated
+// difference (VC_SUBS) unless both operands are stored in fewer than 8 bytes, where the two are the same (vdl_engine.cpp bound_kind).
+static RowP mk_cmp_diff(const RowP &l, const RowP &r) {
+    auto d = std::make_shared<Row>();
+    d->k = Row::BIN; d->bin = B_SUB; d->l = l; d->r = r; d->ord = true;
+    return d;
+}
 bool leaf_cmp(const Row &p, RowP &atom, IvSet &set) {
     if (p.k != Row::BIN) return false;
     const RowP &l = p.l, &r = p.r;
@@ -173,13 +183,11 @@ bool leaf_cmp(const Row &p, RowP &atom, IvSet &set) {
         if (l->k == Row::CONST && is_atom(r)) {           // k > col
             atom = r; set = l->c0 == INT64_MIN ? IvSet{} : IvSet{{INT64_MIN, l->c0 - 1}}; return true;
         }
-        if (is_atom(l) && is_atom(r)) {                   // column against column: a > b  <=>  a - b >= 1 (no wrap-around for the
-            atom = mk_bin(B_SUB, l, r); set = IvSet{{1, INT64_MAX}}; return true;      // date / key / quantity magnitudes compared this way)
-        }
+        if (is_atom(l) && is_atom(r)) { atom = mk_cmp_diff(l, r); set = IvSet{{1, INT64_MAX}}; return true; }      // a > b  <=>  a - b >= 1
     } else if (p.bin == B_EQ) {
         if (is_atom(l) && r->k == Row::CONST) { atom = l; set = {{r->c0, r->c0}}; return true; }
         if (l->k == Row::CONST && is_atom(r)) { atom = r; set = {{l->c0, l->c0}}; return true; }
-        if (is_atom(l) && is_atom(r)) { atom = mk_bin(B_SUB, l, r); set = {{0, 0}}; return true; }
+        if (is_atom(l) && is_atom(r)) { atom = mk_cmp_diff(l, r); set = {{0, 0}}; return true; }                   // a = b  <=>  a - b = 0
     }
     return false;
 }
@@ -896,6 +904,7 @@ struct VCols {
                 c.idx = (*this)(atom->l); c.idx2 = (*this)(atom->r);
                 if (c.idx < 0 || c.idx2 < 0) return -1;
                 c.kind = VC_SUB;
+                c.order_diff = atom->ord;
                 break;
             }
             if (!is_formula(atom)) { why = "not a column form: " + key; return -1; }

@@ -22,6 +22,8 @@ struct ScanColumn {
     int kind = VC_DIRECT;
     int idx = -1, idx2 = -1;   // source virtual column(s): always earlier in the list
     int prelude = -1;
+    bool order_diff = false;   // VC_SUB standing for a comparison of its two sources (a > b as a - b in [1, max]): read for its sign and its
+                               // zero, so the binder makes it the saturated difference (VC_SUBS) where the wrap-around one could differ
     std::vector<FormStep> form; // VC_FORM
     // the earlier columns this one is computed from
     std::vector<int> sources() const {

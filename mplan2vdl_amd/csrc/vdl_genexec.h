@@ -386,6 +386,7 @@ struct GenExec {
                 return true;
             }
             // too big for one kernel: run the larger side now and keep it as a leaf
+            if (trace_forms) std::fprintf(stderr, "  Id %-4d split: %d leaves, %d instructions, depth %d do not fit one kernel\n", n.id, t->leaves, t->instrs, t->depth);
             if (x.kind == DVec::EXPR && (y.kind != DVec::EXPR || el->instrs >= er->instrs)) x = expr_force(x);
             else if (y.kind == DVec::EXPR) y = expr_force(y);
             else return false;
@@ -502,7 +503,10 @@ struct GenExec {
         t->leaves = el->leaves + er->leaves;
         t->instrs = el->instrs + er->instrs + 1;
         t->depth = std::max(el->depth, er->depth + 1);
-        if (!expr_fits(*t)) return false;                                      // the caller forces the pending sides and goes operator by operator
+        if (!expr_fits(*t)) {                                                  // the caller forces the pending sides and goes operator by operator
+            if (trace_forms) std::fprintf(stderr, "  Id %-4d split: %d leaves, %d instructions, depth %d do not fit one kernel (entries of a selection)\n", n.id, t->leaves, t->instrs, t->depth);
+            return false;
+        }
         o = DVec{};
         o.kind = DVec::EXPR; o.n = sel->n; o.sel = sel; o.ex = t;
         if (!lazy) o = sx_force(o);

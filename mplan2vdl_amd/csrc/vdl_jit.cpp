@@ -297,11 +297,18 @@ static std::string desc_text(Kind kind, const MsArgs &C, const MScanDesc &D, con
     return o.str();
 }
 
+// a column the binder made a saturated difference (VC_SUBS): the unit then compiles that branch of the embedded code in
+static bool has_sat_diff(const MsArgs &C, const MScanDesc &D) {
+    for (int k = 0; k < C.ncol; k++) if (D.dkind[k] == VC_SUBS) return true;
+    return false;
+}
+
 std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Shape &sh) {
     std::ostringstream o;
     o << "#define VDL_SPEC_UNROLL _Pragma(\"unroll\")\n";
     const bool rt = sh.rt_bounds;
     if (rt) o << "#define VDL_RT_BOUNDS 1\n";
+    if (has_sat_diff(C, D)) o << "#define VDL_SAT_DIFF 1\n";
     if (kind == MSCAN && sh.batch) o << "#define VDL_BATCH " << sh.batch << "\n#define VDL_BATCH_NAGG " << D.nagg << "\n";
     if (kind == MSCAN && sh.census) o << "#define VDL_CENSUS 1\n";
     if (kind == MSCAN && C.packed) o << "#define VDL_PACKED 1\n";
@@ -435,6 +442,7 @@ std::string front_source(const MsArgs &Cs, const MScanDesc &Ds, const MsArgs &Ct
     std::ostringstream o;
     o << "#define VDL_SPEC_UNROLL _Pragma(\"unroll\")\n";
     if (sh.rt_bounds) o << "#define VDL_RT_BOUNDS 1\n";
+    if (has_sat_diff(Cs, Ds) || has_sat_diff(Ct, Dt)) o << "#define VDL_SAT_DIFF 1\n";
     o << "#define VDL_PROJ_U " << VDL_PROJ_U_HOST << "\n#define VDL_FRONT_BATCH " << VDL_FRONT_BATCH_HOST << "\n" << kEmbedded << "\n" << desc_text(SELECT, Cs, Ds, "_s", sh.rt_bounds) << desc_text(TAKE, Ct, Dt, "_t", sh.rt_bounds);
     const char *b = sh.vec ? "true" : "false";
     // (Q3's front: 107 VGPRs = 4 blocks per CU; asked to fit 5 or 6 waves per SIMD -- 96 / 80 registers, 12 / 76 bytes of scratch -- the pass

@@ -29,6 +29,16 @@ constexpr int kProjU = VDL_PROJ_U;
 constexpr int kProjTile = kMsBlock * 2 * kProjU;
 enum { R_SUM = 0, R_MIN = 1, R_MAX = 2 };
 
+// The saturated difference (VC_SUBS) is compiled into the precompiled kernels always, and into a specialised translation unit only
+// when its descriptor holds such a column (vdl_jit.cpp writes VDL_SAT_DIFF ahead of this text): every other unit is the code it was.
+#if !defined(VDL_SAT_DIFF) && !defined(__HIPCC_RTC__)
+#define VDL_SAT_DIFF 1
+#endif
+#if VDL_SAT_DIFF
+#define VDL_IS_DIFF(k) ((k) == VC_SUB || (k) == VC_SUBS)
+#else
+#define VDL_IS_DIFF(k) ((k) == VC_SUB)
+#endif
 __device__ __forceinline__ int rk_of(int kind) { return kind == AGG_SUM ? R_SUM : kind == AGG_MAX ? R_MAX : R_MIN; }
 __device__ __forceinline__ int64_t r_identity(int rk) { return rk == R_SUM ? 0 : rk == R_MIN ? INT64_MAX : INT64_MIN; }
 __device__ __forceinline__ int64_t r_combine(int rk, int64_t a, int64_t b) {
@@ -436,9 +446,17 @@ __device__ __forceinline__ void derive(const MsArgs &C, const MsArgs &Cr, const 
                     for (int r = 0; r < RW; r++) y[r] = v[k][r];
                 }
             }
-            if (kind == VC_SUB) {
+            if (VDL_IS_DIFF(kind)) {
 #pragma unroll
                 for (int r = 0; r < RW; r++) v[c][r] = (int64_t)((uint64_t)x[r] - (uint64_t)y[r]);
+#if VDL_SAT_DIFF
+                // VC_SUBS: where the exact difference lies outside int64 (the operands' signs differ and the result's is not x's), its
+                // nearer end -- so that its sign and its zero are the exact difference's
+                if (kind == VC_SUBS) {
+#pragma unroll
+                    for (int r = 0; r < RW; r++) if (((x[r] ^ y[r]) & (x[r] ^ v[c][r])) < 0) v[c][r] = x[r] < 0 ? INT64_MIN : INT64_MAX;
+                }
+#endif
                 if ((C.filtered >> c) & 1u) {               // (the projection scan has no second look at the filters: fold it here)
                     int64_t lo, hi;
                     range_bounds(D.flo[c], D.fhi[c], Dr.flo[c], Dr.fhi[c], lo, hi);

@@ -49,6 +49,8 @@ enum VColKind : int {
     VC_LUT = 3,      // value = prelude[prelude] (a lookup table) at v[idx]; outside the table -> 0 (Like over heap offsets)
     VC_INRANGE = 4,  // value = 1; the row is EPS unless 0 <= v[idx] < rows of column `name` (a Gather out of an unfiltered table)
     VC_SUB = 5,      // value = v[idx] - v[idx2] (column against column comparisons become a range filter on the difference)
+    VC_SUBS = 8,     // value = v[idx] - v[idx2] SATURATED at the ends of int64: what the binder makes of a VC_SUB that stands for an order
+                     // comparison (a > b as a - b in [1, max]) over operands wide enough for the wrap-around difference to change sign
     VC_ROWID = 7,    // value = the row's own index in the scanned table (the index of a lookup into a set built over this table's rows:
                      // the semi-join bitmap of PreludeItem::SEMI_BITMAP)
     VC_FORM = 6      // value = 0 / 1: a boolean formula over range tests of earlier columns (ScanColumn::form) -- IN lists, disjunctions

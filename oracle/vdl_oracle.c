@@ -361,9 +361,10 @@ static int op_scatter(orc_ctx *c, ovec *out, const ovec *src, const ovec *fold, 
 static int64_t bucket_of(const ovec *piv, int64_t x) {
     if (piv->is_range && piv->step == 1) {
         if (x <= piv->from) return 0;
-        int64_t b = w_sub(x, piv->from);
-        return b < piv->n ? b : piv->n;          /* beyond the last pivot: overflow bucket */
+        int64_t b = w_sub(x, piv->from);         /* x > from: the exact difference is 1 .. 2^64-1; 2^63 and more wrap to b < 0 */
+        return (b < 0 || b >= piv->n) ? piv->n : b;   /* beyond the last pivot: overflow bucket */
     }
+    /* (general pivots: comparisons only, no difference to wrap) */
     int64_t lo = 0, hi = piv->n;                 /* lower_bound over ascending pivots */
     while (lo < hi) { int64_t mid = lo + (hi - lo) / 2; if (slot_val(piv, mid) < x) lo = mid + 1; else hi = mid; }
     return lo;
