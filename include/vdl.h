@@ -115,8 +115,23 @@ int  vdl_column_packed_info(const vdl_ctx *ctx, const char *name, int *bits, int
 int  vdl_download_packed_image(vdl_ctx *ctx, const char *name, void *host_ptr, size_t bytes);
 /* contexts without a device (vdl_plan_jit_check): declare a registered column's packed image (no bytes behind it) */
 int  vdl_declare_packed_image(vdl_ctx *ctx, const char *name, int bits, int64_t base, int64_t scale);
+/* contexts without a device (vdl_plan_jit_check): declare a registered column's byte image (no bytes behind it): width 1, 2 or 4 and
+ * narrower than the column, scale >= 1.  Scans and lookups bound on that context treat it like an image a device built. */
+int  vdl_declare_column_image(vdl_ctx *ctx, const char *name, int width, int64_t base, int64_t scale);
 /* on = 0: scans bind the catalog columns and ignore the images (tests, A/B comparisons in one process); default 1 */
 int  vdl_set_column_images(vdl_ctx *ctx, int on);
+/* Lookup images.  A dimension column looked up through a join index -- p_type at lineitem_part[row], o_orderdate at
+ * lineitem_orders[row] -- is by default read from the catalog column at its stored width.  on = 1: where the target column has a byte
+ * image and the use of the looked-up value allows it, every scan role reads the image at v[index] instead -- a quarter or an eighth of
+ * the table for the caches to hold --, by the rules of the streamed columns: a value used only in a range filter, a formula test or
+ * an aggregate factor stays encoded (bounds and factors rewritten); a value an aggregate scan needs as stored (the source of another
+ * lookup, a group-key load, a FIRST column) takes a pure narrowing only; in fronts, dimension and semi-join scans a value needed per
+ * row (the source of a further lookup or of a difference, a semi-join position) takes an image of scale 1 and is decoded after the
+ * lookup; the take side of a front decodes whatever it looks up, at any scale.  An index outside the target's rows makes the row EPS
+ * as before.  Results are bit-identical.  Off by default (VDL_LOOKUP_IMAGES=1 in the environment when the context opens switches it
+ * on); ignored while vdl_set_column_images(ctx, 0).  Flipping it re-binds bound plans at their next run.  Kernels that read a
+ * lookup image carry ",limg" in the names vdl_plan_jit_note and the timings list.  Bit-packed and step images are not read by lookups. */
+int  vdl_set_lookup_images(vdl_ctx *ctx, int on);
 
 /* ---- step images ------------------------------------------------------------------
  * A column that never decreases and whose consecutive rows differ by 0 or 1 -- the join index of a table clustered by its
@@ -202,6 +217,10 @@ int  vdl_plan_image_columns(const vdl_plan *plan, const char **list);
  * not listed under that role by vdl_plan_image_columns.  Kernels that read a step image carry ",stp" in the names
  * vdl_plan_jit_note lists. */
 int  vdl_plan_step_columns(const vdl_plan *plan, const char **list);
+/* Likewise the TARGET columns the plan's lookups read from their images (vdl_set_lookup_images), "table.column:width" per scan role,
+ * e.g. "front.take: orders.o_orderdate:2 orders.o_shippriority:1" or "scan0: part.p_type:2".  Lookup targets are never listed by
+ * vdl_plan_image_columns, which speaks of the columns a scan streams.  "" when no lookup reads an image. */
+int  vdl_plan_lookup_columns(const vdl_plan *plan, const char **list);
 
 /* Execute: binds Loads to the catalog, runs all kernels, copies the MaterializeCompact
  * outputs to the host and synchronises. */
@@ -370,7 +389,9 @@ int  vdl_plan_scan_stats(const vdl_plan *plan, int64_t *rows, int64_t *algo_byte
  * late (vdl_plan_set_jit: staged reads) moves the eager columns in full plus 128 bytes for every cache line of a late
  * column in which some row was still in when the column was read -- the memory side fetches whole 128-byte lines
  * (tools/ubench/fetch_calib.hip) -- and that number is COUNTED: a census build of the same kernel form runs once.
- * `detail` (may be null): "column=bytes ..." text, valid until the next call. */
+ * `detail` (may be null): "column=bytes ..." text, valid until the next call.
+ * Only the lines of the scanned (fact) table are counted: what the scan's lookups fetch on the dimension side -- catalog columns or,
+ * under vdl_set_lookup_images, their images -- is not part of this number. */
 int  vdl_plan_scan_traffic(vdl_ctx *ctx, vdl_plan *plan, int64_t *bytes_moved, const char **detail);
 
 /* ---- sharded execution: one process per GPU, columns sharded by row range --------

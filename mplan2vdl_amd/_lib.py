@@ -60,6 +60,9 @@ def load():
         "vdl_column_steps_info": (i32, [vp, cp, P(i32), P(i64), P(i64)]),
         "vdl_download_steps_image": (i32, [vp, cp, vp, vp, i64]),
         "vdl_declare_steps_image": (i32, [vp, cp, i64]),
+        "vdl_declare_column_image": (i32, [vp, cp, i32, i64, i64]),
+        "vdl_set_lookup_images": (i32, [vp, i32]),
+        "vdl_plan_lookup_columns": (i32, [vp, P(ctypes.c_char_p)]),
         "vdl_set_step_images": (i32, [vp, i32]),
         "vdl_parse": (i32, [vp, cp, ctypes.c_size_t, P(vp)]),
         "vdl_plan_free": (None, [vp]),
@@ -139,7 +142,7 @@ ABI_SYMBOLS = [
     "vdl_upload_column", "vdl_generate_column", "vdl_drop_column", "vdl_column_info", "vdl_download_column",
     "vdl_encode_column", "vdl_column_image_info", "vdl_column_packed_info", "vdl_download_packed_image", "vdl_declare_packed_image",
     "vdl_set_column_images", "vdl_encode_steps", "vdl_column_steps_info", "vdl_download_steps_image", "vdl_declare_steps_image", "vdl_set_step_images",
-    "vdl_plan_step_columns",
+    "vdl_plan_step_columns", "vdl_declare_column_image", "vdl_set_lookup_images", "vdl_plan_lookup_columns",
     "vdl_parse", "vdl_plan_free", "vdl_plan_describe", "vdl_plan_is_fused", "vdl_plan_set_fusion",
     "vdl_plan_set_profiling", "vdl_plan_set_jit", "vdl_plan_set_jit_bounds", "vdl_jit_counters", "vdl_plan_jit_note", "vdl_plan_jit_check", "vdl_plan_image_columns", "vdl_plan_set_trace", "vdl_n_traced", "vdl_traced", "vdl_run", "vdl_run_batch", "vdl_batch_jit_check", "vdl_plan_batch_note", "vdl_plan_batch_code_bytes", "vdl_set_batch_grouped", "vdl_n_outputs", "vdl_output", "vdl_plan_set_device_outputs", "vdl_output_device", "vdl_n_timings", "vdl_timing",
     "vdl_plan_set_order", "vdl_plan_order_note", "vdl_order_host", "vdl_plan_set_order_sharded", "vdl_order_merge_host",

@@ -93,6 +93,23 @@ inline bool usable(const Image &im, bool raw_use) { return im.width > 0 && (im.p
 // row expressions), once per survivor, at any scale; a carried column travels decoded, or is not carried.  A pure narrowing decodes
 // to itself and costs nothing.
 inline bool usable_in_vscan(const Image &im, bool per_row_value) { return im.width > 0 && (im.scale == 1 || !per_row_value); }
+// The target of a lookup (VC_GATHER: dimension column `name` at row v[idx]) read from its image -- a lookup image -- is bound by the
+// very rules of a streamed column, applied to the use of the LOOKED-UP value: usable() in an aggregate scan (a source of another
+// derived column, a load of the group key and a FIRST column are raw uses: pure narrowings only), usable_in_vscan() in a scan with
+// derived columns (the source of a further lookup or of a difference and a semi-join position are per-row values: scale 1, decoded
+// right after the lookup, filters as planned).  Every other lookup stays encoded: map_range over its filter and formula tests,
+// compose over its aggregate factors.  The index is checked against the target's row count as before; the image has as many entries.
+// What the binder does with a lookup image it may read (tests/test_lookup_images_cpu.py checks both ways against brute force):
+enum LookupUse { LOOKUP_CATALOG = 0,      // not readable here: the catalog column
+                 LOOKUP_ENCODED = 1,      // read and left encoded: bounds through map_range, factors through compose
+                 LOOKUP_DECODED = 2 };    // read and decoded after the lookup (MsArgs::decode): bounds and tests as planned
+// in an aggregate scan (raw_use: as usable()) -- never decoded: a raw use admits only a pure narrowing, whose encoded values are the column's
+inline LookupUse lookup_use(const Image &im, bool raw_use) { return usable(im, raw_use) ? LOOKUP_ENCODED : LOOKUP_CATALOG; }
+// in a scan with derived columns (per_row_value: as usable_in_vscan())
+inline LookupUse lookup_use_in_vscan(const Image &im, bool per_row_value) {
+    if (!usable_in_vscan(im, per_row_value)) return LOOKUP_CATALOG;
+    return per_row_value && !im.pure() ? LOOKUP_DECODED : LOOKUP_ENCODED;
+}
 // the kernels must decode the column's values (MsArgs::decode)
 inline bool needs_decode(const Image &im) { return im.width > 0 && !im.pure(); }
 

@@ -160,6 +160,18 @@ std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols,
         if (((cols.image & which) >> k) & 1u) t += (t.empty() ? "" : " ") + sc[(size_t)k].name + ":" + std::to_string(cols.width[k]);
     return t;
 }
+// ... the target columns its lookups read from their images (MScanCols::limage): its entry in vdl_plan_lookup_columns
+std::string lookup_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which) {
+    std::string t;
+    for (int k = 0; k < cols.ncol && (size_t)k < sc.size(); k++)
+        if (((cols.limage & which) >> k) & 1u) t += (t.empty() ? "" : " ") + sc[(size_t)k].name + ":" + std::to_string(cols.width[k]);
+    return t;
+}
+// the image a lookup may read in place of its target column: lookup images are on (vdl_set_lookup_images, under vdl_set_column_images)
+// and the column has a byte image -- built on the device, or declared on a context without one (vdl_declare_column_image)
+static bool has_lookup_image(const vdl_ctx *c, const Column &col) {
+    return c->images && c->lookup_images && col.image.width > 0 && (col.image_buf || c->device < 0);
+}
 // ... and from their step images, "name:s ...": its entry in vdl_plan_step_columns
 std::string step_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which) {
     std::string t;
@@ -191,11 +203,11 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
                 throw Error(VDL_ERR_SHAPE, "columns of table '" + sp.table + "' have different lengths in the catalog");
             n = col.n;
             cols.ptr[k] = col.dev; cols.width[k] = col.width;
-            if (c->images && col.image_buf && img::usable(col.image, (raw >> k) & 1u)) {
+            if (c->images && (col.image_buf || c->device < 0) && img::usable(col.image, (raw >> k) & 1u)) {      // (no device: a declared image)
                 // the image instead of the column: its bounds in the encoded domain (the filtered bit stays what the plan says)
                 ims[k] = col.image;
                 cols.image |= 1u << k;
-                cols.ptr[k] = col.image_buf->p; cols.width[k] = col.image.width;
+                cols.ptr[k] = col.image_buf ? col.image_buf->p : nullptr; cols.width[k] = col.image.width;
                 img::map_range(col.image, sc.lo, sc.hi, &cols.lo[k], &cols.hi[k]);
             }
             img::Image pim;                                           // the packed image as an image: for the rules and compose
@@ -214,6 +226,13 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
             const Column &col = find_col(c, sc.name);
             cols.ptr[k] = col.dev; cols.width[k] = col.width;
             d.dn[k] = col.n;
+            if (sc.kind == VC_GATHER && has_lookup_image(c, col) && img::lookup_use(col.image, (raw >> k) & 1u) == img::LOOKUP_ENCODED) {
+                // the lookup image: the looked-up value stays encoded, its bounds, tests and factors rewritten like a streamed column's
+                ims[k] = col.image;
+                cols.limage |= 1u << k;
+                cols.ptr[k] = col.image_buf ? col.image_buf->p : nullptr; cols.width[k] = col.image.width;
+                img::map_range(col.image, sc.lo, sc.hi, &cols.lo[k], &cols.hi[k]);
+            }
         } else {                                                          // VC_BITS / VC_LUT: filled in by run_prelude before every launch
             cols.ptr[k] = nullptr; cols.width[k] = 8;
             d.dn[k] = 0;
@@ -224,7 +243,7 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
     for (int k = 0; k < cols.ncol; k++)                               // a formula's tests of a column read from its image
         if (cols.kind[k] == VC_FORM)
             for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dtests[k]; f++)
-                if (d.form[f].col >= 0 && ((cols.image >> d.form[f].col) & 1u)) img::map_range(ims[d.form[f].col], d.form[f].lo, d.form[f].hi, &d.form[f].lo, &d.form[f].hi);
+                if (d.form[f].col >= 0 && (((cols.image | cols.limage) >> d.form[f].col) & 1u)) img::map_range(ims[d.form[f].col], d.form[f].lo, d.form[f].hi, &d.form[f].lo, &d.form[f].hi);
     cols.n = n;
     cols.row0 = row0;
     cols.rowid_global = rowid_counts_from_the_table(sp.cols);
@@ -235,7 +254,7 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
         m.constant = ag.constant;
         for (const ScanFactor &f : ag.fac) {
             int64_t a = f.a, s = f.s;
-            if ((cols.image >> f.col) & 1u) img::compose(ims[f.col], f.a, f.s, &a, &s);     // a + s * (base + scale * e)
+            if (((cols.image | cols.limage) >> f.col) & 1u) img::compose(ims[f.col], f.a, f.s, &a, &s);     // a + s * (base + scale * e)
             m.used |= 1u << f.col;
             if (img::plain(a, s)) m.plain |= 1u << f.col;
             m.fa[f.col] = a; m.fs[f.col] = s;
@@ -256,6 +275,7 @@ namespace {
 static std::string mscan_label(const ScanLaunch &cfg, const MScanCols &cols) {
     std::string n = mscan_kernel_name(cfg);
     if (cols.image && !n.empty() && n.back() == '>') n.insert(n.size() - 1, ",img");
+    if (cols.limage && !n.empty() && n.back() == '>') n.insert(n.size() - 1, ",limg");      // (a lookup reads its target's image)
     return n;
 }
 // blocks a specialised scan may be launched with, whatever rows-per-lane the tuner settles on: the partials area is sized for it
@@ -280,6 +300,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
     p->jit_note.clear();
     p->jit_builds.clear();
     for (auto it = p->image_roles.begin(); it != p->image_roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->image_roles.erase(it) : std::next(it);
+    for (auto it = p->lookup_roles.begin(); it != p->lookup_roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->lookup_roles.erase(it) : std::next(it);
     p->jit_tuned = false;
     p->gword_offset.assign(ng, 0);
     p->reduce_ops.clear();
@@ -326,6 +347,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
             bpr = 0;
             n = bind_mscan(c, sp, p->mcols[s], p->mdesc[s], &bpr, p->row_offset);
             p->image_roles["scan" + std::to_string(s)] = image_text(sp.cols, p->mcols[s]);
+            p->lookup_roles["scan" + std::to_string(s)] = lookup_text(sp.cols, p->mcols[s]);
             p->mcfg[s] = mscan_launch_config(p->mcols[s], p->mdesc[s], false, c->num_cus);
             if (p->mcfg[s].variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no multi-aggregate scan kernel variant for this shape");
             std::string jname;
@@ -346,6 +368,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         int64_t bpr = 0;
         const int64_t n = bind_mscan(c, gp, p->mcols[m], p->mdesc[m], &bpr, p->row_offset);
         p->image_roles["scan" + std::to_string(m)] = image_text(gp.cols, p->mcols[m]);
+        p->lookup_roles["scan" + std::to_string(m)] = lookup_text(gp.cols, p->mcols[m]);
         MScanDesc &d = p->mdesc[m];
         p->mcfg[m] = mscan_launch_config(p->mcols[m], d, true, c->num_cus);
         if (p->mcfg[m].variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no grouped-scan kernel variant for this shape");
@@ -399,10 +422,10 @@ static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vecto
                 d.ibase[k] = col.steps.base;
                 // (its values are base .. base + n - 1 at most: where they fit 32 signed bits the kernels make the sum in 32)
                 cols.width[k] = col.steps.base >= INT32_MIN && col.steps.base <= (int64_t)INT32_MAX - col.n ? 4 : 8;
-            } else if (c->images && col.image_buf && img::usable_in_vscan(col.image, (per_row >> k) & 1u)) {
+            } else if (c->images && (col.image_buf || c->device < 0) && img::usable_in_vscan(col.image, (per_row >> k) & 1u)) {
                 ims[k] = col.image;
                 cols.image |= 1u << k;
-                cols.ptr[k] = col.image_buf->p; cols.width[k] = col.image.width;
+                cols.ptr[k] = col.image_buf ? col.image_buf->p : nullptr; cols.width[k] = col.image.width;
                 d.ibase[k] = col.image.base; d.iscale[k] = col.image.scale;
                 if (img::needs_decode(col.image) && ((per_row >> k) & 1u)) {
                     cols.decode |= 1u << k;
@@ -415,6 +438,21 @@ static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vecto
             const Column &col = find_col(c, s.name);
             cols.ptr[k] = col.dev; cols.width[k] = col.width;
             d.dn[k] = col.n;
+            const img::LookupUse use = s.kind == VC_GATHER && has_lookup_image(c, col) ? img::lookup_use_in_vscan(col.image, (per_row >> k) & 1u) : img::LOOKUP_CATALOG;
+            if (use != img::LOOKUP_CATALOG) {
+                // the lookup image: a looked-up value the pass needs per row is decoded after the lookup (scale 1) and keeps the plan's
+                // filters; every other one stays encoded, its filter (and, below, its formula tests) rewritten
+                ims[k] = col.image;
+                cols.limage |= 1u << k;
+                cols.ptr[k] = col.image_buf ? col.image_buf->p : nullptr; cols.width[k] = col.image.width;
+                d.ibase[k] = col.image.base; d.iscale[k] = col.image.scale;
+                if (use == img::LOOKUP_DECODED) {
+                    cols.decode |= 1u << k;
+                } else {
+                    img::map_range(col.image, s.lo, s.hi, &cols.lo[k], &cols.hi[k]);
+                    d.flo[k] = cols.lo[k]; d.fhi[k] = cols.hi[k];
+                }
+            }
         } else {
             cols.ptr[k] = nullptr; cols.width[k] = 8;
             if (s.prelude >= 0) wanted[(size_t)s.prelude] = 1;
@@ -424,7 +462,7 @@ static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vecto
     for (int k = 0; k < cols.ncol; k++)                               // a formula's tests of a column read from its image
         if (cols.kind[k] == VC_FORM)
             for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dtests[k]; f++)
-                if (d.form[f].col >= 0 && (((cols.image & ~cols.decode) >> d.form[f].col) & 1u))
+                if (d.form[f].col >= 0 && ((((cols.image | cols.limage) & ~cols.decode) >> d.form[f].col) & 1u))
                     img::map_range(ims[d.form[f].col], d.form[f].lo, d.form[f].hi, &d.form[f].lo, &d.form[f].hi);
     cols.n = n;
     return n;
@@ -438,14 +476,14 @@ static PassSource select_pass(const MScanCols &cols, const MScanDesc &d, bool rt
     jit::Shape sh;
     sh.nc = cols.ncol; sh.u = 4; sh.vec = project_select_vec(cols); sh.der = true; sh.rt_bounds = rt;
     return {jit::scan_source(jit::SELECT, mscan_args(cols), d, sh),
-            std::string(jit::entry_name(jit::SELECT)) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + (cols.steps ? ",stp" : "") + (rt ? ",rtb" : "") + ">", jit::entry_name(jit::SELECT)};
+            std::string(jit::entry_name(jit::SELECT)) + "<" + std::to_string(sh.nc) + (cols.image ? ",img" : "") + (cols.limage ? ",limg" : "") + (cols.steps ? ",stp" : "") + (rt ? ",rtb" : "") + ">", jit::entry_name(jit::SELECT)};
 }
 // the one-pass front: two descriptors in one kernel (jit::front_source)
 static PassSource one_pass_front(const MScanCols &scols, const MScanDesc &sd, const MScanCols &tcols, const MScanDesc &td, bool rt) {
     jit::Shape sh;
     sh.nc = scols.ncol; sh.u = 4; sh.vec = project_select_vec(scols); sh.der = true; sh.rt_bounds = rt;
     return {jit::front_source(mscan_args(scols), sd, mscan_args(tcols), td, sh, tcols.ncol),
-            std::string(jit::entry_name(jit::FRONT)) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ((scols.image | tcols.image) ? ",img" : "") + ((scols.steps | tcols.steps) ? ",stp" : "") + (rt ? ",rtb" : "") + ">",
+            std::string(jit::entry_name(jit::FRONT)) + "<" + std::to_string(sh.nc) + "," + std::to_string(tcols.ncol) + ((scols.image | tcols.image) ? ",img" : "") + ((scols.limage | tcols.limage) ? ",limg" : "") + ((scols.steps | tcols.steps) ? ",stp" : "") + (rt ? ",rtb" : "") + ">",
             jit::entry_name(jit::FRONT)};
 }
 // Compiles the pass and writes its line of the note: "role: entry<shape[,img]>, N B of code; ".  A run loads the kernel and falls back
@@ -545,6 +583,7 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         const int64_t n = bind_vcols(c, it.table, it.cols, cols, *d, unused, pos);
         p->image_roles[(semi ? "semi" : "dim") + std::to_string(k)] = image_text(it.cols, cols);
         p->step_roles[(semi ? "semi" : "dim") + std::to_string(k)] = step_text(it.cols, cols);
+        p->lookup_roles[(semi ? "semi" : "dim") + std::to_string(k)] = lookup_text(it.cols, cols);
         patch_prelude(p, it.cols, cols, *d);
         if (semi) {
             // the set of rows of another table that a selected row of this one points at: one scan, atomic ORs
@@ -886,6 +925,7 @@ static void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b) {
         scols.lo[j] = cols.lo[k]; scols.hi[j] = cols.hi[k]; scols.kind[j] = cols.kind[k];
         sdesc->flo[j] = d.flo[k]; sdesc->fhi[j] = d.fhi[k]; sdesc->dkind[j] = d.dkind[k]; sdesc->dn[j] = d.dn[k]; sdesc->dtests[j] = d.dtests[k];
         scols.image |= ((cols.image >> k) & 1u) << j; scols.decode |= ((cols.decode >> k) & 1u) << j; scols.steps |= ((cols.steps >> k) & 1u) << j;
+        scols.limage |= ((cols.limage >> k) & 1u) << j;
         sdesc->ibase[j] = d.ibase[k]; sdesc->iscale[j] = d.iscale[k];
         if (d.dkind[k] == VC_FORM) {                          // its steps stay where they are in the pool; the tests' columns are
             sdesc->dsrc[j] = d.dsrc[k]; sdesc->dsrc2[j] = d.dsrc2[k];      // renumbered (monotonic: they stay sorted by column)
@@ -903,7 +943,7 @@ static void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b) {
     const uint32_t sel_decode = cols.decode;
     cols.decode = 0;
     for (int k = 0; k < cols.ncol; k++) {
-        if (!((cols.image >> k) & 1u)) continue;
+        if (!(((cols.image | cols.limage) >> k) & 1u)) continue;       // (a lookup image too: decoded right after the lookup)
         d.flo[k] = J.cols[(size_t)k].lo; d.fhi[k] = J.cols[(size_t)k].hi;
         if (d.ibase[k] != 0 || d.iscale[k] != 1) cols.decode |= 1u << k;
     }
@@ -946,6 +986,8 @@ static void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b) {
     p->image_roles["front.take"] = image_text(J.cols, cols, d.take);
     p->step_roles["front.select"] = step_text(J.cols, cols, deciding);
     p->step_roles["front.take"] = step_text(J.cols, cols, d.take);
+    p->lookup_roles["front.select"] = lookup_text(J.cols, cols, deciding);
+    p->lookup_roles["front.take"] = lookup_text(J.cols, cols, d.take);
 }
 // the prelude's tables of this run, in both passes' arguments
 static void patch_front(const vdl_plan *p, FrontBound &b) {
@@ -1090,6 +1132,7 @@ int vdl_open(vdl_ctx **out, int device) {
     int rc = guard(c, [&] {
         c->device = device;
         { const char *g = getenv("VDL_BATCH_GROUPED"); c->batch_grouped = g && *g && *g != '0'; }
+        { const char *g = getenv("VDL_LOOKUP_IMAGES"); c->lookup_images = g && *g && *g != '0'; }
         if (device >= 0) {
             int count = 0;
             if (hipGetDeviceCount(&count) != hipSuccess || device >= count)
@@ -1367,6 +1410,28 @@ int vdl_set_step_images(vdl_ctx *c, int on) {
     });
 }
 
+int vdl_set_lookup_images(vdl_ctx *c, int on) {
+    if (!c) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        if (c->lookup_images != (on != 0)) c->catalog_version++;      // bound plans re-bind
+        c->lookup_images = on != 0;
+    });
+}
+
+int vdl_declare_column_image(vdl_ctx *c, const char *name, int width, int64_t base, int64_t scale) {
+    if (!c || !name) return VDL_ERR_ARG;
+    return guard(c, [&] {
+        if (c->device >= 0) throw Error(VDL_ERR_ARG, "column images are declared only on a context without a device (a device builds them)");
+        if ((width != 1 && width != 2 && width != 4) || scale < 1) throw Error(VDL_ERR_ARG, "width must be 1, 2 or 4 and scale be positive");
+        auto it = c->cols.find(name);
+        if (it == c->cols.end()) throw Error(VDL_ERR_COLUMN, std::string("no column '") + name + "'");
+        if (width >= it->second.width) throw Error(VDL_ERR_ARG, "an image is narrower than its column");
+        it->second.image.width = width; it->second.image.base = base; it->second.image.scale = scale;
+        it->second.image_buf.reset();
+        c->catalog_version++;
+    });
+}
+
 int vdl_column_image_info(const vdl_ctx *c, const char *name, int *width, int64_t *base, int64_t *scale) {
     if (!c || !name) return VDL_ERR_ARG;
     auto it = c->cols.find(name);
@@ -1512,6 +1577,14 @@ int vdl_plan_image_columns(const vdl_plan *p, const char **list) {
     *list = p->image_list.c_str();
     return VDL_OK;
 }
+int vdl_plan_lookup_columns(const vdl_plan *p, const char **list) {
+    if (!p || !list) return VDL_ERR_ARG;
+    p->lookup_list.clear();
+    for (const auto &r : p->lookup_roles)
+        if (!r.second.empty()) p->lookup_list += (p->lookup_list.empty() ? "" : "; ") + r.first + ": " + r.second;
+    *list = p->lookup_list.c_str();
+    return VDL_OK;
+}
 int vdl_plan_step_columns(const vdl_plan *p, const char **list) {
     if (!p || !list) return VDL_ERR_ARG;
     p->step_list.clear();
@@ -1542,6 +1615,7 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
                 const std::string role = (semi ? "semi" : "dim") + std::to_string(k);
                 p->image_roles[role] = image_text(it.cols, cols);
                 p->step_roles[role] = step_text(it.cols, cols);
+                p->lookup_roles[role] = lookup_text(it.cols, cols);
                 d->bitmap_only = semi ? 2 : 1;
                 if (semi) { d->pmin = it.modulus; d->nout = 1; d->out_col[0] = it.index_col; }
                 build_pass(c, p, role, select_pass(cols, *d, p->jit_rt_bounds), true);

@@ -209,6 +209,7 @@ struct vdl_ctx {
     uint64_t catalog_version = 1;      // bumped on every catalog change: plans re-bind only when it moved
     bool images = true;                // aggregate scans read the columns' images where the rules allow (vdl_set_column_images)
     bool step_images = true;           // ... and fronts, dimension and semi-join scans the step images (vdl_set_step_images)
+    bool lookup_images = false;        // lookups (VC_GATHER) read the images of their target columns (vdl_set_lookup_images, VDL_LOOKUP_IMAGES=1); ignored while !images
     const std::map<std::string, Column> *overlay = nullptr;     // columns that stand in for catalog entries during one run (vdl_comm.cpp: sharded_replicate)
     uint64_t overlay_epoch = 0;                                  // moves whenever the overlay is set or cleared
     // what bindings and kernels specialised for column addresses / widths / lengths are keyed by: the catalog's state AND the overlay's
@@ -333,6 +334,9 @@ struct vdl_plan {
     mutable std::string image_list;          // what vdl_plan_image_columns handed out last
     // likewise the columns read from their step images, "name:s ..." (vdl_plan_step_columns): such a column is not in image_roles
     std::map<std::string, std::string> step_roles;
+    // ... and the target columns its lookups read from their images, "name:width ..." (vdl_plan_lookup_columns): not in image_roles either
+    std::map<std::string, std::string> lookup_roles;
+    mutable std::string lookup_list;
     mutable std::string step_list;
     std::vector<BufP> prelude_buf;           // fused join scans: dimension bitmaps / LIKE tables of the current run (FusedPlan::prelude)
     std::vector<int64_t> prelude_n;
@@ -503,6 +507,7 @@ int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, i
 bool use_kscan(const ScanPlan &sp);
 std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
 std::string step_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
+std::string lookup_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
 // Sharded entry points and a plan with an order set.  merges = the entry point runs the collectives itself (vdl_run_sharded*): it
 // accepts the plan once vdl_plan_set_order_sharded has switched the merged order on.  The others (vdl_run_local, vdl_exchange_begin)
 // leave the collectives to their caller and refuse it either way -- except inside vdl_run_sharded's own calls (order_inside).

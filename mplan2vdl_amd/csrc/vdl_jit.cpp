@@ -303,12 +303,17 @@ static bool has_sat_diff(const MsArgs &C, const MScanDesc &D) {
     return false;
 }
 
+// a lookup that reads the image of its target column and is decoded after the lookup (MsArgs::decode among the derived columns): the
+// unit then compiles that step of the embedded code in (VDL_LOOKUP_DECODE); every other unit is the code it was
+static bool has_lookup_decode(const MsArgs &C) { return (C.decode & C.derived) != 0; }
+
 std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Shape &sh) {
     std::ostringstream o;
     o << "#define VDL_SPEC_UNROLL _Pragma(\"unroll\")\n";
     const bool rt = sh.rt_bounds;
     if (rt) o << "#define VDL_RT_BOUNDS 1\n";
     if (has_sat_diff(C, D)) o << "#define VDL_SAT_DIFF 1\n";
+    if (has_lookup_decode(C)) o << "#define VDL_LOOKUP_DECODE 1\n";
     if (kind == MSCAN && sh.batch) o << "#define VDL_BATCH " << sh.batch << "\n#define VDL_BATCH_NAGG " << D.nagg << "\n";
     if (kind == MSCAN && sh.census) o << "#define VDL_CENSUS 1\n";
     if (kind == MSCAN && C.packed) o << "#define VDL_PACKED 1\n";
@@ -443,6 +448,7 @@ std::string front_source(const MsArgs &Cs, const MScanDesc &Ds, const MsArgs &Ct
     o << "#define VDL_SPEC_UNROLL _Pragma(\"unroll\")\n";
     if (sh.rt_bounds) o << "#define VDL_RT_BOUNDS 1\n";
     if (has_sat_diff(Cs, Ds) || has_sat_diff(Ct, Dt)) o << "#define VDL_SAT_DIFF 1\n";
+    if (has_lookup_decode(Cs) || has_lookup_decode(Ct)) o << "#define VDL_LOOKUP_DECODE 1\n";
     o << "#define VDL_PROJ_U " << VDL_PROJ_U_HOST << "\n#define VDL_FRONT_BATCH " << VDL_FRONT_BATCH_HOST << "\n" << kEmbedded << "\n" << desc_text(SELECT, Cs, Ds, "_s", sh.rt_bounds) << desc_text(TAKE, Ct, Dt, "_t", sh.rt_bounds);
     const char *b = sh.vec ? "true" : "false";
     // (Q3's front: 107 VGPRs = 4 blocks per CU; asked to fit 5 or 6 waves per SIMD -- 96 / 80 registers, 12 / 76 bytes of scratch -- the pass

@@ -39,6 +39,18 @@ enum { R_SUM = 0, R_MIN = 1, R_MAX = 2 };
 #else
 #define VDL_IS_DIFF(k) ((k) == VC_SUB)
 #endif
+// The decode of a lookup image right after the lookup (derive(), the bits MsArgs::decode has among the derived columns) likewise: always
+// in the precompiled kernels, in a specialised unit only when one of its descriptors holds such a lookup (vdl_jit.cpp writes
+// VDL_LOOKUP_DECODE ahead of this text).  A branch on a constant that folds away was not enough: the units of Q14, Q12 and Q19 came out
+// with the same instructions in another order.
+#if !defined(VDL_LOOKUP_DECODE) && !defined(__HIPCC_RTC__)
+#define VDL_LOOKUP_DECODE 1
+#endif
+#if VDL_LOOKUP_DECODE
+#define VDL_TILE_DECODE(C) ((C).decode & ~(C).derived)      // (a lookup's bit: decoded where it is looked up)
+#else
+#define VDL_TILE_DECODE(C) ((C).decode)
+#endif
 __device__ __forceinline__ int rk_of(int kind) { return kind == AGG_SUM ? R_SUM : kind == AGG_MAX ? R_MAX : R_MIN; }
 __device__ __forceinline__ int64_t r_identity(int rk) { return rk == R_SUM ? 0 : rk == R_MIN ? INT64_MAX : INT64_MIN; }
 __device__ __forceinline__ int64_t r_combine(int rk, int64_t a, int64_t b) {
@@ -259,7 +271,7 @@ template <int NC, int RW>
 __device__ __forceinline__ void decode_tile(const MsArgs &C, const MScanDesc &D, int64_t (&v)[NC][RW]) {
 #pragma unroll
     for (int c = 0; c < NC; c++) {
-        if ((C.decode >> c) & 1u) {                        // wave-uniform
+        if ((VDL_TILE_DECODE(C) >> c) & 1u) {               // wave-uniform
             const uint64_t ib = (uint64_t)D.ibase[c];
 #pragma unroll
             for (int r = 0; r < RW; r++) v[c][r] = (int64_t)((uint64_t)v[c][r] + ib);
@@ -477,6 +489,15 @@ __device__ __forceinline__ void derive(const MsArgs &C, const MsArgs &Cr, const 
                 int64_t q[RW];
 #pragma unroll
                 for (int r = 0; r < RW; r++) { q[r] = 0; if (in[r]) q[r] = load_scalar(t, w, x[r]); }
+                // a lookup image (the byte image of the target column, vdl_column_image.h) whose values the scan needs as the column
+                // holds them -- the source of a further lookup or of a difference, a semi-join position, anything the take side of a
+                // front loads: decoded here, once the loads are out; every other lookup image stays encoded, its bounds rewritten
+#if VDL_LOOKUP_DECODE
+                if ((C.decode >> c) & 1u) {                 // wave-uniform
+#pragma unroll
+                    for (int r = 0; r < RW; r++) if (in[r]) q[r] = img_decode(q[r], D.ibase[c], D.iscale[c]);
+                }
+#endif
 #pragma unroll
                 for (int r = 0; r < RW; r++) { v[c][r] = q[r]; alive[r] = in[r]; }
             } else if (kind == VC_BITS) {

@@ -104,6 +104,9 @@ struct MScanCols {                           // host-side description of a scan'
     int lazy[kMaxVCols] = {};                // projection scan: the column decides nothing about a row's survival -- read it for survivors only
     uint32_t image = 0;                      // bit c: column c is read from its frame-of-reference image (vdl_column_image.h; bounds rewritten)
     uint32_t decode = 0;                     // bit c: ... and decoded by the kernel (MsArgs::decode)
+    // bit c: the lookup c (VC_GATHER) reads the image of its target column, a LOOKUP IMAGE (vdl_set_lookup_images): ptr[c] / width[c] are
+    // the image's, its bounds are rewritten or `decode` names it.  A mask of its own: `image` speaks of the streamed table columns only
+    uint32_t limage = 0;
     uint32_t packed = 0;                     // bit c: read from its bit-packed image (MsArgs::packed), pbits[c] bits per row
     int pbits[kMaxVCols] = {};
     uint32_t steps = 0;                      // bit c: read from its step image (MsArgs::steps); width[c] = 4 when all its values fit 32 signed bits, else 8
@@ -127,7 +130,7 @@ struct MScanDesc {                           // lives in device memory, read wit
     FormStep form[kMaxFormPool];
     int64_t dn[kMaxVCols] = {};              // derived columns: entries of the table looked up
     // projection scans (fronts, dimension and semi-join scans): column c read from its image is ibase[c] + iscale[c] * e (wrapping); read
-    // only for the columns of MsArgs::decode; for a column of MsArgs::steps ibase[c] is its step image's base
+    // only for the columns of MsArgs::decode (table columns and lookups alike); for a column of MsArgs::steps ibase[c] is its step image's base
     int64_t ibase[kMaxVCols] = {}, iscale[kMaxVCols] = {};
     // projection scan (k_project): what to write for the surviving rows
     int nout = 0, out_col[kMaxProjOuts] = {};     // out_col[o] >= 0: that column; -2 - e: the row expression e (below)
@@ -189,7 +192,9 @@ struct MsArgs {
     uint32_t derived = 0;                    // bit c: column c is derived from earlier columns (MScanDesc::dkind ...), ptr[c] = its table
     uint32_t lazy = 0;                       // bit c: not read with the tile (projection scan: needed for surviving rows only; staged scans: below)
     // projection scans, bit c: read from an image that is not a pure narrowing, decoded (MScanDesc::ibase / iscale) -- on the select
-    // side as the tile comes in (scale 1: per-row values, vdl_column_image.h usable_in_vscan), on the take side as a survivor's is loaded
+    // side as the tile comes in (scale 1: per-row values, vdl_column_image.h usable_in_vscan), on the take side as a survivor's is loaded.
+    // A bit of a derived column: a lookup (VC_GATHER) that reads the image of its target column and whose values are needed as the
+    // column holds them -- decoded right after the lookup (derive()), by the same MScanDesc::ibase / iscale
     uint32_t decode = 0;
     // specialised aggregate scans that read late (vdl_jit.cpp): 4 bits per table column -- 0: read with the tile; 1..3: a filter
     // column read for the rows that passed the earlier stages; 14: a source of derived columns / of the group key, read for

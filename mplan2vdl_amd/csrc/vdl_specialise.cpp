@@ -36,9 +36,10 @@ static jit::Shape jit_shape(const MScanCols &cols, const ScanLaunch &cfg, const 
 }
 // (",img": some columns are read from their images -- a kernel that moves other bytes than the same form over the catalog columns;
 // ",rtb", after the form's suffix: bounds at run time)
-static std::string jit_name(const jit::Shape &sh, bool image) {
+// (",limg": a lookup reads the image of its target column, vdl_set_lookup_images)
+static std::string jit_name(const jit::Shape &sh, const MScanCols &cols) {
     return "k_mscan_specialised<" + std::to_string(sh.nc) + "," + std::to_string(sh.u) + "," + (sh.vec ? "vec" : "novec") + "," + (sh.grouped ? "grouped" : "global") +
-           (sh.der ? ",derived" : "") + (image ? ",img" : "") + ">";
+           (sh.der ? ",derived" : "") + (cols.image ? ",img" : "") + (cols.limage ? ",limg" : "") + ">";
 }
 // (tests, profiles: VDL_JIT_LATE=1|2 forces the staged form -- with that many filter columns read with the tile, 4: all of them -- where a column allows it;
 // 5 | 6: the packed form, at 2 row pairs per slice unless VDL_JIT_U says otherwise)
@@ -236,7 +237,7 @@ static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, c
     if (grid > most) grid = most;
     if (grid < 1) grid = 1;
     out.grid = (int)grid; out.per_cu = per_cu; out.code_bytes = code.size(); out.form = f; out.form.u = sh.u;
-    out.name = jit_name(sh, out.b.cols->image != 0);
+    out.name = jit_name(sh, *out.b.cols);
     out.name.insert(out.name.size() - 1, std::string(f.suffix()) + (sh.rt_bounds ? ",rtb" : ""));
     out.stages = stages_text(p, s, args);
     out.packed = packed_text(p, s, *out.b.cols);
@@ -469,6 +470,7 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
         if (grouped) bind_mscan(c, F.gscans[s - ns], cols, *d, &bpr, 0);
         else bind_mscan(c, F.scans[s], cols, *d, &bpr, 0);
         p->image_roles["scan" + std::to_string(s)] = image_text(scan_columns(p, s), cols);
+        p->lookup_roles["scan" + std::to_string(s)] = lookup_text(scan_columns(p, s), cols);
         const ScanLaunch cfg = mscan_launch_config(cols, *d, grouped, c->num_cus);
         if (cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no scan kernel variant for this shape");
         // the staged, queue or packed form of the same scan (VDL_JIT_LATE as in specialise_scan), refused where the tuner refuses it
@@ -484,7 +486,7 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
         }
         if (!jit::compile(jit::mscan_source(b.args, *b.desc, sh), c->arch, code, log))
             throw Error(VDL_ERR_UNSUPPORTED, "scan " + std::to_string(s) + " does not build: " + log.substr(0, 2000));
-        std::string name = jit_name(sh, b.cols->image != 0);
+        std::string name = jit_name(sh, *b.cols);
         if (b.args.packed) name.insert(name.size() - 1, late.suffix());
         if (sh.rt_bounds) name.insert(name.size() - 1, ",rtb");
         p->jit_note += "scan " + std::to_string(s) + ": " + name + (b.args.packed ? " (packed: " + packed_text(p, s, *b.cols) + ")" : "") +
@@ -617,7 +619,7 @@ static bool batch_build(vdl_ctx *c, const ScanForm &f, const jit::Shape &sh, con
     out.grouped = sh.grouped;
     out.code_bytes = code.size();
     out.entry = entry;
-    out.name = jit_name(sh, bound[0].cols->image != 0);
+    out.name = jit_name(sh, *bound[0].cols);
     out.name.insert(out.name.size() - 1, std::string(f.suffix()) + ",batch" + std::to_string(sh.batch) + ",rtb");
     if (check_only) return true;
     out.k = jit::load(code, why, entry);

@@ -21,6 +21,10 @@
 // steps by at most 1 -- a clustered join index -- gets one, and fronts, dimension and semi-join scans read it.  After the run one
 // line "vdlrun: step images: <vdl_plan_step_columns>" goes to stderr beside the images line; it is also printed when --encode runs
 // under VDL_STEP_IMAGES=1, which makes vdl_encode_column try a step image too.
+//   ... | vdlrun --encode --lookup-images ...                                   join lookups read the dimension columns' images
+// --lookup-images switches vdl_set_lookup_images on: a dimension column looked up through a join index is read from its image
+// (built by --encode) where its use allows.  After the run one line "vdlrun: lookup images: <vdl_plan_lookup_columns>" goes to
+// stderr (rank 0's); it is also printed under VDL_LOOKUP_IMAGES=1, which switches them on when the context opens.
 //   ... | vdlrun --order-by revenue:desc,o_orderdate__orders__o_orderdate --limit 10 ...      ORDER BY / LIMIT on the device
 // --order-by FIELD[:asc|:desc][:text[=HEAP]],... names outputs by their full field name or their tmpN key, --limit N keeps the first N
 // rows (vdl_plan_set_order); :text orders the key by its strings (vdl_plan_set_order_text) over HEAP, or over table.col.heap for a
@@ -192,7 +196,7 @@ bool read_reply(const std::string &path, Reply &r) {
 struct Options {
     int64_t rows = 60175;           // SF0.01 lineitem, /root/reference/tests/tpchnoorder/bounds.csv:59
     uint64_t seed = 0x5EED0006ULL;
-    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0;
+    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0, lookup_images = 0;
     std::string data_dir, shard = "lineitem";
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
@@ -250,6 +254,7 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
     int rc = vdl_open(&ctx, o.describe ? -1 : (world > 1 || !comm_dir.empty() ? rank : o.device));
     if (rc) return die(ctx, "vdl_open", rc);
     if (o.batch_grouped) vdl_set_batch_grouped(ctx, 1);
+    if (o.lookup_images) vdl_set_lookup_images(ctx, 1);
     std::vector<vdl_plan *> plans;
     std::string loads = text;                                  // every program's text: what --data looks for Loads in
     for (size_t k = 0; k <= o.batch_texts.size(); k++) {
@@ -334,6 +339,12 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
         vdl_plan_step_columns(plan, &list);
         std::fprintf(stderr, "vdlrun: step images: %s\n", list);
     }
+    const char *lk_env = std::getenv("VDL_LOOKUP_IMAGES");
+    if ((o.lookup_images || (lk_env && *lk_env && *lk_env != '0')) && rank == 0) {
+        const char *list = "";
+        vdl_plan_lookup_columns(plan, &list);
+        std::fprintf(stderr, "vdlrun: lookup images: %s\n", list);
+    }
     for (vdl_plan *one : plans) vdl_plan_free(one);
     vdl_close(ctx);
     return 0;
@@ -352,6 +363,7 @@ int main(int argc, char **argv) {
         else if (a == "--shard" && i + 1 < argc) o.shard = argv[++i];
         else if (a == "--batch" && i + 1 < argc) o.batch_files.push_back(argv[++i]);
         else if (a == "--batch-grouped") o.batch_grouped = 1;
+        else if (a == "--lookup-images") o.lookup_images = 1;
         else if (a == "--order-by" && i + 1 < argc && parse_order_by(argv[i + 1], o)) i++;
         else if (a == "--order-sharded") o.order_sharded = 1;
         else if (a == "--limit" && i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]) &&
@@ -365,7 +377,7 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--lookup-images] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }

@@ -191,15 +191,21 @@ def q14_tables(n_li, seed=SEED):
     return t
 
 
-def register_q14_columns(engine, n_li, li_rows=None, device="cuda", seed=SEED):
+def register_q14_columns(engine, n_li, li_rows=None, device="cuda", seed=SEED, lookup_images=False):
     """The Q14 catalog of `q14_tables` built on the GPU: part in full (uploaded: 1/30 of lineitem), lineitem rows
-    [li_rows[0], li_rows[1]) generated in place.  Returns the tensors backing registered columns."""
+    [li_rows[0], li_rows[1]) generated in place.  Returns the tensors backing registered columns.
+    lookup_images=True (or VDL_LOOKUP_IMAGES=1 in the environment) encodes part.p_type, so that a context with lookup images on
+    (Engine.set_lookup_images) reads its offsets through a 2-byte image."""
+    import os
+
     import torch
 
     n_part = max(n_li // 30, 1)
     r0, r1 = li_rows if li_rows is not None else (0, n_li)
     for name, v in q14_part(n_part, seed).items():
         engine.upload(name, v)
+    if lookup_images or os.environ.get("VDL_LOOKUP_IMAGES", "0") not in ("", "0"):
+        engine.encode("part.p_type")
     for name in ("lineitem.l_shipdate", "lineitem.l_extendedprice", "lineitem.l_discount"):
         engine.generate(LINEITEM[name], r0, r1 - r0, seed)
     engine.generate(ColumnSpec("lineitem.lineitem_part", np.int64, 0, n_part - 1, 1, 0), r0, r1 - r0, seed)

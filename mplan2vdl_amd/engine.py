@@ -104,6 +104,14 @@ class Plan:
         self._e._check(self._e._L.vdl_plan_step_columns(self._h, ctypes.byref(text)))
         return _lib.parse_step_columns((text.value or b"").decode())
 
+    def lookup_columns(self):
+        """{role: {target column: image width}} of the lookups that read the image of their target column (Engine.set_lookup_images),
+        as bound at the last run or jit_check (vdl.h: vdl_plan_lookup_columns); the roles are image_columns()'s, and a lookup target
+        is never listed there.  {} when no lookup reads an image."""
+        text = ctypes.c_char_p()
+        self._e._check(self._e._L.vdl_plan_lookup_columns(self._h, ctypes.byref(text)))
+        return _lib.parse_image_columns((text.value or b"").decode())
+
     def set_trace(self, enabled):
         """Keep a host copy of every statement's vector (statement-by-statement runs only): see `traced()`."""
         self._e._check(self._e._L.vdl_plan_set_trace(self._h, int(bool(enabled))))
@@ -542,6 +550,17 @@ class Engine:
     def declare_packed(self, name, bits, base=0, scale=1):
         """a context without a device: the column has a packed image of `bits` bits (jit_check builds the packed form over it)"""
         self._check(self._L.vdl_declare_packed_image(self._c, name.encode(), int(bits), int(base), int(scale)))
+
+    def declare_image(self, name, width, base=0, scale=1):
+        """a context without a device: the column has a byte image of `width` bytes, v = base + scale * e (jit_check builds the scans
+        and lookups that read it)"""
+        self._check(self._L.vdl_declare_column_image(self._c, name.encode(), int(width), int(base), int(scale)))
+
+    def set_lookup_images(self, enabled):
+        """True: lookups through a join index read the byte image of their target column where its use allows (vdl.h:
+        vdl_set_lookup_images; off by default, VDL_LOOKUP_IMAGES=1 switches it on when the context opens; ignored while
+        set_column_images(False)).  Bound plans re-bind at their next run."""
+        self._check(self._L.vdl_set_lookup_images(self._c, 1 if enabled else 0))
 
     def set_column_images(self, enabled):
         """False: scans read the catalog columns and ignore their images (tests, A/B runs in one process)"""
