@@ -1,6 +1,7 @@
 // vdl_partition.hip -- device-wide prefix sum, Partition (stable LSD radix ranks) and the row exchange of a sharded
 // Partition.
 #include "vdl_device.h"
+#include "vdl_partition_index.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -96,7 +97,6 @@ hipError_t launch_prefix_sum(int64_t *x, int64_t n, int64_t *sums, hipStream_t s
 constexpr int kPartBlock = VDL_PART_BLOCK, kPartSteps = VDL_PART_STEPS, kPartTile = kPartBlock * kPartSteps, kRadix = 256, kPartWaves = kPartBlock / kWave;
 static_assert(kPartBlock >= kRadix, "threads 0..255 own a digit each");
 constexpr int kPartMaxPasses = 8;
-constexpr int kFanBits = 4, kFan = 1 << kFanBits, kFenLevels = 6;            // tiles < 16^6 (launch_partition checks)
 int64_t partition_tiles(int64_t n) { return (n + kPartTile - 1) / kPartTile; }
 
 struct PartIn {
@@ -128,26 +128,7 @@ struct PartIn {
 #endif
 
 // ---- status rows -------------------------------------------------------------------------------------------------------------
-// row of node (u, level) in a pass's rows: level j holds the tiles u with 16^j | u + 1, in order
-__host__ __device__ static inline int64_t partition_rows(int64_t ntiles) { int64_t r = 0; for (int j = 0; j < kFenLevels; j++) r += ntiles >> (kFanBits * j); return r; }
-__device__ __forceinline__ int64_t fen_row(int64_t ntiles, int64_t u, int level) {
-    int64_t base = 0;
-    for (int j = 0; j < level; j++) base += ntiles >> (kFanBits * j);
-    return base + ((u + 1) >> (kFanBits * level)) - 1;
-}
-// the i-th row of the prefix of tile t: one row per unit of each hex digit of t
-__device__ __forceinline__ int fen_prefix_rows(int64_t t) { int r = 0; for (int j = 0; j < kFenLevels; j++) r += (int)((t >> (kFanBits * j)) & (kFan - 1)); return r; }
-__device__ __forceinline__ int64_t fen_prefix_row(int64_t ntiles, int64_t t, int i) {
-    for (int j = 0; j < kFenLevels; j++) {
-        const int v = (int)((t >> (kFanBits * j)) & (kFan - 1));
-        if (i < v) {
-            const int64_t hi = t & ~(((int64_t)kFan << (kFanBits * j)) - 1);
-            return fen_row(ntiles, hi + ((int64_t)(i + 1) << (kFanBits * j)) - 1, j);
-        }
-        i -= v;
-    }
-    return 0;   // not reached
-}
+// (which row holds which node, which rows make up a prefix, who publishes what: vdl_partition_index.h)
 // A wave reads a row with every lane taking 4 of its 256 words.  32-bit words: two 8-byte loads, the lane's digits are
 // 2l, 2l+1, 128+2l, 129+2l; 64-bit words (counts beyond 2^31): four loads, digits l, 64+l, 128+l, 192+l.
 template <class ST> struct StRow;
@@ -882,7 +863,11 @@ hipError_t launch_sorted_heads(Src d, int64_t n, uint64_t *heads, int64_t *flag,
 // Scratch of one Partition: tickets, the up-front histogram and its scan, and per pass the Fenwick nodes of its tiles
 // (partition_rows(tiles) rows of 256 status words: 32-bit words while a count fits 31 bits).
 static int partition_bits(int64_t top) { int bits = 0; while (bits < 63 && ((uint64_t)top >> bits) != 0) bits++; return bits; }
-static bool partition_narrow_status(int64_t n) { return n < ((int64_t)1 << 31); }
+// (VDL_PART_WIDE_STATUS=1 takes the 64-bit status words and destinations at any size: the form that counts of 2^31 and more need, for tests)
+static bool partition_narrow_status(int64_t n) {
+    const char *wide = getenv("VDL_PART_WIDE_STATUS");
+    return n < ((int64_t)1 << 31) && !(wide && wide[0] == '1');
+}
 static size_t partition_head_bytes() { return 64 + 2 * sizeof(int64_t) * (size_t)kPartMaxPasses * kRadix; }
 static size_t partition_node_bytes(int64_t n) { return (size_t)partition_rows(partition_tiles(n)) * kRadix * (partition_narrow_status(n) ? 4 : 8); }
 size_t partition_scratch_bytes(int64_t n, int64_t pcount) {
@@ -909,7 +894,7 @@ hipError_t launch_partition(Src data, const uint64_t *valid, int64_t n, int64_t 
                             int64_t *n_valid_dev /* 1 word */, int64_t *pos_out, hipStream_t s, int64_t max_bucket, int64_t *order_out, int64_t *sorted_keys_out) {
     (void)hipGetLastError();   // see launch_status()
     if (n <= 0) return hipSuccess;
-    if (partition_tiles(n) >= ((int64_t)1 << (kFanBits * kFenLevels))) return hipErrorInvalidValue;      // (2^37 slots: the look-back's level count)
+    if (partition_tiles(n) >= kFenTileLimit) return hipErrorInvalidValue;      // (2^37 slots: the look-back's level count)
     const int64_t top = (max_bucket >= 0 && max_bucket < pcount) ? max_bucket : pcount;      // buckets 0..pcount, or those known to occur
     const int bits = partition_bits(top);
     const int passes = bits <= 8 ? 1 : (bits + 7) / 8;
