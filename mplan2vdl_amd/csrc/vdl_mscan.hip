@@ -319,6 +319,9 @@ hipError_t launch_project_front(const MScanCols &scols, const MScanDesc *dev_sde
                                 int64_t *total_dev, int64_t *total_host, int num_cus, hipStream_t s, hipFunction_t jit_fn) {
     (void)hipGetLastError();
     if (scols.n <= 0) return hipSuccess;
+    // The look-back's tree is over BATCHES of kFrontBatch tiles and expresses batch numbers below kFrontBatchLimit = 16^7; this check is in
+    // TILES, so the largest run let through has ceil((16^7 - 1) / kFrontBatch) = 2^26 batches: on the safe side by a factor of kFrontBatch
+    // (4), the top hex digit of a batch number never exceeds 3.  (tools/sanitize/front_index_main.cpp plays that run through.)
     if (project_tiles(scols.n) >= ((int64_t)1 << (kFrontFanBits * kFrontLevels))) return hipErrorInvalidValue;
     // (one kernel: the runtime's memset of a size like this one came as two fill kernels of 5 us each)
     hipError_t e = launch_fill_words((uint64_t *)look, 0, project_look_bytes(scols.n) / (int64_t)sizeof(uint64_t), s);

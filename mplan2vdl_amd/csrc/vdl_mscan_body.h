@@ -3,6 +3,7 @@
 // scan is specialised at run time (vdl_jit.cpp).  HIP built-ins only -- no C++ library.
 #pragma once
 #include "vdl_scan_desc.h"
+#include "vdl_front_index.h"
 
 #ifndef VDL_SPEC_UNROLL
 #define VDL_SPEC_UNROLL                     // specialised builds: _Pragma("unroll") on the loops a descriptor drives
@@ -1284,24 +1285,20 @@ __device__ __forceinline__ void project_select_body(const MsArgs &C, const MsArg
 // survivors go from the counts of the tiles before it, and writes the output vectors itself: every lane takes survivors
 // k, k + 256, ... as the take pass's waves did.  No tile counts, no 16-bit position scratch and no carry area in memory, no
 // prefix-sum launches, no second kernel; the isolated-line fetches of the survivors' columns run beside the other blocks' streams.
-// Where a tile's survivors go is a prefix over tiles that run at the same time; as in the radix Partition (vdl_partition.hip, where
-// the reasoning and the measurements are) the tiles keep a Fenwick tree of fan-out 16 over their counts -- here one word per
-// node {ready bit, count} --: a tile's prefix is the sum of at most 15 nodes per level, fetched by the lanes of one wave at once;
-// the node of 16 / 256 / ... tiles is made by the tile that completes them.  A tile only waits for tiles that already run.
+// Where a block's survivors go is a prefix over work that runs at the same time; as in the radix Partition (vdl_partition.hip, where
+// the reasoning and the measurements are) a Fenwick tree of fan-out 16 is kept over the counts -- here over the counts of BATCHES of
+// kFrontBatch tiles (below), one word per node {ready bit, count} --: a batch's prefix is the sum of at most 15 nodes per level, fetched
+// by the lanes of one wave at once; the node of 16 / 256 / ... batches is made by the batch that completes them.  A batch only waits
+// for batches that already run.
 struct FrontLook {
     unsigned int *ticket;              // zeroed before the launch
-    unsigned long long *nodes;         // front_look_words(tiles) words, zeroed
-    int64_t *total;                    // the survivors' number, left by the last tile (device)
+    unsigned long long *nodes;         // front_look_words(batches) words, zeroed
+    int64_t *total;                    // the survivors' number, left by the last batch (device)
     int64_t *total_host;               // ... and in pinned host memory (may be null)
 };
-constexpr int kFrontFanBits = 4, kFrontFan = 1 << kFrontFanBits, kFrontLevels = 7;         // tiles < 16^7
+// (which word holds which node, who publishes what and the prefix walk: vdl_front_index.h, shared with a host program)
+static_assert(kFrontWave == kWave, "the prefix walk deals the nodes to the lanes of one wave");
 constexpr unsigned long long kFrontReady = 1ull << 63;
-__host__ __device__ inline int64_t front_look_words(int64_t ntiles) { int64_t w = 0; for (int j = 0; j < kFrontLevels; j++) w += ntiles >> (kFrontFanBits * j); return w; }
-__device__ __forceinline__ int64_t front_node(int64_t ntiles, int64_t u, int level) {
-    int64_t base = 0;
-    for (int j = 0; j < level; j++) base += ntiles >> (kFrontFanBits * j);
-    return base + ((u + 1) >> (kFrontFanBits * level)) - 1;
-}
 __device__ __forceinline__ int64_t front_wait(const unsigned long long *p) {
     unsigned long long v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     while (!(v & kFrontReady)) { __builtin_amdgcn_s_sleep(2); v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1427,10 +1424,10 @@ __device__ __forceinline__ void project_front_body(const MsArgs &Cs, const MsArg
         if (wave == 0) {
             if (lane == 0) front_publish(lk.nodes + front_node(nbatches, batch, 0), total);
             int64_t acc = total;
+            // (front_publishes(batch, j), spelled out: behind the call one constant of this kernel came out in another form)
             for (int j = 1; j < kFrontLevels && ((batch + 1) & (((int64_t)1 << (kFrontFanBits * j)) - 1)) == 0; j++) {
-                const int64_t step = (int64_t)1 << (kFrontFanBits * (j - 1));
                 int64_t x = 0;
-                if (lane < kFrontFan - 1) x = front_wait(lk.nodes + front_node(nbatches, batch - (int64_t)(lane + 1) * step, j - 1));
+                if (lane < kFrontFan - 1) x = front_wait(lk.nodes + front_sibling(nbatches, batch, j, lane));
                 acc += wave_reduce(x, R_SUM);              // (lane 0 holds the sums)
                 if (lane == 0) front_publish(lk.nodes + front_node(nbatches, batch, j), acc);
             }
@@ -1438,13 +1435,9 @@ __device__ __forceinline__ void project_front_body(const MsArgs &Cs, const MsArg
         // where the survivors go: one node per unit of each hex digit of the batch number, a lane each
         if (wave == NW - 1) {
             int64_t x = 0;
-            int i = lane;
-            for (int j = 0; j < kFrontLevels; j++) {
-                const int dgt = (int)((batch >> (kFrontFanBits * j)) & (kFrontFan - 1));
-                const int64_t hi = batch & ~(((int64_t)kFrontFan << (kFrontFanBits * j)) - 1);
-                for (; i < dgt; i += kWave) x += front_wait(lk.nodes + front_node(nbatches, hi + ((int64_t)(i + 1) << (kFrontFanBits * j)) - 1, j));
-                i -= dgt;                                  // (lanes beyond this level's nodes move on to the next level's)
-            }
+#define VDL_FRONT_WAIT_AT(word) front_wait(lk.nodes + (word))
+            VDL_FRONT_PREFIX_WALK(x, nbatches, batch, lane, VDL_FRONT_WAIT_AT);          // (vdl_front_index.h: the text a host program runs too)
+#undef VDL_FRONT_WAIT_AT
             x = wave_reduce(x, R_SUM);
             if (lane == 0) s_off = x;
         }

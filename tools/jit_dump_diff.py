@@ -4,7 +4,7 @@ run in a checkout of the parent commit and in this one.
 
     python3 tools/jit_dump_diff.py PARENT_DUMPS THIS_DUMPS [--compile N]
 
-A translation unit is [generated stage lines] + the embedded device code (csrc/vdl_scan_desc.h + vdl_mscan_body.h as text) + [the
+A translation unit is [generated stage lines] + the embedded device code (csrc/vdl_scan_desc.h + vdl_front_index.h + vdl_mscan_body.h as text) + [the
 descriptor as constants + the kernel].  A file's name holds the hash of its whole text, so a change of the embedded code renames
 every file; what a change of the host code may alter is the generated parts.  Printed: the number of distinct units per side, how many
 generated parts occur on both sides / on one side only, the line diff of the embedded code, and -- with --compile N -- for N units
