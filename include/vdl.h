@@ -45,7 +45,8 @@ enum {
     VDL_ERR_DEVICE      = 4,  /* no HIP device, or a HIP call failed                          */
     VDL_ERR_ARG         = 5,  /* bad argument                                                 */
     VDL_ERR_SHAPE       = 6,  /* operand lengths / field names do not fit                     */
-    VDL_ERR_NOMEM       = 7
+    VDL_ERR_NOMEM       = 7,
+    VDL_ERR_OVERFLOW    = 8   /* checked sums (vdl_plan_set_wide_sums 2): a result does not fit int64 */
 };
 
 /* partial-state merge operators for sharded execution */
@@ -284,6 +285,44 @@ int  vdl_output(const vdl_plan *plan, int k, const char **name, const char **tmp
  * 445 MB over PCIe is a quarter of the run (vdl_plan_set_order with the query's own LIMIT is the way not to make that copy). */
 int  vdl_plan_set_device_outputs(vdl_plan *plan, int enabled);
 int  vdl_output_device(const vdl_plan *plan, int k, const int64_t **dev_vals, size_t *n);
+
+/* ---- wide sums: exact 128-bit SUM results from the fused aggregate scans ---------------------------------------------
+ * Every FoldSum adds in int64 and wraps around, and so does the CPU oracle: a sum that leaves int64 comes back as a wrong
+ * number, silently (Q1's sum_charge over the generated lineitem is 0.547 of INT64_MAX at SF100 and wraps from about SF183: measured).  The switch widens the ACCUMULATION.
+ *   mode 0  off: everything as it is without the switch (the default; VDL_WIDE_SUMS=1|2 in the environment sets the mode at vdl_parse).
+ *   mode 1  wide: every output carries a second vector of the same length, bits 64..127 of its exact value (vdl_output_high);
+ *           vdl_output's vector is what it is with the switch off -- bits 0..63.
+ *   mode 2  checked: as wide, and a run in which some output's high word is not the sign extension of its low word fails with
+ *           VDL_ERR_OVERFLOW; the message names the output field, the group (its position in the result) and the exact value
+ *           in decimal, and the outputs are not delivered (vdl_n_outputs is 0).
+ * "Exact" is the SUM of the per-row terms in two's-complement 128-bit arithmetic.  The per-row TERM stays the int64 the program
+ * computes, wrap-around included: overflow of a per-row product is out of scope, only the accumulation widens.  A sum that leaves
+ * int64 on the way and comes back ends with a clean high word: excursions are no overflow.  COUNT, MIN, MAX and FIRST have the
+ * sign extension as their high word.  An output that is a scalar expression over aggregates (avg = Divide(sum, count)) is
+ * evaluated over the exact 128-bit aggregate values with 128-bit wrap-around, the int64 rules widened (x / 0 = x % 0 = 0,
+ * MIN128 / -1 wraps, a shift count of 127 or more shifts everything out).
+ * Served: plans that fuse as a whole (vdl_plan_is_fused) -- global and dense-domain grouped aggregate scans, with or without
+ * derived columns -- on the precompiled kernels (a single-sum scan runs on k_mscan, not k_scan) and, with vdl_plan_set_jit, on
+ * the specialised ones in every form the scan has (eager, staged, queue; packed, which only global scans over table columns
+ * have): their names carry ",wide".  Refused with
+ * VDL_ERR_UNSUPPORTED before any kernel runs, the message naming the route: a plan that does not fuse as a whole or whose
+ * fusion is off (its sums would run through the GROUP BY tail or the per-operator folds); a fused plan whose rows carry group
+ * keys outside the pivots (it would be rerun statement by statement); every sharded entry point (vdl_run_local, vdl_finalize*,
+ * vdl_resolve_first, vdl_exchange_begin, vdl_run_sharded*).  vdl_run_batch runs such a plan alone inside the call ("alone: wide
+ * sums are not batched").  With an order set the high vectors are permuted and cut with the low ones; keys are compared as the
+ * int64 they are, and a key output whose value does not fit int64 fails the run with VDL_ERR_OVERFLOW naming it, in either mode.
+ * vdl_plan_set_wide_sums: mode outside 0..2 is VDL_ERR_ARG.  vdl_output_high: *hi is NULL before a run and after a mode-0 run,
+ * else n values (on the host also under vdl_plan_set_device_outputs: a fused plan assembles a handful of rows there).
+ * vdl_plan_wide_note: what served the plan's scans in the last run ("wide: k_mscan grouped, 7 sums"), or the reason of a refusal.
+ * vdl_plan_jit_check builds the wide units without a device when the switch is on.
+ * vdl_wide_eval_bin: the 128-bit operator of the scalar expressions on its own, (alo, ahi) op (blo, bhi), `op` numbered as
+ * the engine numbers the VDL binary operators (0 LogicalAnd, 1 LogicalOr, 2 BitwiseAnd, 3 BitwiseOr, 4 BitShift, 5 Equals, 6 Add,
+ * 7 Subtract, 8 Greater, 9 Multiply, 10 Divide, 11 Modulo; anything else VDL_ERR_ARG); host only, no device needed. */
+int  vdl_plan_set_wide_sums(vdl_plan *plan, int mode);
+int  vdl_plan_wide_sums(const vdl_plan *plan);
+int  vdl_output_high(const vdl_plan *plan, int k, const int64_t **hi, size_t *n);
+const char *vdl_plan_wide_note(const vdl_plan *plan);
+int  vdl_wide_eval_bin(int op, int64_t alo, int64_t ahi, int64_t blo, int64_t bhi, int64_t *lo, int64_t *hi);
 int  vdl_n_timings(const vdl_plan *plan);
 int  vdl_timing(const vdl_plan *plan, int k, const char **label, double *usec);
 

@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VDL_LIB") or os.path.join(_HERE, "lib", "libvdl.so")      # VDL_LIB: kernel experiments (tools/build_variant.sh)
 
-VDL_OK, VDL_ERR_PARSE, VDL_ERR_COLUMN, VDL_ERR_UNSUPPORTED, VDL_ERR_DEVICE, VDL_ERR_ARG, VDL_ERR_SHAPE, VDL_ERR_NOMEM = range(8)
+VDL_OK, VDL_ERR_PARSE, VDL_ERR_COLUMN, VDL_ERR_UNSUPPORTED, VDL_ERR_DEVICE, VDL_ERR_ARG, VDL_ERR_SHAPE, VDL_ERR_NOMEM, VDL_ERR_OVERFLOW = range(9)
 REDUCE_NONE, REDUCE_SUM, REDUCE_MIN, REDUCE_MAX, REDUCE_FIRST = range(5)
 
 _lib = None
@@ -90,6 +90,11 @@ def load():
         "vdl_output": (i32, [vp, i32, P(cp), P(cp), P(P(i64)), P(ctypes.c_size_t)]),
         "vdl_plan_set_device_outputs": (i32, [vp, i32]),
         "vdl_output_device": (i32, [vp, i32, P(P(i64)), P(ctypes.c_size_t)]),
+        "vdl_plan_set_wide_sums": (i32, [vp, i32]),
+        "vdl_plan_wide_sums": (i32, [vp]),
+        "vdl_output_high": (i32, [vp, i32, P(P(i64)), P(ctypes.c_size_t)]),
+        "vdl_plan_wide_note": (cp, [vp]),
+        "vdl_wide_eval_bin": (i32, [i32, i64, i64, i64, i64, P(i64), P(i64)]),
         "vdl_plan_set_order": (i32, [vp, i32, P(cp), P(i32), i64]),
         "vdl_plan_order_note": (cp, [vp]),
         "vdl_plan_set_order_sharded": (i32, [vp, i32]),
@@ -150,6 +155,7 @@ ABI_SYMBOLS = [
     "vdl_plan_scan_stats", "vdl_plan_scan_traffic", "vdl_plan_partial_spec", "vdl_plan_sharded_route", "vdl_run_local", "vdl_finalize", "vdl_finalize_begin", "vdl_finalize_end", "vdl_plan_set_row_offset", "vdl_plan_set_sharded_table", "vdl_resolve_first", "vdl_exchange_spec", "vdl_exchange_begin", "vdl_exchange_pack",
     "vdl_exchange_finish", "vdl_comm_unique_id", "vdl_comm_init", "vdl_comm_init_host", "vdl_comm_info", "vdl_comm_free", "vdl_run_sharded",
     "vdl_run_sharded_begin", "vdl_run_sharded_end", "vdl_comm_merge_host",
+    "vdl_plan_set_wide_sums", "vdl_plan_wide_sums", "vdl_output_high", "vdl_plan_wide_note", "vdl_wide_eval_bin",
 ]
 
 

@@ -966,6 +966,7 @@ int vdl_run_sharded_begin(vdl_ctx *c, vdl_plan *p, int slot) {
     if (!c || !p) return VDL_ERR_ARG;
     return guard(c, [&] {
         refuse_order_sharded(p, true);
+        refuse_wide_sharded(p, "vdl_run_sharded_begin");
         p->order_note.clear();
         if (!fold_route(c, p)) throw Error(VDL_ERR_UNSUPPORTED, "vdl_run_sharded_begin serves plans whose outputs are folds (partial words); plans with a "
                                                                "Partition exchange rows and run through vdl_run_sharded");
@@ -986,7 +987,7 @@ int vdl_run_sharded_end(vdl_ctx *c, vdl_plan *p, int slot) {
 
 int vdl_run_sharded(vdl_ctx *c, vdl_plan *p) {
     if (!c || !p) return VDL_ERR_ARG;
-    if (const int rc = guard(c, [&] { refuse_order_sharded(p, true); })) return rc;
+    if (const int rc = guard(c, [&] { refuse_order_sharded(p, true); refuse_wide_sharded(p, "vdl_run_sharded"); })) return rc;
     p->order_note.clear();
     if (p->use_fusion && p->fused.ok) {                       // a fused plan with a semi-join set: the sets are merged across the ranks
         bool semi = false;

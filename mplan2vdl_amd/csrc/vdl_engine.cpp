@@ -278,6 +278,12 @@ static std::string mscan_label(const ScanLaunch &cfg, const MScanCols &cols) {
     if (cols.limage && !n.empty() && n.back() == '>') n.insert(n.size() - 1, ",limg");      // (a lookup reads its target's image)
     return n;
 }
+// ... and ",wide" where the wide-sums build of it runs (vdl_mscan_wide.hip)
+static std::string mscan_label(const ScanLaunch &cfg, const MScanCols &cols, const MScanDesc &d) {
+    std::string n = mscan_label(cfg, cols);
+    if (d.wide && !n.empty() && n.back() == '>') n.insert(n.size() - 1, ",wide");
+    return n;
+}
 // blocks a specialised scan may be launched with, whatever rows-per-lane the tuner settles on: the partials area is sized for it
 static int max_scan_grid(const vdl_ctx *c, const vdl_plan *p, int chosen) { return p->use_jit ? std::max(chosen, c->num_cus * 8) : chosen; }
 
@@ -298,6 +304,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
     p->mjit_form.assign(ns + ng, ScanForm{});
     p->kscan.assign(ns + ng, 0);
     p->jit_note.clear();
+    p->wide_note.clear();
     p->jit_builds.clear();
     for (auto it = p->image_roles.begin(); it != p->image_roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->image_roles.erase(it) : std::next(it);
     for (auto it = p->lookup_roles.begin(); it != p->lookup_roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->lookup_roles.erase(it) : std::next(it);
@@ -314,7 +321,8 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         int64_t bpr = 0, n = 0;
         std::string kname;
         const bool eligible = use_kscan(sp);
-        p->kscan[s] = eligible && !(p->use_jit && !sp.never);    // specialising: the single-aggregate scan runs through the general body too
+        // (wide sums: k_scan has no wide build -- a single-sum scan runs on k_mscan's)
+        p->kscan[s] = eligible && !(p->use_jit && !sp.never) && !p->wide;    // specialising: the single-aggregate scan runs through the general body too
         if (eligible) {                                       // (bound either way: the tuner compares the two)
             ScanArgs &a = p->sargs[s];
             a.ncol = (int)sp.cols.size(); a.nagg = 1; a.never = sp.never ? 1 : 0;
@@ -346,17 +354,20 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         if (!p->kscan[s]) {
             bpr = 0;
             n = bind_mscan(c, sp, p->mcols[s], p->mdesc[s], &bpr, p->row_offset);
+            p->mdesc[s].wide = p->wide ? 1 : 0;
             p->image_roles["scan" + std::to_string(s)] = image_text(sp.cols, p->mcols[s]);
             p->lookup_roles["scan" + std::to_string(s)] = lookup_text(sp.cols, p->mcols[s]);
             p->mcfg[s] = mscan_launch_config(p->mcols[s], p->mdesc[s], false, c->num_cus);
             if (p->mcfg[s].variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no multi-aggregate scan kernel variant for this shape");
             std::string jname;
             const bool spec = p->use_jit && !sp.never && specialise_scan(c, p, s, false, &jname);
-            if (eligible && !spec) { p->kscan[s] = 1; }       // it did not build: the tuned single-aggregate kernel after all
-            p->mparts[s] = dev_alloc(c, sizeof(int64_t) * (size_t)max_scan_grid(c, p, p->mcfg[s].grid) * (size_t)(p->mdesc[s].nagg + 1));
+            if (eligible && !spec && !p->wide) { p->kscan[s] = 1; }       // it did not build: the tuned single-aggregate kernel after all
+            p->mparts[s] = dev_alloc(c, sizeof(int64_t) * (size_t)max_scan_grid(c, p, p->mcfg[s].grid) * (size_t)mscan_partial_words(p->mdesc[s], false));
             p->mdesc[s].block_partials = (int64_t *)p->mparts[s]->p;
             if (!p->mdev[s]) p->mdev[s] = dev_alloc(c, sizeof(MScanDesc));
-            if (!p->kscan[s]) kname = (spec ? jname : mscan_label(p->mcfg[s], p->mcols[s])) + "_grid" + std::to_string(p->mcfg[s].grid);
+            if (!p->kscan[s]) kname = (spec ? jname : mscan_label(p->mcfg[s], p->mcols[s], p->mdesc[s])) + "_grid" + std::to_string(p->mcfg[s].grid);
+            if (p->wide) p->wide_note += std::string(p->wide_note.empty() ? "wide: " : "; ") + (spec ? jname : mscan_label(p->mcfg[s], p->mcols[s], p->mdesc[s])) + " global, " +
+                                         std::to_string(mscan_sums(p->mdesc[s])) + " sums";
         }
         p->word_offset[s] = off;
         off += (int64_t)sp.aggs.size() + 1;
@@ -370,20 +381,28 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         p->image_roles["scan" + std::to_string(m)] = image_text(gp.cols, p->mcols[m]);
         p->lookup_roles["scan" + std::to_string(m)] = lookup_text(gp.cols, p->mcols[m]);
         MScanDesc &d = p->mdesc[m];
+        d.wide = p->wide ? 1 : 0;
         p->mcfg[m] = mscan_launch_config(p->mcols[m], d, true, c->num_cus);
         if (p->mcfg[m].variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no grouped-scan kernel variant for this shape");
+        // (wide sums: the table holds one more word per SUM aggregate and bucket; one replica of it has to fit what a block gets)
+        if (d.wide && mscan_lds_bytes(d, true) > (size_t)kGroupLdsWords * sizeof(int64_t))
+            throw Error(VDL_ERR_UNSUPPORTED, "wide sums: the group table of scan " + std::to_string(m) + ", " + std::to_string(d.pcount) + " buckets x (1 + " + std::to_string(d.nagg) +
+                                             " aggregates + " + std::to_string(mscan_sums(d)) + " high words), leaves no room in LDS for one replica (" +
+                                             std::to_string(mscan_lds_bytes(d, true)) + " of " + std::to_string((size_t)kGroupLdsWords * sizeof(int64_t)) + " bytes)");
         std::string jname;
         const bool spec = p->use_jit && !gp.never && specialise_scan(c, p, m, true, &jname);
         const int64_t words = d.pcount * (d.nagg + 1) + 1;
-        p->mparts[m] = dev_alloc(c, sizeof(int64_t) * (size_t)max_scan_grid(c, p, p->mcfg[m].grid) * (size_t)words);
+        p->mparts[m] = dev_alloc(c, sizeof(int64_t) * (size_t)max_scan_grid(c, p, p->mcfg[m].grid) * (size_t)mscan_partial_words(d, true));
         d.block_partials = (int64_t *)p->mparts[m]->p;
         if (!p->mdev[m]) p->mdev[m] = dev_alloc(c, sizeof(MScanDesc));
         p->gword_offset[g] = off;
         off += words;
         if (!gp.never && n * bpr > p->scan_bytes) {
             p->scan_bytes = n * bpr; p->scan_rows = n; p->dominant = (int)m;
-            p->dominant_kernel = (spec ? jname : mscan_label(p->mcfg[m], p->mcols[m])) + "_grid" + std::to_string(p->mcfg[m].grid) + "_rep" + std::to_string(d.replicas);
+            p->dominant_kernel = (spec ? jname : mscan_label(p->mcfg[m], p->mcols[m], d)) + "_grid" + std::to_string(p->mcfg[m].grid) + "_rep" + std::to_string(d.replicas);
         }
+        if (p->wide) p->wide_note += std::string(p->wide_note.empty() ? "wide: " : "; ") + (spec ? jname : mscan_label(p->mcfg[m], p->mcols[m], d)) + " grouped, " +
+                                     std::to_string(mscan_sums(d)) + " sums";
     }
     p->bound = true;
 }
@@ -648,6 +667,12 @@ void run_fused_local(vdl_ctx *c, vdl_plan *p, int64_t *dev_words, bool single_ra
         bind_fused(c, p);
         p->bound_version = c->binding_version();
     }
+    // wide sums: the high words of the partial words, laid out as dev_words is (the finish step of every scan writes both)
+    int64_t *hi_words = nullptr;
+    if (p->wide) {
+        if (!p->wide_hi || p->wide_hi_cap < p->n_words) { p->wide_hi = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(p->n_words, 1)); p->wide_hi_cap = p->n_words; }
+        hi_words = (int64_t *)p->wide_hi->p;
+    }
     run_prelude(c, p);
     if (p->use_jit && p->jit_tune && !p->jit_tuned) {
         p->jit_tuned = true;
@@ -687,7 +712,8 @@ void run_fused_local(vdl_ctx *c, vdl_plan *p, int64_t *dev_words, bool single_ra
             // events bracket the scan together with its tiny finish kernel(s)
             if (timed) HIP_CHECK(hipEventRecord(p->ev0[ei], c->stream));
             HIP_CHECK(launch_mscan(p->mcols[s], p->mdesc[s], on_dev, p->mcfg[s], grouped, never, out,
-                                   grouped && single_rank, c->stream, p->mjit[s] ? p->mjit[s]->fn : nullptr));
+                                   grouped && single_rank, c->stream, p->mjit[s] ? p->mjit[s]->fn : nullptr,
+                                   hi_words ? hi_words + (grouped ? p->gword_offset[s - ns] : p->word_offset[s]) : nullptr));
             if (timed) { HIP_CHECK(hipEventRecord(p->ev1[ei], c->stream)); p->ev_pending[ei] = true; }
         }
     }
@@ -708,6 +734,11 @@ void finalize_begin(vdl_ctx *c, vdl_plan *p, const int64_t *dev_words, int slot)
     }
     if (!p->slot_ev[slot]) HIP_CHECK(hipEventCreateWithFlags(&p->slot_ev[slot], hipEventDisableTiming));
     if (p->n_words) HIP_CHECK(hipMemcpyAsync(p->host_words[slot], dev_words, sizeof(int64_t) * (size_t)p->n_words, hipMemcpyDeviceToHost, c->stream));
+    p->wide_host_hi.clear();
+    if (p->wide && p->wide_hi && p->n_words) {                 // (a wide run is never pipelined: vdl_run alone serves it)
+        p->wide_host_hi.resize((size_t)p->n_words);
+        HIP_CHECK(hipMemcpyAsync(p->wide_host_hi.data(), p->wide_hi->p, sizeof(int64_t) * (size_t)p->n_words, hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_CHECK(hipEventRecord(p->slot_ev[slot], c->stream));
     p->slot_pending[slot] = true;
     int ei = -1;
@@ -743,11 +774,39 @@ void finalize_end(vdl_ctx *c, vdl_plan *p, int slot) {
                                   std::to_string(a.pmin + a.pcount - 1) + "]");
     }
     p->outs.clear();
+    // wide sums: every output from the exact 128-bit aggregate values (the low words are `w`, the high words came beside them); the
+    // high word of a MIN, MAX or FIRST aggregate is its sign extension (a FIRST word became a column value after the finish step)
+    const bool wide = p->wide && !p->wide_host_hi.empty() && (int64_t)p->wide_host_hi.size() == p->n_words;
+    if (p->wide && !wide && p->n_words) throw Error(VDL_ERR_ARG, "internal: a wide-sums run without its high words");
+    auto wide_values = [&](const int64_t *lo, const int64_t *hi, const MScanDesc &a, std::vector<wide_t> &v) {
+        v.resize((size_t)a.nagg + 1);
+        v[0] = (wide_t)lo[0];
+        for (int j = 0; j < a.nagg; j++) {
+            const int64_t h = a.agg[j].kind == AGG_SUM ? hi[1 + j] : (lo[1 + j] >> 63);
+            v[(size_t)j + 1] = (wide_t)(((unsigned __int128)(uint64_t)h << 64) | (uint64_t)lo[1 + j]);
+        }
+    };
+    auto push_wide = [&](Output &o, wide_t x) {
+        o.vals.push_back((int64_t)(uint64_t)(unsigned __int128)x);
+        o.hi.push_back((int64_t)(uint64_t)((unsigned __int128)x >> 64));
+    };
+    std::vector<wide_t> wv;
     for (const FusedOutput &fo : p->fused.outputs) {
         Output o;
         o.node = fo.node;
         o.name = p->prog.at(fo.node).field;
         o.tmp = "tmp" + std::to_string(fo.node);
+        o.has_hi = wide;
+        if (wide && fo.gscan < 0) {
+            const int64_t *sw = w.data() + p->word_offset[(size_t)fo.scan];
+            if (sw[0] > 0) { wide_values(sw, p->wide_host_hi.data() + p->word_offset[(size_t)fo.scan], p->mdesc[(size_t)fo.scan], wv); push_wide(o, eval_scalar_wide(*fo.value, wv.data() + 1)); }
+        } else if (wide) {
+            const MScanDesc &a = p->mdesc[ns + (size_t)fo.gscan];
+            const int W = a.nagg + 1;
+            const int64_t *tab = w.data() + p->gword_offset[(size_t)fo.gscan], *tabh = p->wide_host_hi.data() + p->gword_offset[(size_t)fo.gscan];
+            for (int64_t b = 0; b < a.pcount; b++)
+                if (tab[b * W] > 0) { wide_values(tab + b * W, tabh + b * W, a, wv); push_wide(o, eval_scalar_wide(*fo.value, wv.data() + 1)); }
+        } else
         if (fo.gscan < 0) {
             const int64_t *sw = w.data() + p->word_offset[(size_t)fo.scan];
             if (sw[0] > 0) o.vals.push_back(eval_scalar(*fo.value, sw + 1));   // no selected row -> the fold slot is EPS
@@ -819,9 +878,45 @@ int order_sort_key(vdl_ctx *c, hipStream_t s, const int64_t *key, uint64_t flip,
     }
     return sorts;
 }
+// ---- wide sums: values outside int64 ---------------------------------------------------------------------------------------------
+std::string wide_decimal(int64_t lo, int64_t hi) {
+    unsigned __int128 u = ((unsigned __int128)(uint64_t)hi << 64) | (uint64_t)lo;
+    const bool neg = hi < 0;
+    if (neg) u = (unsigned __int128)0 - u;
+    std::string s;
+    do { s.insert(s.begin(), (char)('0' + (int)(u % 10))); u /= 10; } while (u != 0);
+    return neg ? "-" + s : s;
+}
+// the first value of output o whose high word is not the sign extension of its low word: -1 = every value fits int64
+static int64_t wide_first_overflow(const Output &o) {
+    if (!o.has_hi) return -1;
+    for (size_t i = 0; i < o.vals.size() && i < o.hi.size(); i++) if (o.hi[i] != (o.vals[i] >> 63)) return (int64_t)i;
+    return -1;
+}
+// checked sums (mode 2): the run fails on the first such value, and delivers nothing
+void wide_check_outputs(vdl_plan *p) {
+    for (const Output &o : p->outs) {
+        const int64_t i = wide_first_overflow(o);
+        if (i < 0) continue;
+        const std::string msg = "checked sums: output '" + o.name + "' (" + o.tmp + "), group " + std::to_string(i) + ": the exact value " +
+                                wide_decimal(o.vals[(size_t)i], o.hi[(size_t)i]) + " does not fit int64 (vdl_plan_set_wide_sums(plan, 1) delivers it as two words)";
+        p->outs.clear();
+        throw Error(VDL_ERR_OVERFLOW, msg);
+    }
+}
+
 void order_outputs_on_host(vdl_ctx *c, vdl_plan *p) {
     std::vector<size_t> keys;
     const int64_t m = order_resolve(p, keys);
+    // wide sums: keys are compared as the int64 they are -- a key whose exact value is not one cannot be ordered by it
+    for (size_t k : keys) {
+        const int64_t i = wide_first_overflow(p->outs[k]);
+        if (i < 0) continue;
+        const std::string msg = "wide sums: the order key '" + p->outs[k].name + "' (" + p->outs[k].tmp + ") holds, in group " + std::to_string(i) + ", the exact value " +
+                                wide_decimal(p->outs[k].vals[(size_t)i], p->outs[k].hi[(size_t)i]) + ", which does not fit the int64 that keys are compared as";
+        p->outs.clear();
+        throw Error(VDL_ERR_OVERFLOW, msg);
+    }
     const int64_t L = p->order.limit > 0 ? std::min<int64_t>(p->order.limit, m) : m;
     // text keys: an index that has to be built is built (and timed under its own label) before the step's clock starts
     const int n_text = p->order.n_text();
@@ -861,6 +956,11 @@ void order_outputs_on_host(vdl_ctx *c, vdl_plan *p) {
         for (int64_t i = 0; i < L; i++) cut[(size_t)i] = src[index[(size_t)i]];
         o.vals.swap(cut);
         o.big = nullptr; o.big_n = 0;
+        if (o.has_hi) {                                        // wide sums: the high words go with their low words
+            std::vector<int64_t> cut_hi((size_t)L);
+            for (int64_t i = 0; i < L; i++) cut_hi[(size_t)i] = o.hi[(size_t)index[(size_t)i]];
+            o.hi.swap(cut_hi);
+        }
     }
     p->order_note = "host m=" + std::to_string(m) + " rows=" + std::to_string(L);
     if (n_text > 0) p->order_note += " text_keys=" + std::to_string(n_text);
@@ -1528,6 +1628,7 @@ int vdl_parse(vdl_ctx *c, const char *text, size_t len, vdl_plan **out) {
         p->fused = fuse_program(p->prog);
         { const char *j = getenv("VDL_JIT"); p->use_jit = j && *j && *j != '0'; p->jit_tune = p->use_jit && atoi(j) >= 2; }
         { const char *b = getenv("VDL_JIT_BOUNDS"); p->jit_rt_bounds = b && strcmp(b, "runtime") == 0; }
+        { const char *w = getenv("VDL_WIDE_SUMS"); p->wide = w && (strcmp(w, "1") == 0 || strcmp(w, "2") == 0) ? atoi(w) : 0; }
         p->description = describe_plan(p.get());
         *out = p.release();
     });
@@ -1599,6 +1700,10 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
     if (!c || !p) return VDL_ERR_ARG;
     return guard(c, [&] {
         p->jit_note.clear();
+        if (p->wide) {                                         // (wide sums: the units a run would refuse to build are refused here too)
+            const std::string why = wide_refusal(p);
+            if (!why.empty()) throw Error(VDL_ERR_UNSUPPORTED, why);
+        }
         if (!p->fused.ok && p->fused.proj.ok) {
             // the fused front of a plan that does not fuse as a whole: both passes of the projection scan, and the dimension
             // scans its prelude holds
@@ -1730,6 +1835,34 @@ int vdl_output_device(const vdl_plan *p, int k, const int64_t **dev_vals, size_t
     if (n) *n = o.count();
     return VDL_OK;
 }
+// ---- wide sums ----------------------------------------------------------------------------------------
+int vdl_plan_set_wide_sums(vdl_plan *p, int mode) {
+    if (!p || mode < 0 || mode > 2) return VDL_ERR_ARG;
+    if ((p->wide != 0) != (mode != 0)) {                       // other kernels, other partials: the scans are bound and built again
+        p->bound = false;
+        p->jit_tuned = false;
+        p->wide_note.clear();
+    }
+    p->wide = mode;
+    return VDL_OK;
+}
+int vdl_plan_wide_sums(const vdl_plan *p) { return p ? p->wide : 0; }
+int vdl_output_high(const vdl_plan *p, int k, const int64_t **hi, size_t *n) {
+    if (!p || k < 0 || k >= (int)p->outs.size()) return VDL_ERR_ARG;
+    const Output &o = p->outs[(size_t)k];
+    if (hi) *hi = o.has_hi ? o.hi.data() : nullptr;
+    if (n) *n = o.count();
+    return VDL_OK;
+}
+const char *vdl_plan_wide_note(const vdl_plan *p) { return p ? p->wide_note.c_str() : ""; }
+int vdl_wide_eval_bin(int op, int64_t alo, int64_t ahi, int64_t blo, int64_t bhi, int64_t *lo, int64_t *hi) {
+    if (op < 0 || op >= B_COUNT || !lo || !hi) return VDL_ERR_ARG;
+    const wide_t a = (wide_t)(((unsigned __int128)(uint64_t)ahi << 64) | (uint64_t)alo), b = (wide_t)(((unsigned __int128)(uint64_t)bhi << 64) | (uint64_t)blo);
+    const unsigned __int128 r = (unsigned __int128)apply_bin_wide(op, a, b);
+    *lo = (int64_t)(uint64_t)r;
+    *hi = (int64_t)(uint64_t)(r >> 64);
+    return VDL_OK;
+}
 int vdl_plan_set_trace(vdl_plan *p, int enabled) {
     if (!p) return VDL_ERR_ARG;
     p->tracing = enabled != 0;
@@ -1762,6 +1895,13 @@ static int run_plan(vdl_ctx *c, vdl_plan *p, const std::string *abandoned) {
         p->order_note.clear();
         p->batch_note.clear();
         p->batch_code_bytes = 0;
+        if (p->wide) {
+            // wide sums are served by the fused aggregate scans alone: refused here, before any kernel runs, where the plan's sums
+            // would be computed by anything else
+            p->outs.clear();
+            const std::string why = wide_refusal(p);
+            if (!why.empty()) { p->wide_note = "refused: " + why; throw Error(VDL_ERR_UNSUPPORTED, why); }
+        }
         if (abandoned) p->fallback_note = *abandoned;
         else if (p->use_fusion && p->fused.ok) {
             const int64_t nw = plan_words(p, nullptr, nullptr);
@@ -1770,10 +1910,19 @@ static int run_plan(vdl_ctx *c, vdl_plan *p, const std::string *abandoned) {
                 run_fused_local(c, p, (int64_t *)p->words->p, true);
                 finalize_begin(c, p, (const int64_t *)p->words->p, 0);
                 finalize_end(c, p, 0);
+                if (p->wide == 2) wide_check_outputs(p);
                 if (p->order.set) order_outputs_on_host(c, p);     // a fused plan's outputs are assembled on the host: a handful of rows
                 return;
             } catch (const NeedGeneralPath &e) {
                 p->fallback_note = e.what();          // exact for any data: rerun statement by statement
+            }
+            if (p->wide) {
+                const std::string why = "wide sums are on, and this run of the fused plan cannot stand: " + p->fallback_note + ".  The statement-by-statement rerun computes its sums with "
+                                        "k_group_fold / k_seg_fold / k_fold_global, which have no wide form; clear the switch (vdl_plan_set_wide_sums(plan, 0)) to run it";
+                p->wide_note = "refused: " + why;
+                p->fallback_note.clear();
+                p->outs.clear();
+                throw Error(VDL_ERR_UNSUPPORTED, why);
             }
         }
         std::map<int, DVec> over;
@@ -2026,6 +2175,7 @@ int vdl_run_local(vdl_ctx *c, vdl_plan *p, void *dev_partials) {
     if (!c || !p || !dev_partials) return VDL_ERR_ARG;
     return guard(c, [&] {
         refuse_order_sharded(p);
+        refuse_wide_sharded(p, "vdl_run_local");
         need_device(c);
         if (!(p->use_fusion && p->fused.ok)) { general_run_local(c, p, (int64_t *)dev_partials); return; }
         bool shardable = true;
@@ -2038,6 +2188,7 @@ int vdl_run_local(vdl_ctx *c, vdl_plan *p, void *dev_partials) {
 int vdl_finalize(vdl_ctx *c, vdl_plan *p, const void *dev_partials) {
     if (!c || !p || !dev_partials) return VDL_ERR_ARG;
     return guard(c, [&] {
+        refuse_wide_sharded(p, "vdl_finalize");
         need_device(c);
         if (!(p->use_fusion && p->fused.ok)) { general_finalize(c, p, (const int64_t *)dev_partials); return; }
         finalize_begin(c, p, (const int64_t *)dev_partials, 0);
@@ -2060,6 +2211,7 @@ int vdl_plan_set_row_offset(vdl_plan *p, int64_t row0) {
 int vdl_resolve_first(vdl_ctx *c, vdl_plan *p, void *dev_partials) {
     if (!c || !p || !dev_partials) return VDL_ERR_ARG;
     return guard(c, [&] {
+        refuse_wide_sharded(p, "vdl_resolve_first");
         need_device(c);
         if (!(p->use_fusion && p->fused.ok) || !p->bound) throw Error(VDL_ERR_ARG, "vdl_resolve_first needs a fused plan after vdl_run_local");
         const size_t ns = p->fused.scans.size();
@@ -2076,6 +2228,7 @@ int vdl_resolve_first(vdl_ctx *c, vdl_plan *p, void *dev_partials) {
 int vdl_finalize_begin(vdl_ctx *c, vdl_plan *p, const void *dev_partials, int slot) {
     if (!c || !p || !dev_partials) return VDL_ERR_ARG;
     return guard(c, [&] {
+        refuse_wide_sharded(p, "vdl_finalize_begin");
         need_device(c);
         if (!(p->use_fusion && p->fused.ok)) { general_finalize(c, p, (const int64_t *)dev_partials); return; }   // nothing left for _end
         finalize_begin(c, p, (const int64_t *)dev_partials, slot);
@@ -2085,6 +2238,7 @@ int vdl_finalize_begin(vdl_ctx *c, vdl_plan *p, const void *dev_partials, int sl
 int vdl_finalize_end(vdl_ctx *c, vdl_plan *p, int slot) {
     if (!c || !p) return VDL_ERR_ARG;
     return guard(c, [&] {
+        refuse_wide_sharded(p, "vdl_finalize_end");
         need_device(c);
         if (!(p->use_fusion && p->fused.ok)) return;
         finalize_end(c, p, slot);

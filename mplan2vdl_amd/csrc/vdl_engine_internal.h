@@ -176,6 +176,8 @@ struct Output {
     int node = 0;
     std::string name, tmp;
     std::vector<int64_t> vals;
+    std::vector<int64_t> hi;           // wide sums (vdl_plan_set_wide_sums): bits 64..127 of every value of `vals`; has_hi says whether the run made them
+    bool has_hi = false;
     const int64_t *big = nullptr;      // large results land in a pinned buffer the plan keeps (pageable copies run at a few GB/s)
     size_t big_n = 0;
     std::shared_ptr<void> dev_keep;    // vdl_plan_set_device_outputs: large results stay in HBM, owned by the plan until its next run
@@ -272,6 +274,14 @@ struct vdl_plan {
     std::vector<Traced> traced;
     hipEvent_t stmt_ev[2] = {nullptr, nullptr};   // per-statement profiling of the per-operator executor (created on first use)
     bool device_outputs = false;
+    // vdl_plan_set_wide_sums / VDL_WIDE_SUMS: 0 off, 1 wide (every output carries its bits 64..127), 2 checked (... and a value outside
+    // int64 fails the run).  wide_hi: the high words of the last run's partial words, laid out as `words` is; wide_note: what served
+    // the scans, or why the run was refused
+    int wide = 0;
+    std::string wide_note;
+    BufP wide_hi;
+    int64_t wide_hi_cap = 0;
+    std::vector<int64_t> wide_host_hi;
     // vdl_plan_set_order: the outputs of vdl_run come back permuted by one order and cut to the limit (vdl_genexec.h "order step")
     struct OrderSpec {
         bool set = false;
@@ -521,6 +531,28 @@ inline void refuse_order_sharded(const vdl_plan *p, bool merges = false) {
                                          "collectives to its caller: the merge of the ranks' ordered rows lives in vdl_run_sharded; run the plan through "
                                          "vdl_run_sharded, or clear the order");
 }
+// Wide sums (vdl_plan_set_wide_sums) are served where every sum of the plan is computed by a fused aggregate scan.  "" = this plan's
+// are; else the reason vdl_run refuses it with, naming the route its sums would take
+inline std::string wide_refusal(const vdl_plan *p) {
+    if (!p->wide) return "";
+    if (!p->fused.ok)
+        return "wide sums are on for this plan (vdl_plan_set_wide_sums), but it does not fuse as a whole into aggregate scans (" + p->fused.why_not + "): " +
+               (p->fused.proj.ok ? "its fused front feeds a GROUP BY tail whose sums run through k_group_fold / k_seg_fold"
+                                 : "its statements run one by one and its sums through k_fold_global / k_group_fold / k_seg_fold") +
+               ", which have no wide form; clear the switch to run it";
+    if (!p->use_fusion)
+        return "wide sums are on for this plan (vdl_plan_set_wide_sums), but its fusion is off (vdl_plan_set_fusion): the statements run one by one and the sums through "
+               "k_fold_global / k_group_fold / k_seg_fold, which have no wide form; switch fusion on, or clear the switch";
+    return "";
+}
+// every sharded entry point refuses a plan with wide sums on: the ranks' partial words are merged with 64-bit adds
+inline void refuse_wide_sharded(const vdl_plan *p, const char *entry) {
+    if (p && p->wide)
+        throw Error(VDL_ERR_UNSUPPORTED, std::string(entry) + ": wide sums are on for this plan (vdl_plan_set_wide_sums), and the sharded routes merge the ranks' partial words "
+                                         "with 64-bit operators (the merge has no add-with-carry); run it on one GPU with vdl_run, or clear the switch");
+}
+void wide_check_outputs(vdl_plan *p);                                             // vdl_engine.cpp: checked sums, VDL_ERR_OVERFLOW on the first value outside int64
+std::string wide_decimal(int64_t lo, int64_t hi);
 // the exchange route under a switched-on order merges per-rank top-N candidates: "" = this order can be served, else why not
 inline std::string order_exchange_refusal(const vdl_plan *p) {
     if (!p->order.set || !p->order.sharded || (p->order.limit > 0 && p->order.limit <= kOrdTopMax)) return "";

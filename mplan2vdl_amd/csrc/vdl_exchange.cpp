@@ -250,6 +250,7 @@ int vdl_exchange_begin(vdl_ctx *c, vdl_plan *p, int world, int64_t *counts_host)
     if (!c || !p || !counts_host || world < 1 || world > kMaxExWorld) return VDL_ERR_ARG;
     return guard(c, [&] {
         refuse_order_sharded(p);
+        refuse_wide_sharded(p, "vdl_exchange_begin");
         exchange_local(c, p, world);
         exchange_route(c, p, nullptr, counts_host);
     });

@@ -988,6 +988,39 @@ int64_t eval_scalar(const Scalar &s, const int64_t *agg) {
     }
 }
 
+wide_t apply_bin_wide(int op, wide_t a, wide_t b) {
+    typedef unsigned __int128 uwide_t;
+    switch (op) {
+    case B_LAND: return (a != 0) && (b != 0);
+    case B_LOR:  return (a != 0) || (b != 0);
+    case B_BAND: return a & b;
+    case B_BOR:  return a | b;
+    case B_SHIFT:
+        if (b >= 0) return a >> (b > 127 ? 127 : (int)b);
+        if (b <= -128) return 0;
+        return (wide_t)((uwide_t)a << (unsigned)(-b));
+    case B_EQ:  return a == b;
+    case B_ADD: return (wide_t)((uwide_t)a + (uwide_t)b);
+    case B_SUB: return (wide_t)((uwide_t)a - (uwide_t)b);
+    case B_GT:  return a > b;
+    case B_MUL: return (wide_t)((uwide_t)a * (uwide_t)b);
+    case B_DIV:
+        if (b == 0) return 0;
+        if (b == -1) return (wide_t)((uwide_t)0 - (uwide_t)a);
+        return a / b;
+    default:
+        if (b == 0 || b == -1) return 0;
+        return a % b;
+    }
+}
+wide_t eval_scalar_wide(const Scalar &s, const wide_t *agg) {
+    switch (s.k) {
+    case Scalar::AGG: return agg[s.agg];
+    case Scalar::CONST: return (wide_t)s.c;
+    default: return apply_bin_wide(s.bin, eval_scalar_wide(*s.l, agg), eval_scalar_wide(*s.r, agg));
+    }
+}
+
 static void show_col(const ScanColumn &c, size_t k, std::ostringstream &o);
 // ProjPlan (vdl_fuse.h): the selection of the program's Partition key, and the atom statements living on it that the
 // rest of the program reads.

@@ -146,5 +146,11 @@ void rewrite_program(Program &P);            // equivalent forms the planner and
 FusedPlan fuse_program(const Program &P);
 std::string describe_fused(const FusedPlan &F);
 int64_t eval_scalar(const Scalar &s, const int64_t *agg_values);
+// Wide sums (vdl_plan_set_wide_sums): the same expression over the exact 128-bit aggregate values, in two's-complement 128-bit
+// arithmetic with wrap-around -- apply_bin's rules widened: x / 0 = x % 0 = 0, x / -1 = 0 - x (wrapping), x % -1 = 0, a right shift by
+// 127 or more leaves the sign, a left shift by 128 or more leaves 0.  Host only.
+typedef __int128 wide_t;
+wide_t apply_bin_wide(int op, wide_t a, wide_t b);
+wide_t eval_scalar_wide(const Scalar &s, const wide_t *agg_values);
 
 }  // namespace vdl

@@ -315,6 +315,7 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
     if (has_sat_diff(C, D)) o << "#define VDL_SAT_DIFF 1\n";
     if (has_lookup_decode(C)) o << "#define VDL_LOOKUP_DECODE 1\n";
     if (kind == MSCAN && sh.batch) o << "#define VDL_BATCH " << sh.batch << "\n#define VDL_BATCH_NAGG " << D.nagg << "\n";
+    if (kind == MSCAN && sh.wide) o << "#define VDL_WIDE 1\n";
     if (kind == MSCAN && sh.census) o << "#define VDL_CENSUS 1\n";
     if (kind == MSCAN && C.packed) o << "#define VDL_PACKED 1\n";
     if (kind == MSCAN && C.lazy && C.packed) {
@@ -472,7 +473,7 @@ std::string entry_name(Kind kind, const MsArgs &C, const MScanDesc &D, const Sha
     int eager_filters = 0;
     for (int c = 0; c < C.ncol; c++) eager_filters += ((C.filtered >> c) & 1u) && !((C.derived >> c) & 1u) && C.stage(c) == 0;
     return std::string("vdl_jit_mscan_") + (sh.grouped ? "grouped_" : "") + (C.packed ? "packed_" : "") + "u" + std::to_string(sh.u) + (C.lazy ? "_staged" + std::to_string(eager_filters) + "_" : "_") +
-           (sh.census ? "census_" : "") + tag + (sh.batch ? "_batch" + std::to_string(sh.batch) : "") + (sh.rt_bounds ? "_rtb" : "");
+           (sh.census ? "census_" : "") + tag + (sh.batch ? "_batch" + std::to_string(sh.batch) : "") + (sh.rt_bounds ? "_rtb" : "") + (sh.wide ? "_wide" : "");
 }
 
 bool compile(const std::string &src, const std::string &arch, std::vector<char> &code, std::string &log, Origin *origin) {

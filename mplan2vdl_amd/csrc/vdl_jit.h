@@ -18,7 +18,10 @@ struct Shape { int nc = 0, u = 0; bool vec = false, grouped = false, der = false
                bool rt_bounds = false;
                // a batched scan (vdl_run_batch): that many plans' descriptors per launch, each with its own count and accumulators
                // (vdl_mscan_body.h VDL_BATCH); 0 = the scan of one plan.  Always with rt_bounds: that is what makes the code shareable
-               int batch = 0; };
+               int batch = 0;
+               // wide sums (vdl_plan_set_wide_sums): the unit is built with VDL_WIDE (vdl_mscan_body.h) -- (lo, hi) SUM accumulators, the
+               // high words behind the aggregates' in LDS and in the partials.  Source, key and entry name change only when it is set
+               bool wide = false; };
 
 // what is specialised: an aggregate scan, or the two passes of the projection scan (fused front; dimension scans are the
 // select pass with bitmap_only set)

@@ -55,8 +55,16 @@ const char *mscan_kernel_name(const ScanLaunch &cfg);
 // bucket {row count, aggregates...}, last word = rows whose key fell outside [pmin, pmin + pcount).
 // resolve_first: turn AGG_FIRST row ids into column values (single rank only).
 // jit_fn: the scan kernel specialised for this plan (vdl_jit.cpp) instead of the precompiled variant cfg names
+// out_hi: a wide-sums scan (d.wide) leaves bits 64..127 of every word of `out` at the same place of out_hi -- the
+// exact high word of a SUM aggregate, the sign extension of every other word (an AGG_FIRST word: of the row id; the host extends the value)
 hipError_t launch_mscan(const MScanCols &cols, const MScanDesc &d, const MScanDesc *dev_desc, const ScanLaunch &cfg, bool grouped,
-                        bool never, int64_t *out, bool resolve_first, hipStream_t s, hipFunction_t jit_fn = nullptr);
+                        bool never, int64_t *out, bool resolve_first, hipStream_t s, hipFunction_t jit_fn = nullptr, int64_t *out_hi = nullptr);
+int mscan_sums(const MScanDesc &d);                                  // its SUM aggregates: the high words a wide scan carries per block / bucket
+int64_t mscan_partial_words(const MScanDesc &d, bool grouped);       // words of ONE block's partials (MScanDesc::block_partials), wide or not
+// the wide-sums build of the precompiled kernels (vdl_mscan_wide.hip): variant for variant the shapes of vdl_mscan.hip
+const void *mscan_wide_fn(int variant);
+hipError_t launch_mscan_wide_kernel(int variant, int grid, int block, size_t lds_bytes, hipStream_t s, const MsArgs &a, const MScanDesc *dev_desc);
+hipError_t launch_mscan_finish_wide(const MScanDesc &d, const MScanDesc *dev_desc, int nblocks, bool grouped, int64_t *out, int64_t *out_hi, hipStream_t s);
 // A batched scan (vdl_run_batch): `fn` is the kernel specialised for k plans that share `cols` (vdl_jit.cpp, Shape::batch), b.d[q] slot
 // q's descriptor on the device, b.partials room for grid x k x (1 + nagg) words; the finish step folds the blocks' partials and leaves slot
 // q's 1 + nagg words at outs[q].  d: any slot's descriptor on the host (the aggregates' kinds are the same in all of them).

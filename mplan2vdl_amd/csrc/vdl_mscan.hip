@@ -17,6 +17,7 @@
 // + Fold per aggregate) and :721-730 (Select -> FoldSelect + Gather).
 #include "vdl_kernels.h"
 #include "vdl_mscan_body.h"
+#include "vdl_mscan_variants.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -126,28 +127,29 @@ typedef void (*mscan_fn)(const MsArgs, const MScanDesc *);
 struct MsVariant { int nc, u; bool vec, grouped, der; mscan_fn fn; const char *name; };
 #define VDL_MS(NC, U, VEC, NT, GR) {NC, U, VEC, GR, false, k_mscan<NC, U, VEC, NT, GR, false>, "k_mscan<" #NC "," #U "," #VEC "," #NT "," #GR ">"}
 #define VDL_MSJ(NC, U, VEC, NT, GR) {NC, U, VEC, GR, true, k_mscan<NC, U, VEC, NT, GR, true>, "k_mscan_join<" #NC "," #U "," #VEC "," #NT "," #GR ">"}
-const MsVariant kMsVariants[] = {
-    VDL_MS(4, 6, true, true, false),  VDL_MS(8, 4, true, true, false),
-    VDL_MS(4, 4, false, false, false), VDL_MS(8, 4, false, false, false),
-    VDL_MS(4, 6, true, true, true),   VDL_MS(8, 2, true, true, true),   VDL_MS(8, 4, true, true, true),
-    VDL_MS(4, 4, false, false, true),  VDL_MS(8, 4, false, false, true),
-    VDL_MS(8, 1, true, true, true),   VDL_MS(8, 3, true, true, true),      // VDL_GROUP_U sweeps (tools/q1_ab.sh)
-    // scans with derived columns (FK lookups: fused join scans)
-    VDL_MSJ(8, 4, true, true, false), VDL_MSJ(8, 4, false, false, false),
-    VDL_MSJ(8, 2, true, true, true),  VDL_MSJ(8, 2, false, false, true),
-    VDL_MSJ(12, 2, true, true, false), VDL_MSJ(12, 2, false, false, false),
-    VDL_MSJ(12, 1, true, true, true),  VDL_MSJ(12, 1, false, false, true),      // (U = 2 spills 720 B/lane in the grouped form)
-};
+const MsVariant kMsVariants[] = { VDL_MS_VARIANTS(VDL_MS, VDL_MSJ) };      // (the list: vdl_mscan_variants.h)
 #undef VDL_MS
 #undef VDL_MSJ
 constexpr int kNumMsVariants = sizeof(kMsVariants) / sizeof(kMsVariants[0]);
 
 size_t ms_lds_bytes(const MScanDesc &d, bool grouped) {
-    if (grouped) return ((size_t)((d.pcount * (d.nagg + 1)) | 1) * (size_t)d.replicas + (size_t)kMsBlock + (size_t)(d.nagg + 1)) * sizeof(int64_t);
-    return (size_t)(d.nagg > 0 ? d.nagg : 1) * kMsBlock * sizeof(int64_t);
+    // (wide sums: one more word per SUM aggregate -- and bucket -- behind the table, one more lane slot each in the global form)
+    const int nsum = d.wide ? mscan_sums(d) : 0;
+    if (grouped) return ((size_t)((d.pcount * (d.nagg + 1 + nsum)) | 1) * (size_t)d.replicas + (size_t)kMsBlock + (size_t)(d.nagg + 1)) * sizeof(int64_t);
+    return (size_t)(d.nagg + nsum > 0 ? d.nagg + nsum : 1) * kMsBlock * sizeof(int64_t);
 }
 
 }  // namespace
+
+int mscan_sums(const MScanDesc &d) {
+    int n = 0;
+    for (int j = 0; j < d.nagg; j++) n += d.agg[j].kind == AGG_SUM ? 1 : 0;
+    return n;
+}
+int64_t mscan_partial_words(const MScanDesc &d, bool grouped) {
+    const int nsum = d.wide ? mscan_sums(d) : 0;
+    return grouped ? d.pcount * (d.nagg + 1 + nsum) + 1 : d.nagg + 1 + nsum;
+}
 
 ScanLaunch mscan_launch_config(const MScanCols &cols, MScanDesc &d, bool grouped, int num_cus) {
     bool vec = true, der = false;
@@ -171,16 +173,22 @@ ScanLaunch mscan_launch_config(const MScanCols &cols, MScanDesc &d, bool grouped
     d.replicas = 1;
     if (grouped) {
         d.ncomp = composite_key(d.key, d.nkey, d.comp, &d.key_masked, &d.key_mask);
-        const int64_t words = d.pcount * (d.nagg + 1);
+        const int64_t plain = d.pcount * (d.nagg + 1);
+        const int64_t words = plain + d.pcount * (d.wide ? mscan_sums(d) : 0);             // (wide sums: the table with its high words)
         int r = 8;
-        while (r > 1 && words * r > 2304) r >>= 1;         // replicas <= 18 KiB (+ 2 KiB of trash rows): LDS never caps the occupancy
+        while (r > 1 && plain * r > 2304) r >>= 1;         // replicas <= 18 KiB (+ 2 KiB of trash rows): LDS never caps the occupancy
+        // Wide sums keep the replicas the plain table gets while the larger table stays within 32 KiB (five blocks per CU), and halve them
+        // beyond: contention costs more than occupancy.  Q1 at SF100, one form (u = 2, eager), kernel time: plain 8 replicas 1.69 ms, plain 4
+        // replicas 2.69 ms; wide 4 replicas (the 18 KiB rule applied to the larger table) 3.12 ms, wide 8 replicas 2.25 ms
+        // (profiles/r20/q1_replicas.txt).
+        while (r > 1 && words * r > 4096) r >>= 1;
         const char *tune = getenv("VDL_GROUP_TUNE");
         if (tune) { int v = atoi(tune); if (v >= 1 && v <= 64 && words * v <= 8192) r = v; }
         d.replicas = r;
     }
     const MsVariant &v = kMsVariants[cfg.variant];
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v.fn, kMsBlock, ms_lds_bytes(d, grouped)) != hipSuccess || per_cu < 1) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, d.wide ? mscan_wide_fn(cfg.variant) : (const void *)v.fn, kMsBlock, ms_lds_bytes(d, grouped)) != hipSuccess || per_cu < 1) {
         (void)hipGetLastError();
         per_cu = 2;
     }
@@ -206,9 +214,10 @@ void mscan_variant_shape(const ScanLaunch &cfg, int *nc, int *u, bool *vec, bool
 }
 
 hipError_t launch_mscan(const MScanCols &cols, const MScanDesc &d, const MScanDesc *dev_desc, const ScanLaunch &cfg, bool grouped,
-                        bool never, int64_t *out, bool resolve_first, hipStream_t s, hipFunction_t jit_fn) {
+                        bool never, int64_t *out, bool resolve_first, hipStream_t s, hipFunction_t jit_fn, int64_t *out_hi) {
     (void)hipGetLastError();
     if (cfg.variant < 0 || cfg.variant >= kNumMsVariants) return hipErrorInvalidValue;
+    if ((d.wide != 0) != (out_hi != nullptr)) return hipErrorInvalidValue;      // a wide scan leaves its high words, and nobody else does
     int nblocks = 0;
     if (!never && cols.n > 0) {
         if (jit_fn) {
@@ -216,12 +225,19 @@ hipError_t launch_mscan(const MScanCols &cols, const MScanDesc &d, const MScanDe
             void *params[] = {&a, &dev_desc};
             const hipError_t e = hipModuleLaunchKernel(jit_fn, (unsigned)cfg.grid, 1, 1, (unsigned)cfg.block, 1, 1, (unsigned)ms_lds_bytes(d, grouped), s, params, nullptr);
             if (e != hipSuccess) return e;
+        } else if (d.wide) {
+            const hipError_t e = launch_mscan_wide_kernel(cfg.variant, cfg.grid, cfg.block, ms_lds_bytes(d, grouped), s, ms_args(cols), dev_desc);
+            if (e != hipSuccess) return e;
         } else {
             hipLaunchKernelGGL(kMsVariants[cfg.variant].fn, dim3(cfg.grid), dim3(cfg.block), ms_lds_bytes(d, grouped), s, ms_args(cols), dev_desc);
         }
         nblocks = cfg.grid;
     }
     const int64_t words = grouped ? d.pcount * (d.nagg + 1) + 1 : d.nagg + 1;
+    if (d.wide) {
+        const hipError_t e = launch_mscan_finish_wide(d, dev_desc, nblocks, grouped, out, out_hi, s);
+        if (e != hipSuccess) return e;
+    } else
     k_mscan_finish<<<(int)((words + 3) / 4), 256, 0, s>>>(dev_desc, nblocks, grouped ? 1 : 0, out);
     if (grouped && resolve_first) k_mscan_first<<<(int)((d.pcount + 255) / 256), 256, 0, s>>>(ms_args(cols), dev_desc, 0, out);
     return hipGetLastError();

@@ -64,6 +64,33 @@ __device__ __forceinline__ int64_t wave_reduce(int64_t x, int rk) {
     for (int off = kWave / 2; off > 0; off >>= 1) x = r_combine(rk, x, __shfl_down(x, off, kWave));
     return x;
 }
+#ifdef VDL_WIDE
+// WIDE SUMS (vdl_plan_set_wide_sums): every SUM accumulator is a pair (lo, hi) -- bits 0..63 and 64..127 of the
+// exact two's-complement sum of the int64 terms.  lo is the word the plain build keeps; only the accumulation widens, the term stays the
+// int64 the program computes.  The aggregates keep their words, the high words of the SUM aggregates lie behind them in aggregate
+// order: LDS lane slots nagg .. nagg + nsum - 1 (global form), G * nsum words behind a replica's table (grouped form), and the same
+// in the block's partials.  Two 64-bit adds and a compare per step: no 128-bit type, no library call.
+#ifdef VDL_BATCH
+#error "wide sums are not batched: a plan with the switch on runs alone (vdl_run_batch)"
+#endif
+__device__ __forceinline__ int wide_nsum(const MScanDesc &D, int j) {      // SUM aggregates below j: where aggregate j's high word lies
+    int h = 0;
+#pragma unroll
+    for (int k = 0; k < kMaxGroupAggs; k++) h += (k < j && D.agg[k].kind == AGG_SUM) ? 1 : 0;
+    return h;
+}
+__device__ __forceinline__ void wide_add(uint64_t &lo, uint64_t &hi, uint64_t blo, uint64_t bhi) {
+    lo += blo;
+    hi += bhi + (uint64_t)(lo < blo);
+}
+__device__ __forceinline__ void wide_wave_reduce(uint64_t &lo, uint64_t &hi) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const uint64_t blo = __shfl_down(lo, off, kWave), bhi = __shfl_down(hi, off, kWave);
+        wide_add(lo, hi, blo, bhi);
+    }
+}
+#endif
 __device__ __forceinline__ int64_t load_scalar(const void *p, int width, int64_t i) {
     switch (width) {
     case 8: return ((const int64_t *)p)[i];
@@ -657,7 +684,13 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
     const int W = nagg + 1;
     const int64_t G = D.pcount;
     const int64_t words = G * W;
+#ifdef VDL_WIDE
+    const int nsum = wide_nsum(D, nagg);
+    const int64_t hwords = GROUPED ? G * nsum : 0;         // a replica's high words, [bucket][SUM aggregate], behind its table
+    const int64_t rstride = (words + hwords) | 1;
+#else
     const int64_t rstride = words | 1;                     // odd int64 stride: replicas start on different banks
+#endif
     const int R = D.replicas;
 
     int64_t cnt = 0, oob = 0;
@@ -729,8 +762,15 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
         // atomic instruction every lane addresses its own word (same 1 + j for all), so there is no conflict
         trash = (int)((int64_t)R * rstride + (int64_t)tid - (int64_t)(tid % R) * rstride);
         for (int64_t i = tid; i < BS + W; i += BS) lds[(int64_t)R * rstride + i] = 0;
+#ifdef VDL_WIDE
+        for (int r = 0; r < R; r++)
+            for (int64_t i = tid; i < hwords; i += BS) lds[(int64_t)r * rstride + words + i] = 0;
+#endif
     } else {
         for (int j = 0; j < nagg; j++) lds[(int64_t)j * BS + tid] = r_identity(rk_of(D.agg[j].kind));
+#ifdef VDL_WIDE
+        for (int h = 0; h < nsum; h++) lds[(int64_t)(nagg + h) * BS + tid] = 0;
+#endif
     }
     __syncthreads();
 #endif
@@ -859,6 +899,9 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
             }
         }
         int off[RW];
+#ifdef VDL_WIDE
+        int hoff[RW] = {};                                 // the bucket's high words (read only where pass[r])
+#endif
         if (GROUPED) {
             int64_t acc[RW];
             group_key<NC, RW>(D, v, acc);
@@ -870,18 +913,57 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
                 pass[r] = pass[r] && in;
                 // rows that do not count go to this lane's own trash slot with the identity: no branches
                 off[r] = pass[r] ? (int)b * W : trash;         // the trash row absorbs whatever is added: no selects below
+#ifdef VDL_WIDE
+                hoff[r] = pass[r] ? (int)words + (int)b * nsum : 0;
+#endif
                 atomicAdd((unsigned long long *)&mytab[off[r]], 1ull);
             }
         } else {
 #pragma unroll
             for (int r = 0; r < RW; r++) cnt += pass[r] ? 1 : 0;
         }
+#ifdef VDL_WIDE
+        int hs = 0;                                        // SUM aggregates so far: the place of the next one's high word
+#endif
         VDL_SPEC_UNROLL
         for (int j = 0; j < nagg; j++) {                   // runtime loop: descriptors by scalar loads (specialised: unrolled)
             const MAggDesc d = D.agg[j];                   // whole descriptor into SGPRs: one scalar-load wait per aggregate
             const int rk = rk_of(d.kind);
             int64_t t[RW];
             eval_term<NC, RW>(d, v, rowid, t);
+#ifdef VDL_WIDE
+            if (rk == R_SUM) {
+                if (GROUPED) {
+                    // A RETURNING atomic add on the low word: the adds to one word are serialised, every one sees the word as its
+                    // predecessors left it, so (old + t < t) is that add's own carry and the carries of all adds sum to the number of
+                    // times the word wrapped -- exact however many lanes meet in one bucket.  The high word takes sign + carry, which
+                    // is 0 for a non-negative term that does not carry: then there is no second atomic.  Rows that do not count have
+                    // added to the lane's trash row and leave the high words alone.
+#pragma unroll
+                    for (int r = 0; r < RW; r++) {
+                        const uint64_t x = (uint64_t)t[r];
+                        const uint64_t old = atomicAdd((unsigned long long *)&mytab[off[r] + 1 + j], (unsigned long long)x);
+                        const uint64_t up = (uint64_t)(t[r] >> 63) + (uint64_t)(old + x < x);
+                        if (pass[r] && up) atomicAdd((unsigned long long *)&mytab[hoff[r] + hs], (unsigned long long)up);
+                    }
+                } else {
+                    // the general per-row step, lo += t; hi += (t >> 63) + (lo < t), over the lane's rows, then into the lane's own slots
+                    uint64_t slo = 0, shi = 0;
+#pragma unroll
+                    for (int r = 0; r < RW; r++) {
+                        const int64_t x = pass[r] ? t[r] : 0;
+                        slo += (uint64_t)x;
+                        shi += (uint64_t)(x >> 63) + (uint64_t)(slo < (uint64_t)x);
+                    }
+                    uint64_t *ls = (uint64_t *)&lds[(int64_t)j * BS + tid], *hsl = (uint64_t *)&lds[(int64_t)(nagg + hs) * BS + tid];
+                    uint64_t lo = *ls, hi = *hsl;
+                    wide_add(lo, hi, slo, shi);
+                    *ls = lo; *hsl = hi;
+                }
+                hs++;
+                continue;
+            }
+#endif
             if (GROUPED) {
                 if (rk == R_SUM) {
 #pragma unroll
@@ -1168,6 +1250,62 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
         for (int c = 0; c < NC; c++) if (census_cnt[c]) atomicAdd(&Dr.census[c], census_cnt[c]);
     }
 #endif
+#ifdef VDL_WIDE
+    // the block's partials with the high words behind: global [1 + nagg][nsum]; grouped [pcount * (1 + nagg)][rows outside][pcount * nsum].
+    // Every pair is folded with its carry: over the replicas (grouped), over the wave and the block's waves (global).
+    __shared__ int64_t redh[kMsBlock / kWave];
+    if (GROUPED) {
+        int64_t *dst = Dr.block_partials + (int64_t)blockIdx.x * (words + 1 + hwords);
+        for (int64_t i = tid; i < words; i += BS) {
+            const int w = (int)(i % W);
+            const int rk = w == 0 ? R_SUM : rk_of(D.agg[w - 1].kind);
+            if (w > 0 && rk == R_SUM) {
+                const int64_t hi_at = (i / W) * nsum + wide_nsum(D, w - 1);
+                uint64_t lo = (uint64_t)lds[i], hi = (uint64_t)lds[words + hi_at];
+                for (int r = 1; r < R; r++) wide_add(lo, hi, (uint64_t)lds[(int64_t)r * rstride + i], (uint64_t)lds[(int64_t)r * rstride + words + hi_at]);
+                dst[i] = (int64_t)lo;
+                dst[words + 1 + hi_at] = (int64_t)hi;
+                continue;
+            }
+            int64_t x = lds[i];
+            for (int r = 1; r < R; r++) x = r_combine(rk, x, lds[(int64_t)r * rstride + i]);
+            dst[i] = x;
+        }
+        oob = wave_reduce(oob, R_SUM);
+        if (lane == 0) red[wave] = oob;
+        __syncthreads();
+        if (tid == 0) { int64_t x = 0; for (int w = 0; w < kMsBlock / kWave; w++) x += red[w]; dst[words] = x; }
+    } else {
+        int64_t *dst = Dr.block_partials + (int64_t)blockIdx.x * (W + nsum);
+        int hs = 0;
+        for (int j = -1; j < nagg; j++) {
+            const int rk = j < 0 ? R_SUM : rk_of(D.agg[j].kind);
+            const bool pair = j >= 0 && rk == R_SUM;
+            if (pair) {
+                uint64_t lo = (uint64_t)lds[(int64_t)j * BS + tid], hi = (uint64_t)lds[(int64_t)(nagg + hs) * BS + tid];
+                wide_wave_reduce(lo, hi);
+                if (lane == 0) { red[wave] = (int64_t)lo; redh[wave] = (int64_t)hi; }
+            } else {
+                int64_t x = j < 0 ? cnt : lds[(int64_t)j * BS + tid];
+                x = wave_reduce(x, rk);
+                if (lane == 0) red[wave] = x;
+            }
+            __syncthreads();
+            if (tid == 0 && pair) {
+                uint64_t lo = (uint64_t)red[0], hi = (uint64_t)redh[0];
+                for (int w = 1; w < kMsBlock / kWave; w++) wide_add(lo, hi, (uint64_t)red[w], (uint64_t)redh[w]);
+                dst[j + 1] = (int64_t)lo;
+                dst[W + hs] = (int64_t)hi;
+            } else if (tid == 0) {
+                int64_t y = red[0];
+                for (int w = 1; w < kMsBlock / kWave; w++) y = r_combine(rk, y, red[w]);
+                dst[j + 1] = y;
+            }
+            if (pair) hs++;
+            __syncthreads();
+        }
+    }
+#else
     if (GROUPED) {
         int64_t *dst = Dr.block_partials + (int64_t)blockIdx.x * (words + 1);
         for (int64_t i = tid; i < words; i += BS) {
@@ -1197,6 +1335,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
             __syncthreads();
         }
     }
+#endif
 }
 
 // ---- projection scan (ProjPlan, vdl_fuse.h) -----------------------------------------------------------------------------

@@ -119,9 +119,13 @@ struct MAggDesc {
     int64_t fa[kMaxProjCols] = {}, fs[kMaxProjCols] = {};
 };
 struct MScanDesc {                           // lives in device memory, read with scalar loads
-    int nagg = 0, nkey = 0, replicas = 1, pad = 0;
+    // wide (it sits in what was padding): the scan runs the wide-sums build of the kernels (VDL_WIDE in vdl_mscan_body.h) -- what the host
+    // sizes LDS, the partials and the finish step by; the kernels themselves are built one way or the other and never read it
+    int nagg = 0, nkey = 0, replicas = 1, wide = 0;
     int64_t pmin = 0, pcount = 0;            // grouped: bucket = key - pmin in [0, pcount)
-    int64_t *block_partials = nullptr;       // global: [grid][1 + nagg]; grouped: [grid][pcount * (1 + nagg) + 1]
+    // global: [grid][1 + nagg]; grouped: [grid][pcount * (1 + nagg) + 1]; wide: the high words of the SUM aggregates behind those, nsum
+    // per block (global) or pcount * nsum (grouped, [bucket][SUM aggregate])
+    int64_t *block_partials = nullptr;
     int64_t flo[kMaxVCols] = {}, fhi[kMaxVCols] = {};            // range filter per column (read only for filtered columns)
     int dkind[kMaxVCols] = {}, dsrc[kMaxVCols] = {}, dsrc2[kMaxVCols] = {};   // derived columns: VColKind, source column(s); VC_FORM: first step, steps
     // formula columns (VC_FORM), one after the other: column c owns form[dsrc[c] .. dsrc[c] + dsrc2[c]) -- first its dtests[c]

@@ -180,6 +180,7 @@ static bool bind_form(vdl_ctx *c, const vdl_plan *p, size_t s, bool grouped, con
     int64_t bpr = 0;
     bind_mscan(c, sp, pc, pd, &bpr, p->row_offset, f.every_column ? 2 : 1);
     pd.block_partials = d.block_partials;
+    pd.wide = d.wide;
     out.cols = &pc;
     out.desc = &pd;
     if (pc.ncol > 10) { why = "the packed form takes at most 10 columns"; return false; }
@@ -216,6 +217,7 @@ static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, c
     if (!bind_form(c, p, s, grouped, f, sh.u, cols, d, out.b, why)) return false;
     const MsArgs &args = out.b.args;
     const MScanDesc &desc = *out.b.desc;
+    sh.wide = desc.wide != 0;                                  // (wide sums: every form accumulates through the body's one process step)
     jit::Origin from = jit::COMPILED;
     if (!jit::compile(jit::mscan_source(args, desc, sh), c->arch, code, why, &from)) { why = why.substr(0, 400); return false; }
     count_build(p, "scan " + std::to_string(s), from);
@@ -238,7 +240,7 @@ static bool build_specialised(vdl_ctx *c, vdl_plan *p, size_t s, bool grouped, c
     if (grid < 1) grid = 1;
     out.grid = (int)grid; out.per_cu = per_cu; out.code_bytes = code.size(); out.form = f; out.form.u = sh.u;
     out.name = jit_name(sh, *out.b.cols);
-    out.name.insert(out.name.size() - 1, std::string(f.suffix()) + (sh.rt_bounds ? ",rtb" : ""));
+    out.name.insert(out.name.size() - 1, std::string(f.suffix()) + (sh.rt_bounds ? ",rtb" : "") + (sh.wide ? ",wide" : ""));
     out.stages = stages_text(p, s, args);
     out.packed = packed_text(p, s, *out.b.cols);
     return true;
@@ -311,6 +313,8 @@ void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
         if (!p->mjit[s]) continue;
         const bool grouped = s >= ns;
         int64_t *out = dev_words + (grouped ? p->gword_offset[s - ns] : p->word_offset[s]);
+        // (wide sums: the candidates leave their high words where the run will)
+        int64_t *out_hi = p->wide && p->wide_hi ? (int64_t *)p->wide_hi->p + (grouped ? p->gword_offset[s - ns] : p->word_offset[s]) : nullptr;
         Specialised best;
         float best_ms = 0;
         std::string tried;
@@ -352,6 +356,7 @@ void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
             int64_t bpr = 0;
             bind_mscan(c, p->fused.scans[s], plain_cols, *plain_desc, &bpr, p->row_offset);
             plain_desc->block_partials = p->mdesc[s].block_partials;
+            plain_desc->wide = p->mdesc[s].wide;
             cols = &plain_cols;
             desc = plain_desc.get();
         }
@@ -366,13 +371,13 @@ void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
             ScanLaunch cfg = p->mcfg[s];
             cfg.grid = cand.grid;
             HIP_CHECK(hipMemcpyAsync(p->mdev[s]->p, cand.b.desc, sizeof(MScanDesc), hipMemcpyHostToDevice, c->stream));
-            const float ms = median_ms([&] { HIP_CHECK(launch_mscan(*cand.b.cols, *cand.b.desc, (const MScanDesc *)p->mdev[s]->p, cfg, grouped, false, out, false, c->stream, cand.k->fn)); });
+            const float ms = median_ms([&] { HIP_CHECK(launch_mscan(*cand.b.cols, *cand.b.desc, (const MScanDesc *)p->mdev[s]->p, cfg, grouped, false, out, false, c->stream, cand.k->fn, out_hi)); });
             tried += " u=" + std::to_string(f.u) + f.suffix() + ":" + std::to_string((int)(ms * 1000)) + "us";
             if (!best.k || ms < best_ms * 0.98f) { best = cand; best_ms = ms; }
             if (f.kind == ScanForm::EAGER && (best_u == 0 || cand.k == best.k)) best_u = f.u;       // the staged forms start from the quickest eager shape
         }
         if (!best.k) continue;
-        if (!grouped && use_kscan(p->fused.scans[s]) && p->block_partials[s] && pin_u <= 0) {
+        if (!grouped && use_kscan(p->fused.scans[s]) && p->block_partials[s] && pin_u <= 0 && !p->wide) {      // (k_scan has no wide build)
             // the hand-tuned single-aggregate kernel is a candidate too
             const float ms = median_ms([&] {
                 HIP_CHECK(launch_scan(p->sargs[s], p->scfg[s], c->stream));
@@ -388,6 +393,7 @@ void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
             }
         }
         install_form(p, s, best);
+        if (p->wide) p->wide_note += "; scan " + std::to_string(s) + " tuned -> " + best.name;      // (the note named the form the scan was bound in)
         p->jit_note += "scan " + std::to_string(s) + " tuned:" + tried + " -> " + best.name + (best.packed.empty() ? "" : " (packed: " + best.packed + ")") +
                        (best.stages.empty() ? "" : " (read late: " + best.stages + ")") + "; " + builds_text(p, "scan " + std::to_string(s));
         if ((int)s == p->dominant)
@@ -441,7 +447,9 @@ int64_t scan_bytes_moved(vdl_ctx *c, vdl_plan *p, std::string &detail) {
     ScanLaunch cfg = p->mcfg[s];
     cfg.grid = cen.grid;
     int64_t *out = (int64_t *)words->p + (grouped ? p->gword_offset[s - ns] : p->word_offset[s]);
-    HIP_CHECK(launch_mscan(cols, d, (const MScanDesc *)ddev->p, cfg, grouped, false, out, false, c->stream, cen.k->fn));
+    BufP words_hi = d.wide ? dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(p->n_words, 1)) : nullptr;
+    int64_t *out_hi = words_hi ? (int64_t *)words_hi->p + (grouped ? p->gword_offset[s - ns] : p->word_offset[s]) : nullptr;
+    HIP_CHECK(launch_mscan(cols, d, (const MScanDesc *)ddev->p, cfg, grouped, false, out, false, c->stream, cen.k->fn, out_hi));
     unsigned long long lines[kMaxVCols] = {};
     c->fetch_to_host(counts->p, kMaxVCols, (int64_t *)lines, c->stream);
     for (int k = 0; k < cols.ncol; k++) {
@@ -469,6 +477,7 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
         int64_t bpr = 0;
         if (grouped) bind_mscan(c, F.gscans[s - ns], cols, *d, &bpr, 0);
         else bind_mscan(c, F.scans[s], cols, *d, &bpr, 0);
+        d->wide = p->wide ? 1 : 0;                                   // (the wide units build without a device like the others)
         p->image_roles["scan" + std::to_string(s)] = image_text(scan_columns(p, s), cols);
         p->lookup_roles["scan" + std::to_string(s)] = lookup_text(scan_columns(p, s), cols);
         const ScanLaunch cfg = mscan_launch_config(cols, *d, grouped, c->num_cus);
@@ -477,6 +486,7 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
         const ScanForm late = form_asked_for();
         jit::Shape sh = jit_shape(cols, cfg, late, p->jit_rt_bounds);
         if (getenv("VDL_JIT_CENSUS")) sh.census = true;              // (tests: the measurement build of a staged scan compiles too)
+        sh.wide = d->wide != 0;
         std::vector<char> code;
         std::string log;
         BoundForm b;
@@ -489,6 +499,7 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
         std::string name = jit_name(sh, *b.cols);
         if (b.args.packed) name.insert(name.size() - 1, late.suffix());
         if (sh.rt_bounds) name.insert(name.size() - 1, ",rtb");
+        if (sh.wide) name.insert(name.size() - 1, ",wide");
         p->jit_note += "scan " + std::to_string(s) + ": " + name + (b.args.packed ? " (packed: " + packed_text(p, s, *b.cols) + ")" : "") +
                        (b.args.queued ? " (queue)" : b.args.lazy ? " (late)" : "") + ", " + std::to_string(code.size()) + " B of code; ";
     }
@@ -500,6 +511,7 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
 // whose one scan is a grouped scan over table columns shares a grouped batch by the same rules; a batch never mixes the two kinds
 // (their shape keys differ).
 std::string batch_alone_reason(const vdl_plan *p, bool grouped_on) {
+    if (p->wide) return "wide sums are not batched";
     if (!p->use_fusion || !p->fused.ok) return "the plan is not fused";
     if (!p->use_jit) return "specialisation is off";
     const FusedPlan &F = p->fused;

@@ -37,6 +37,11 @@
 // those that differ in their literals alone share one scan of the columns, the others run alone inside the same call -- and one reply
 // is printed per line, stdin's first.  The options (--order-by included) apply to every program.  One line per program "vdlrun:
 // batch: <vdl_plan_batch_note>" goes to stderr.  Not with --gpus: a sharded run takes one plan.
+//   ... | vdlrun --wide-sums ...  |  vdlrun --checked-sums ...                       exact 128-bit SUM results
+// --wide-sums (vdl_plan_set_wide_sums 1): the reply keeps its shape and every value is printed as the exact decimal integer, of any
+// size (JSON has no limit; Python's json reads them as ints and resolve.py passes ints through).  --checked-sums (mode 2): a value
+// outside int64 fails the run, the message naming output, group and value, and vdlrun exits non-zero.  Fused plans only; not with
+// --gpus (every sharded entry point refuses the switch).  VDL_WIDE_SUMS=1|2 in the environment does the same when no option is given.
 // --batch-grouped: programs whose one scan is a GROUP BY over table columns share a grouped batch too (vdl_set_batch_grouped); without it
 // they run alone, as "grouped scans are not batched".
 #include <signal.h>
@@ -128,7 +133,7 @@ int die(vdl_ctx *c, const char *what, int rc) {
     return 1;
 }
 struct Reply {
-    struct Out { std::string name, tmp; std::vector<int64_t> vals; };
+    struct Out { std::string name, tmp; std::vector<int64_t> vals; std::vector<int64_t> hi; };      // hi: --wide-sums / --checked-sums, bits 64..127 of every value
     std::vector<Out> outs;
     std::vector<std::pair<std::string, double>> timings;
     bool replicated = true;          // every rank holds the whole answer (fold plans) / this is one rank's slice (Partition plans)
@@ -138,7 +143,9 @@ void collect(vdl_plan *plan, Reply &r) {
     for (int k = 0; k < vdl_n_outputs(plan); k++) {
         const char *name, *tmp; const int64_t *vals; size_t n;
         vdl_output(plan, k, &name, &tmp, &vals, &n);
-        r.outs.push_back({name, tmp, std::vector<int64_t>(vals, vals + n)});
+        r.outs.push_back({name, tmp, std::vector<int64_t>(vals, vals + n), {}});
+        const int64_t *hi = nullptr;
+        if (vdl_output_high(plan, k, &hi, nullptr) == VDL_OK && hi) r.outs.back().hi.assign(hi, hi + n);
     }
     for (int k = 0; k < vdl_n_timings(plan); k++) {
         const char *label; double us;
@@ -147,11 +154,23 @@ void collect(vdl_plan *plan, Reply &r) {
     }
 }
 
+// (hi << 64) | lo as a decimal integer of any size: JSON has no upper limit for one
+std::string wide_decimal(int64_t lo, int64_t hi) {
+    unsigned __int128 u = ((unsigned __int128)(uint64_t)hi << 64) | (uint64_t)lo;
+    if (hi < 0) u = (unsigned __int128)0 - u;
+    std::string s;
+    do { s.insert(s.begin(), (char)('0' + (int)(u % 10))); u /= 10; } while (u != 0);
+    return hi < 0 ? "-" + s : s;
+}
+
 void print_reply(const Reply &r) {
     std::printf("{\"results\": {");
     for (size_t k = 0; k < r.outs.size(); k++) {
         std::printf("%s\"%s\": {\".%s\": [", k ? ", " : "", r.outs[k].tmp.c_str(), r.outs[k].name.c_str());
-        for (size_t i = 0; i < r.outs[k].vals.size(); i++) std::printf("%s%lld", i ? ", " : "", (long long)r.outs[k].vals[i]);
+        for (size_t i = 0; i < r.outs[k].vals.size(); i++) {
+            if (i < r.outs[k].hi.size()) std::printf("%s%s", i ? ", " : "", wide_decimal(r.outs[k].vals[i], r.outs[k].hi[i]).c_str());      // wide sums: the exact value
+            else std::printf("%s%lld", i ? ", " : "", (long long)r.outs[k].vals[i]);
+        }
         std::printf("]}");
     }
     std::printf("}, \"timings\": {");
@@ -197,6 +216,7 @@ struct Options {
     int64_t rows = 60175;           // SF0.01 lineitem, /root/reference/tests/tpchnoorder/bounds.csv:59
     uint64_t seed = 0x5EED0006ULL;
     int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0, lookup_images = 0;
+    int wide = -1;                  // --wide-sums 1 / --checked-sums 2; -1: as the plan was parsed (VDL_WIDE_SUMS)
     std::string data_dir, shard = "lineitem";
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
@@ -266,6 +286,7 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
         vdl_plan_set_profiling(one, o.profile);
         if (o.jit) vdl_plan_set_jit(one, o.jit);
         if (o.jit_share) vdl_plan_set_jit_bounds(one, 1);
+        if (o.wide >= 0 && (rc = vdl_plan_set_wide_sums(one, o.wide))) return die(ctx, "vdl_plan_set_wide_sums", rc);
         if (!o.order_fields.empty() || o.limit > 0) {
             std::vector<const char *> fields;
             for (const std::string &f : o.order_fields) fields.push_back(f.c_str());
@@ -364,6 +385,8 @@ int main(int argc, char **argv) {
         else if (a == "--batch" && i + 1 < argc) o.batch_files.push_back(argv[++i]);
         else if (a == "--batch-grouped") o.batch_grouped = 1;
         else if (a == "--lookup-images") o.lookup_images = 1;
+        else if (a == "--wide-sums") o.wide = 1;
+        else if (a == "--checked-sums") o.wide = 2;
         else if (a == "--order-by" && i + 1 < argc && parse_order_by(argv[i + 1], o)) i++;
         else if (a == "--order-sharded") o.order_sharded = 1;
         else if (a == "--limit" && i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]) &&
@@ -377,7 +400,7 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--lookup-images] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--lookup-images] [--wide-sums | --checked-sums] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }

@@ -137,6 +137,37 @@ class Plan:
         to the plan until its next run."""
         self._e._check(self._e._L.vdl_plan_set_device_outputs(self._h, int(bool(enabled))))
 
+    def set_wide_sums(self, mode):
+        """Exact 128-bit SUM results (vdl.h: vdl_plan_set_wide_sums).  0: off -- sums wrap around in int64 and results have the
+        types they always had.  1: wide -- `run()` / `collect()` return every output as a list of exact Python ints of any size
+        (as_numpy=True: an object-dtype array of them); `collect_words()` hands out the (lo, hi) int64 pairs instead.  2: checked
+        -- as 1, and a run in which a value does not fit int64 raises VdlError with code VDL_ERR_OVERFLOW naming output, group and
+        value.  Only plans that fuse as a whole are served; every other route raises VDL_ERR_UNSUPPORTED with its reason."""
+        self._e._check(self._e._L.vdl_plan_set_wide_sums(self._h, int(mode)))
+
+    @property
+    def wide_sums(self):
+        return int(self._e._L.vdl_plan_wide_sums(self._h))
+
+    def wide_note(self):
+        """What served the plan's scans in the last wide run ("wide: k_mscan<...> grouped, 7 sums"), or "refused: <reason>"."""
+        return (self._e._L.vdl_plan_wide_note(self._h) or b"").decode()
+
+    def collect_words(self):
+        """{tmpN: (lo, hi)} of the last run as int64 arrays: what vdl_output and vdl_output_high hand out; hi is None after a
+        run with wide sums off."""
+        L, out = self._e._L, {}
+        for k in range(L.vdl_n_outputs(self._h)):
+            tmp = ctypes.c_char_p()
+            vals, high, n = ctypes.POINTER(ctypes.c_int64)(), ctypes.POINTER(ctypes.c_int64)(), ctypes.c_size_t()
+            L.vdl_output(self._h, k, None, ctypes.byref(tmp), ctypes.byref(vals), ctypes.byref(n))
+            L.vdl_output_high(self._h, k, ctypes.byref(high), None)
+            grab = lambda p: np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value and p else np.zeros(0, np.int64)      # noqa: E731
+            # (an output of no values has no high vector to point at: it is the empty one while the switch is on)
+            has_high = bool(high) or (n.value == 0 and self.wide_sums != 0)
+            out[tmp.value.decode()] = (grab(vals), grab(high) if has_high else None)
+        return out
+
     def set_order(self, keys, limit=0, sharded=False):
         """ORDER BY / LIMIT on the device: `keys` is a list of (field, descending) pairs (a bare string = ascending), a field
         being an output's full name or its "tmpN" key; `limit` 0 = all rows.  Every output of `run()` then comes back permuted
@@ -181,7 +212,16 @@ class Plan:
             name, tmp = ctypes.c_char_p(), ctypes.c_char_p()
             vals, n = ctypes.POINTER(ctypes.c_int64)(), ctypes.c_size_t()
             L.vdl_output(self._h, k, ctypes.byref(name), ctypes.byref(tmp), ctypes.byref(vals), ctypes.byref(n))
-            if n.value and not vals:
+            high = ctypes.POINTER(ctypes.c_int64)()
+            L.vdl_output_high(self._h, k, ctypes.byref(high), None)
+            if high and vals and n.value:
+                # wide sums: the exact values as Python ints, (hi << 64) | lo with lo taken unsigned; as_numpy: an object array of them
+                lo = np.ctypeslib.as_array(vals, shape=(n.value,)).tolist()
+                hi = np.ctypeslib.as_array(high, shape=(n.value,)).tolist()
+                arr = [(h << 64) | (x & 0xFFFFFFFFFFFFFFFF) for x, h in zip(lo, hi)]
+                if as_numpy:
+                    arr = np.array(arr, dtype=object)
+            elif n.value and not vals:
                 dev = ctypes.POINTER(ctypes.c_int64)()
                 L.vdl_output_device(self._h, k, ctypes.byref(dev), ctypes.byref(n))
                 arr = DeviceValues(ctypes.cast(dev, ctypes.c_void_p).value, n.value, self)
