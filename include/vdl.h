@@ -308,7 +308,8 @@ int  vdl_output_device(const vdl_plan *plan, int k, const int64_t **dev_vals, si
  * VDL_ERR_UNSUPPORTED before any kernel runs, the message naming the route: a plan that does not fuse as a whole or whose
  * fusion is off (its sums would run through the GROUP BY tail or the per-operator folds); a fused plan whose rows carry group
  * keys outside the pivots (it would be rerun statement by statement); every sharded entry point (vdl_run_local, vdl_finalize*,
- * vdl_resolve_first, vdl_exchange_begin, vdl_run_sharded*).  vdl_run_batch runs such a plan alone inside the call ("alone: wide
+ * vdl_resolve_first, vdl_exchange_begin, vdl_run_sharded*) unless vdl_plan_set_wide_sums_sharded (below, with the sharded entry
+ * points) has switched the merge of (lo, hi) pairs on.  vdl_run_batch runs such a plan alone inside the call ("alone: wide
  * sums are not batched").  With an order set the high vectors are permuted and cut with the low ones; keys are compared as the
  * int64 they are, and a key output whose value does not fit int64 fails the run with VDL_ERR_OVERFLOW naming it, in either mode.
  * vdl_plan_set_wide_sums: mode outside 0..2 is VDL_ERR_ARG.  vdl_output_high: *hi is NULL before a run and after a mode-0 run,
@@ -589,6 +590,33 @@ int  vdl_order_merge_host(int world, int n_keys, const int64_t *counts, const ui
  * rank (-1: every local phase succeeded).  For hosts / tests that want to check a transport without a GPU. */
 int  vdl_comm_merge_host(int world, int64_t n_words, const int32_t *ops, const int64_t *gathered, int64_t stride_words, int64_t *out,
                          int64_t *status_out);
+/* ---- wide sums in a sharded run ----
+ * vdl_plan_set_wide_sums_sharded(plan, on): with on != 0 and vdl_plan_set_wide_sums at 1 or 2, vdl_run_sharded, vdl_run_sharded_begin and
+ * vdl_run_sharded_end accept a plan that fuses as a whole (vdl_plan_is_fused, no semi-join set) on the fold route, and EVERY rank ends
+ * with what vdl_run over the whole table delivers under the same mode: the low words in vdl_output, the high words in vdl_output_high,
+ * scalar outputs (avg) evaluated over the exact merged values.  on = 0 (the default; VDL_WIDE_SHARDED=1 in the environment sets it at
+ * vdl_parse; vdl_plan_set_wide_sums(plan, 0) clears it) keeps the refusal of every sharded entry point.
+ *   - A rank's block of the ONE all-gather is [n_words raw][n_words resolved][status][n_words high words of the raw words]: 3 * n_words + 1
+ *     int64, the first 2 * n_words + 1 as without the switch.  The merge adds a SUM word's (lo, hi) pairs with carry in rank order
+ *     (deterministic); MIN, MAX and FIRST words are merged as ever and carry the sign extension; a failed rank sends zeros.
+ *   - Mode 2 is checked on the MERGED values, in vdl_run_sharded_end: a rank whose own partial sum leaves int64 while the total fits is no
+ *     failure; a total that does not fit fails on every rank with VDL_ERR_OVERFLOW and vdl_run's message (field, group, decimal value).
+ *   - With vdl_plan_set_order_sharded also on, the order step runs after the merge as it does without the switch and permutes the high
+ *     vectors with the low ones.
+ *   - vdl_plan_wide_note names the scans and ends in "; merged over N ranks".
+ *   - Still refused, VDL_ERR_UNSUPPORTED naming the route, before a kernel or a collective runs and from the plan alone (every rank
+ *     decides the same): a fused plan with a semi-join set (the set route); a plan that does not fuse as a whole or whose fusion is off
+ *     -- sharded through its global folds (k_fold_global) or on the exchange, front, chain or replicate route (k_group_fold /
+ *     k_seg_fold); and the entry points that leave the collectives to their caller -- vdl_run_local, vdl_finalize*, vdl_resolve_first,
+ *     vdl_exchange_begin -- except inside vdl_run_sharded's own calls.  A fused plan whose rows carry group keys outside the pivots
+ *     fails as it does unsharded.
+ * vdl_comm_merge_host_wide: the merge rule of such blocks on the host (what the device kernel computes); stride_words >= 3 * n_words + 1
+ * (0 = exactly that), rank r's high word of word i at gathered[r * stride_words + 2 * n_words + 1 + i]; out_lo is what vdl_comm_merge_host
+ * gives for the blocks' first 2 * n_words + 1 words; status_out as there. */
+int  vdl_plan_set_wide_sums_sharded(vdl_plan *plan, int on);
+int  vdl_plan_wide_sums_sharded(const vdl_plan *plan);
+int  vdl_comm_merge_host_wide(int world, int64_t n_words, const int32_t *ops, const int64_t *gathered, int64_t stride_words, int64_t *out_lo,
+                              int64_t *out_hi, int64_t *status_out);
 
 #ifdef __cplusplus
 }

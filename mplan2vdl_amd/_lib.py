@@ -92,6 +92,8 @@ def load():
         "vdl_output_device": (i32, [vp, i32, P(P(i64)), P(ctypes.c_size_t)]),
         "vdl_plan_set_wide_sums": (i32, [vp, i32]),
         "vdl_plan_wide_sums": (i32, [vp]),
+        "vdl_plan_set_wide_sums_sharded": (i32, [vp, i32]),
+        "vdl_plan_wide_sums_sharded": (i32, [vp]),
         "vdl_output_high": (i32, [vp, i32, P(P(i64)), P(ctypes.c_size_t)]),
         "vdl_plan_wide_note": (cp, [vp]),
         "vdl_wide_eval_bin": (i32, [i32, i64, i64, i64, i64, P(i64), P(i64)]),
@@ -133,6 +135,7 @@ def load():
         "vdl_run_sharded_begin": (i32, [vp, vp, i32]),
         "vdl_run_sharded_end": (i32, [vp, vp, i32]),
         "vdl_comm_merge_host": (i32, [i32, i64, P(ctypes.c_int32), P(i64), i64, P(i64), P(i64)]),
+        "vdl_comm_merge_host_wide": (i32, [i32, i64, P(ctypes.c_int32), P(i64), i64, P(i64), P(i64), P(i64)]),
     })
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here = the library does not export the ABI
@@ -156,6 +159,7 @@ ABI_SYMBOLS = [
     "vdl_exchange_finish", "vdl_comm_unique_id", "vdl_comm_init", "vdl_comm_init_host", "vdl_comm_info", "vdl_comm_free", "vdl_run_sharded",
     "vdl_run_sharded_begin", "vdl_run_sharded_end", "vdl_comm_merge_host",
     "vdl_plan_set_wide_sums", "vdl_plan_wide_sums", "vdl_output_high", "vdl_plan_wide_note", "vdl_wide_eval_bin",
+    "vdl_plan_set_wide_sums_sharded", "vdl_plan_wide_sums_sharded", "vdl_comm_merge_host_wide",
 ]
 
 

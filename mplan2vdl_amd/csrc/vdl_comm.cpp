@@ -111,11 +111,15 @@ struct CommState {
 // STATUS of its local phase (VDL_OK or the error code).  A rank whose local phase failed still takes part in the collective
 // (zeroed words, its status) -- otherwise its peers would wait in ncclAllGather / the host transport for ever -- and every
 // rank reports the failure: the failing rank at once with its own message, the others when they collect the answer.
+// A wide run (vdl_plan_set_wide_sums_sharded) puts the n_words HIGH words of the raw words behind the status word: 3 * n_words + 1 int64
+// per rank, the prefix as it was, still one all-gather; a failed rank zeroes them with the rest.
 struct ShardState {
     int64_t n_words = 0;
     bool any_first = false;
+    bool wide = false;           // the buffers are sized for the wide block
     BufP ops;                    // int32 per word on the device
     BufP send[2], recv[2], merged[2], status[2];
+    BufP merged_hi[2];           // wide: the high words of merged[]
     int64_t *status_host = nullptr;       // pinned: 2 slots x {status, rank}
     ~ShardState() { if (status_host) (void)hipHostFree(status_host); }
 };
@@ -216,17 +220,21 @@ static ShardState &shard_state(vdl_ctx *c, vdl_plan *p, const CommState &m) {
     if (!p->shard) p->shard = std::make_shared<ShardState>();
     ShardState &st = *p->shard;
     const size_t words = (size_t)std::max<int64_t>(nw, 1);
-    if (st.n_words != nw || !st.ops || !st.recv[0] || st.recv[0]->cls < sizeof(int64_t) * (2 * words + 1) * (size_t)m.world) {
+    const bool wide = p->wide != 0;
+    const size_t block = (wide ? 3 : 2) * words + 1;           // int64 per rank
+    if (st.n_words != nw || st.wide != wide || !st.ops || !st.recv[0] || st.recv[0]->cls < sizeof(int64_t) * block * (size_t)m.world) {
         st.n_words = nw;
+        st.wide = wide;
         st.any_first = false;
         for (int64_t i = 0; i < nw; i++) st.any_first |= ops[i] == VDL_REDUCE_FIRST;
         st.ops = dev_alloc(c, sizeof(int32_t) * words);
         if (nw) HIP_CHECK(hipMemcpyAsync(st.ops->p, ops, sizeof(int32_t) * (size_t)nw, hipMemcpyHostToDevice, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));                    // `ops` belongs to the plan and may be rewritten by the next spec call
         for (int k = 0; k < 2; k++) {
-            st.send[k] = dev_alloc(c, sizeof(int64_t) * (2 * words + 1));
-            st.recv[k] = dev_alloc(c, sizeof(int64_t) * (2 * words + 1) * (size_t)m.world);
+            st.send[k] = dev_alloc(c, sizeof(int64_t) * block);
+            st.recv[k] = dev_alloc(c, sizeof(int64_t) * block * (size_t)m.world);
             st.merged[k] = dev_alloc(c, sizeof(int64_t) * words);
+            st.merged_hi[k] = wide ? dev_alloc(c, sizeof(int64_t) * words) : nullptr;
             st.status[k] = dev_alloc(c, sizeof(int64_t) * 2);
         }
         if (!st.status_host) HIP_CHECK(hipHostMalloc((void **)&st.status_host, sizeof(int64_t) * 4, hipHostMallocDefault));
@@ -239,12 +247,22 @@ static void sharded_begin(vdl_ctx *c, vdl_plan *p, int slot) {
     need_device(c);
     // (an order switched on for sharded runs: vdl_run_local lets the plan through, and a plan sharded through its global folds orders
     // its outputs where it writes them, general_finalize; a fused plan's merged answer is ordered in vdl_run_sharded_end)
-    struct Inside { vdl_plan *p; Inside(vdl_plan *q) : p(q) { p->order_inside = true; } ~Inside() { p->order_inside = false; } } inside(p);
+    // (wide sums switched on for sharded runs: likewise, and the plan is told where this slot's high words go and come from)
+    struct Inside {
+        vdl_plan *p;
+        Inside(vdl_plan *q) : p(q) { p->order_inside = true; p->wide_inside = true; }
+        ~Inside() { p->order_inside = false; p->wide_inside = false; p->wide_hi_out = nullptr; p->wide_hi_src = nullptr; }
+    } inside(p);
     if (slot < 0 || slot > 1) throw Error(VDL_ERR_ARG, "slot must be 0 or 1");
     CommState &m = comm_of(c);
     ShardState &st = shard_state(c, p, m);
     const int64_t nw = st.n_words;
+    const bool wide = st.wide;
     int64_t *send = (int64_t *)st.send[slot]->p;
+    // The high words of the local phase are written by the scans' finish steps straight into the send buffer, behind the status word:
+    // on the engine's stream, ahead of ev_local, into a buffer that belongs to this slot and that the previous query of the slot has
+    // left (ev_merged) -- the plan's own wide_hi would be overwritten by the next query's local phase while this gather is queued.
+    if (wide) p->wide_hi_out = send + 2 * nw + 1;
     const bool overlap = m.kind == CommState::RCCL;
     hipStream_t cs = overlap ? m.stream : c->stream;
     if (overlap && m.ev_merged[slot]) HIP_CHECK(hipStreamWaitEvent(c->stream, m.ev_merged[slot], 0));    // the previous query of this slot has left the send buffer
@@ -266,18 +284,23 @@ static void sharded_begin(vdl_ctx *c, vdl_plan *p, int slot) {
         if (nw) HIP_CHECK(hipMemcpyAsync(send + nw, send, sizeof(int64_t) * (size_t)nw, hipMemcpyDeviceToDevice, cs));
         if (st.any_first && vdl_resolve_first(c, p, send + nw) != VDL_OK) { local_rc = VDL_ERR_DEVICE; local_error = c->err; }
     }
-    if (local_rc != VDL_OK && nw) HIP_CHECK(hipMemsetAsync(send, 0, sizeof(int64_t) * 2 * (size_t)nw, cs));
+    const int64_t stride = (wide ? 3 : 2) * nw + 1;
+    if (local_rc != VDL_OK && nw) HIP_CHECK(hipMemsetAsync(send, 0, sizeof(int64_t) * (size_t)stride, cs));      // (the high words too; the status follows)
     int64_t *slot_status = st.status_host + 2 * slot;
     slot_status[0] = local_rc;                 // (pinned: read by the copy below when the stream gets there; this slot's previous
     slot_status[1] = m.rank;                   //  query has been collected -- _end -- before the slot is begun again)
     HIP_CHECK(hipMemcpyAsync(send + 2 * nw, slot_status, sizeof(int64_t), hipMemcpyHostToDevice, cs));
     int64_t *merged = (int64_t *)st.merged[slot]->p;
-    const int64_t stride = 2 * nw + 1;
+    const int64_t *gathered = send;                            // (one rank: no gather, the merge reads the send buffer)
     if (m.world > 1) {
         all_gather(c, send, st.recv[slot]->p, sizeof(int64_t) * (size_t)stride, cs);
-        HIP_CHECK(launch_merge_words((const int64_t *)st.recv[slot]->p, m.world, nw, stride, (const int32_t *)st.ops->p, merged, (int64_t *)st.status[slot]->p, cs));
+        gathered = (const int64_t *)st.recv[slot]->p;
+    }
+    if (wide) {
+        HIP_CHECK(launch_merge_words_wide(gathered, m.world, nw, stride, (const int32_t *)st.ops->p, merged, (int64_t *)st.merged_hi[slot]->p, (int64_t *)st.status[slot]->p, cs));
+        p->wide_hi_src = (const int64_t *)st.merged_hi[slot]->p;       // what finalize_begin copies into the slot's pinned high words
     } else {
-        HIP_CHECK(launch_merge_words(send, 1, nw, stride, (const int32_t *)st.ops->p, merged, (int64_t *)st.status[slot]->p, cs));
+        HIP_CHECK(launch_merge_words(gathered, m.world, nw, stride, (const int32_t *)st.ops->p, merged, (int64_t *)st.status[slot]->p, cs));
     }
     if (overlap) HIP_CHECK(hipEventRecord(m.ev_merged[slot], cs));
     if (local_rc != VDL_OK) {
@@ -287,6 +310,7 @@ static void sharded_begin(vdl_ctx *c, vdl_plan *p, int slot) {
     }
     HIP_CHECK(hipMemcpyAsync(slot_status, st.status[slot]->p, sizeof(int64_t) * 2, hipMemcpyDeviceToHost, cs));   // ahead of the words: same event
     if (vdl_finalize_begin(c, p, merged, slot) != VDL_OK) throw Error(VDL_ERR_DEVICE, c->err);
+    if (wide) wide_note_merged(p, m.world);
     if (!(p->use_fusion && p->fused.ok)) HIP_CHECK(hipStreamSynchronize(cs));     // (fold records: finalised at once, no slot event for _end to wait on)
 }
 
@@ -859,6 +883,39 @@ static bool fold_route(vdl_ctx *c, vdl_plan *p) {
     return ok;
 }
 
+// vdl_run_sharded* and a plan with wide sums on.  Switch off: refuse_wide_sharded's refusal, as ever.  Switch on (vdl_plan_set_wide_sums_sharded): served where
+// the ranks' sums are partial words of fused aggregate scans -- a plan that fuses as a whole, without a semi-join set, on the fold route.
+// Every other route is refused by name, from the plan alone (so every rank decides the same), before a kernel or a collective runs.
+static void wide_sharded_gate(vdl_ctx *c, vdl_plan *p, const char *entry) {
+    if (!p->wide) return;
+    if (!p->wide_sharded) refuse_wide_sharded(p, entry);       // (throws)
+    std::string why;
+    const std::string head = std::string(entry) + ": wide sums are on for this plan and switched on for sharded runs (vdl_plan_set_wide_sums_sharded), but ";
+    if (p->use_fusion && p->fused.ok) {
+        bool semi = false;
+        for (const PreludeItem &it : p->fused.prelude) semi |= it.kind == PreludeItem::SEMI_BITMAP;
+        if (semi) why = head + "this fused plan builds a semi-join set and would take the set route, where the ranks' sets are merged and the wide partial words are not; "
+                               "run it on one GPU with vdl_run, or clear the switch";
+    } else {
+        const std::string keep = c->err;
+        const char *route = nullptr;
+        int whole = 0;
+        const bool known = vdl_plan_sharded_route(c, p, &route, &whole) == VDL_OK && route;
+        c->err = keep;
+        const std::string fusion = !p->use_fusion ? "its fusion is off (vdl_plan_set_fusion)" : "it does not fuse as a whole into aggregate scans (" + p->fused.why_not + ")";
+        if (known && std::strcmp(route, "fold") == 0)
+            why = head + fusion + ": it would be sharded through its global folds on the fold route (general_run_local), whose sums run through k_fold_global, which has no "
+                                  "wide form; switch fusion on where the plan fuses as a whole, or clear the switch";
+        else
+            why = head + fusion + ": it would take the " + (known ? std::string(route) + " route" : std::string("exchange, front, chain or replicate route")) +
+                  ", whose sums run through k_group_fold / k_seg_fold (and k_fold_global), which have no wide form; run it on one GPU with the switch cleared, or clear the switch";
+    }
+    if (why.empty()) return;
+    p->wide_note = "refused: " + why;
+    p->outs.clear();
+    throw Error(VDL_ERR_UNSUPPORTED, why);
+}
+
 }  // namespace eng
 }  // namespace vdl
 
@@ -966,7 +1023,7 @@ int vdl_run_sharded_begin(vdl_ctx *c, vdl_plan *p, int slot) {
     if (!c || !p) return VDL_ERR_ARG;
     return guard(c, [&] {
         refuse_order_sharded(p, true);
-        refuse_wide_sharded(p, "vdl_run_sharded_begin");
+        wide_sharded_gate(c, p, "vdl_run_sharded_begin");
         p->order_note.clear();
         if (!fold_route(c, p)) throw Error(VDL_ERR_UNSUPPORTED, "vdl_run_sharded_begin serves plans whose outputs are folds (partial words); plans with a "
                                                                "Partition exchange rows and run through vdl_run_sharded");
@@ -976,9 +1033,15 @@ int vdl_run_sharded_begin(vdl_ctx *c, vdl_plan *p, int slot) {
 
 int vdl_run_sharded_end(vdl_ctx *c, vdl_plan *p, int slot) {
     if (!c || !p) return VDL_ERR_ARG;
+    // (wide sums switched on for sharded runs: the finalisation is this entry point's own call; with the switch off it refuses as before)
+    p->wide_inside = p->wide && p->wide_sharded;
     const int rc = vdl_finalize_end(c, p, slot);
+    p->wide_inside = false;
     const int rs = guard(c, [&] { sharded_check_status(p, slot); });      // (a failed peer outranks whatever the merged zeros gave)
     if (rs != VDL_OK || rc != VDL_OK) return rs != VDL_OK ? rs : rc;
+    // checked sums: on the MERGED values -- a rank whose own partial left int64 is no failure, a total that does not fit fails on every rank
+    if (p->wide == 2 && p->wide_sharded && p->use_fusion && p->fused.ok)
+        if (const int rw = guard(c, [&] { wide_check_outputs(p); })) return rw;
     // an order switched on for sharded runs: every rank has assembled the whole answer on the host and orders it as vdl_run does
     // (a plan sharded through its global folds ordered its outputs when it wrote them: general_finalize)
     if (p->order.set && p->order.sharded && p->use_fusion && p->fused.ok) return guard(c, [&] { order_outputs_on_host(c, p); });
@@ -987,7 +1050,7 @@ int vdl_run_sharded_end(vdl_ctx *c, vdl_plan *p, int slot) {
 
 int vdl_run_sharded(vdl_ctx *c, vdl_plan *p) {
     if (!c || !p) return VDL_ERR_ARG;
-    if (const int rc = guard(c, [&] { refuse_order_sharded(p, true); refuse_wide_sharded(p, "vdl_run_sharded"); })) return rc;
+    if (const int rc = guard(c, [&] { refuse_order_sharded(p, true); wide_sharded_gate(c, p, "vdl_run_sharded"); })) return rc;
     p->order_note.clear();
     if (p->use_fusion && p->fused.ok) {                       // a fused plan with a semi-join set: the sets are merged across the ranks
         bool semi = false;
@@ -1038,6 +1101,24 @@ int vdl_comm_merge_host(int world, int64_t n_words, const int32_t *ops, const in
     if (status_out && (stride_words < 2 * n_words + 1 || !gathered)) return VDL_ERR_ARG;
     for (int64_t i = 0; i < n_words; i++) out[i] = merge_word(gathered, world, n_words, ops[i], i, stride_words);
     if (status_out) {                                           // as k_merge_words: the first rank whose local phase failed
+        status_out[0] = 0; status_out[1] = -1;
+        for (int r = world - 1; r >= 0; r--) {
+            const int64_t x = gathered[(int64_t)r * stride_words + 2 * n_words];
+            if (x != 0) { status_out[0] = x; status_out[1] = r; }
+        }
+    }
+    return VDL_OK;
+}
+
+/* ... and of a wide run's blocks (merge_word_wide: what k_merge_words_wide applies): the high words stand behind the status word */
+int vdl_comm_merge_host_wide(int world, int64_t n_words, const int32_t *ops, const int64_t *gathered, int64_t stride_words, int64_t *out_lo, int64_t *out_hi,
+                             int64_t *status_out) {
+    if (world < 1 || n_words < 0) return VDL_ERR_ARG;
+    if (stride_words == 0) stride_words = 3 * n_words + 1;
+    if (stride_words < 3 * n_words + 1 || (n_words && (!ops || !gathered || !out_lo || !out_hi))) return VDL_ERR_ARG;
+    if (status_out && !gathered) return VDL_ERR_ARG;
+    for (int64_t i = 0; i < n_words; i++) out_lo[i] = merge_word_wide(gathered, world, n_words, ops[i], i, stride_words, &out_hi[i]);
+    if (status_out) {
         status_out[0] = 0; status_out[1] = -1;
         for (int r = world - 1; r >= 0; r--) {
             const int64_t x = gathered[(int64_t)r * stride_words + 2 * n_words];

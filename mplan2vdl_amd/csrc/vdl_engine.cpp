@@ -671,7 +671,9 @@ void run_fused_local(vdl_ctx *c, vdl_plan *p, int64_t *dev_words, bool single_ra
     int64_t *hi_words = nullptr;
     if (p->wide) {
         if (!p->wide_hi || p->wide_hi_cap < p->n_words) { p->wide_hi = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(p->n_words, 1)); p->wide_hi_cap = p->n_words; }
-        hi_words = (int64_t *)p->wide_hi->p;
+        // (a sharded run: straight into its slot's send buffer -- wide_hi is one buffer per plan, and the next query's local phase runs
+        // while this query's gather is still queued; the tuner's candidates keep using wide_hi)
+        hi_words = p->wide_hi_out ? p->wide_hi_out : (int64_t *)p->wide_hi->p;
     }
     run_prelude(c, p);
     if (p->use_jit && p->jit_tune && !p->jit_tuned) {
@@ -734,10 +736,21 @@ void finalize_begin(vdl_ctx *c, vdl_plan *p, const int64_t *dev_words, int slot)
     }
     if (!p->slot_ev[slot]) HIP_CHECK(hipEventCreateWithFlags(&p->slot_ev[slot], hipEventDisableTiming));
     if (p->n_words) HIP_CHECK(hipMemcpyAsync(p->host_words[slot], dev_words, sizeof(int64_t) * (size_t)p->n_words, hipMemcpyDeviceToHost, c->stream));
-    p->wide_host_hi.clear();
-    if (p->wide && p->wide_hi && p->n_words) {                 // (a wide run is never pipelined: vdl_run alone serves it)
-        p->wide_host_hi.resize((size_t)p->n_words);
-        HIP_CHECK(hipMemcpyAsync(p->wide_host_hi.data(), p->wide_hi->p, sizeof(int64_t) * (size_t)p->n_words, hipMemcpyDeviceToHost, c->stream));
+    // wide sums: the high words travel beside the low ones into a pinned buffer of the slot's own -- a sharded wide run is pipelined
+    // like any other, and hands over its MERGED high words (wide_hi_src); vdl_run's are where its scans left them
+    const int64_t *hi_src = p->wide_hi_src ? p->wide_hi_src : p->wide_hi ? (const int64_t *)p->wide_hi->p : nullptr;
+    p->slot_wide[slot] = p->wide && hi_src && p->n_words;
+    if (p->slot_wide[slot]) {
+        if (p->host_hi_cap < p->n_words) {
+            for (int k = 0; k < 2; k++) {
+                if (p->host_hi[k]) HIP_CHECK(hipHostFree(p->host_hi[k]));
+                p->host_hi[k] = nullptr;
+            }
+            p->host_hi_cap = 0;
+            for (int k = 0; k < 2; k++) HIP_CHECK(hipHostMalloc((void **)&p->host_hi[k], sizeof(int64_t) * (size_t)p->n_words, hipHostMallocDefault));
+            p->host_hi_cap = p->n_words;
+        }
+        HIP_CHECK(hipMemcpyAsync(p->host_hi[slot], hi_src, sizeof(int64_t) * (size_t)p->n_words, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_CHECK(hipEventRecord(p->slot_ev[slot], c->stream));
     p->slot_pending[slot] = true;
@@ -776,8 +789,9 @@ void finalize_end(vdl_ctx *c, vdl_plan *p, int slot) {
     p->outs.clear();
     // wide sums: every output from the exact 128-bit aggregate values (the low words are `w`, the high words came beside them); the
     // high word of a MIN, MAX or FIRST aggregate is its sign extension (a FIRST word became a column value after the finish step)
-    const bool wide = p->wide && !p->wide_host_hi.empty() && (int64_t)p->wide_host_hi.size() == p->n_words;
+    const bool wide = p->wide && p->slot_wide[slot] && p->host_hi[slot] && p->host_hi_cap >= p->n_words;
     if (p->wide && !wide && p->n_words) throw Error(VDL_ERR_ARG, "internal: a wide-sums run without its high words");
+    const std::vector<int64_t> wh(wide ? p->host_hi[slot] : nullptr, wide ? p->host_hi[slot] + p->n_words : nullptr);      // this slot's, as `w`
     auto wide_values = [&](const int64_t *lo, const int64_t *hi, const MScanDesc &a, std::vector<wide_t> &v) {
         v.resize((size_t)a.nagg + 1);
         v[0] = (wide_t)lo[0];
@@ -799,11 +813,11 @@ void finalize_end(vdl_ctx *c, vdl_plan *p, int slot) {
         o.has_hi = wide;
         if (wide && fo.gscan < 0) {
             const int64_t *sw = w.data() + p->word_offset[(size_t)fo.scan];
-            if (sw[0] > 0) { wide_values(sw, p->wide_host_hi.data() + p->word_offset[(size_t)fo.scan], p->mdesc[(size_t)fo.scan], wv); push_wide(o, eval_scalar_wide(*fo.value, wv.data() + 1)); }
+            if (sw[0] > 0) { wide_values(sw, wh.data() + p->word_offset[(size_t)fo.scan], p->mdesc[(size_t)fo.scan], wv); push_wide(o, eval_scalar_wide(*fo.value, wv.data() + 1)); }
         } else if (wide) {
             const MScanDesc &a = p->mdesc[ns + (size_t)fo.gscan];
             const int W = a.nagg + 1;
-            const int64_t *tab = w.data() + p->gword_offset[(size_t)fo.gscan], *tabh = p->wide_host_hi.data() + p->gword_offset[(size_t)fo.gscan];
+            const int64_t *tab = w.data() + p->gword_offset[(size_t)fo.gscan], *tabh = wh.data() + p->gword_offset[(size_t)fo.gscan];
             for (int64_t b = 0; b < a.pcount; b++)
                 if (tab[b * W] > 0) { wide_values(tab + b * W, tabh + b * W, a, wv); push_wide(o, eval_scalar_wide(*fo.value, wv.data() + 1)); }
         } else
@@ -1629,6 +1643,7 @@ int vdl_parse(vdl_ctx *c, const char *text, size_t len, vdl_plan **out) {
         { const char *j = getenv("VDL_JIT"); p->use_jit = j && *j && *j != '0'; p->jit_tune = p->use_jit && atoi(j) >= 2; }
         { const char *b = getenv("VDL_JIT_BOUNDS"); p->jit_rt_bounds = b && strcmp(b, "runtime") == 0; }
         { const char *w = getenv("VDL_WIDE_SUMS"); p->wide = w && (strcmp(w, "1") == 0 || strcmp(w, "2") == 0) ? atoi(w) : 0; }
+        { const char *w = getenv("VDL_WIDE_SHARDED"); p->wide_sharded = w && strcmp(w, "1") == 0; }
         p->description = describe_plan(p.get());
         *out = p.release();
     });
@@ -1844,9 +1859,16 @@ int vdl_plan_set_wide_sums(vdl_plan *p, int mode) {
         p->wide_note.clear();
     }
     p->wide = mode;
+    if (mode == 0) p->wide_sharded = false;                    // (the sharded switch says how a WIDE plan is sharded: it goes with the mode)
     return VDL_OK;
 }
 int vdl_plan_wide_sums(const vdl_plan *p) { return p ? p->wide : 0; }
+int vdl_plan_set_wide_sums_sharded(vdl_plan *p, int on) {
+    if (!p) return VDL_ERR_ARG;
+    p->wide_sharded = on != 0;
+    return VDL_OK;
+}
+int vdl_plan_wide_sums_sharded(const vdl_plan *p) { return p && p->wide_sharded ? 1 : 0; }
 int vdl_output_high(const vdl_plan *p, int k, const int64_t **hi, size_t *n) {
     if (!p || k < 0 || k >= (int)p->outs.size()) return VDL_ERR_ARG;
     const Output &o = p->outs[(size_t)k];
@@ -1901,6 +1923,7 @@ static int run_plan(vdl_ctx *c, vdl_plan *p, const std::string *abandoned) {
             p->outs.clear();
             const std::string why = wide_refusal(p);
             if (!why.empty()) { p->wide_note = "refused: " + why; throw Error(VDL_ERR_UNSUPPORTED, why); }
+            wide_note_merged(p, 0);                            // (an unsharded run: a sharded one's "merged over N ranks" goes)
         }
         if (abandoned) p->fallback_note = *abandoned;
         else if (p->use_fusion && p->fused.ok) {

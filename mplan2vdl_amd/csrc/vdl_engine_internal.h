@@ -281,7 +281,18 @@ struct vdl_plan {
     std::string wide_note;
     BufP wide_hi;
     int64_t wide_hi_cap = 0;
-    std::vector<int64_t> wide_host_hi;
+    // vdl_plan_set_wide_sums_sharded: vdl_run_sharded* accept the plan on the fold route and merge the ranks' (lo, hi) pairs with carry.
+    // vdl_run_sharded* set these three around their own calls: wide_inside lets the plan through the entry points that refuse it;
+    // wide_hi_out is where the finish steps of the local phase leave the high words instead of wide_hi (the slot's send buffer: they
+    // are written on the engine's stream ahead of the event the gather waits for, and no buffer is shared between two queries in
+    // flight); wide_hi_src is what finalize_begin copies instead of wide_hi (the slot's MERGED high words)
+    bool wide_sharded = false, wide_inside = false;
+    int64_t *wide_hi_out = nullptr;
+    const int64_t *wide_hi_src = nullptr;
+    // the high words of a finalisation in flight: one pinned buffer per slot beside host_words, slot_wide = the slot's run made them
+    int64_t *host_hi[2] = {nullptr, nullptr};
+    int64_t host_hi_cap = 0;
+    bool slot_wide[2] = {false, false};
     // vdl_plan_set_order: the outputs of vdl_run come back permuted by one order and cut to the limit (vdl_genexec.h "order step")
     struct OrderSpec {
         bool set = false;
@@ -452,6 +463,7 @@ struct vdl_plan {
             if (ev1[k + 2]) (void)hipEventDestroy(ev1[k + 2]);
             if (slot_ev[k]) (void)hipEventDestroy(slot_ev[k]);
             if (host_words[k]) (void)hipHostFree(host_words[k]);
+            if (host_hi[k]) (void)hipHostFree(host_hi[k]);
         }
     }
 };
@@ -545,11 +557,26 @@ inline std::string wide_refusal(const vdl_plan *p) {
                "k_fold_global / k_group_fold / k_seg_fold, which have no wide form; switch fusion on, or clear the switch";
     return "";
 }
-// every sharded entry point refuses a plan with wide sums on: the ranks' partial words are merged with 64-bit adds
+// Sharded entry points and a plan with wide sums on.  Without vdl_plan_set_wide_sums_sharded every one of them refuses it: the ranks'
+// partial words are merged with 64-bit adds.  With it, vdl_run_sharded* decide by the route (vdl_comm.cpp: wide_sharded_refusal) and the
+// fold route of a plan that fuses as a whole merges (lo, hi) pairs; the entry points that leave the collectives to their caller
+// (vdl_run_local, vdl_finalize*, vdl_resolve_first, vdl_exchange_begin) refuse either way -- their callers merge with the plain
+// operators -- except inside vdl_run_sharded's own calls (wide_inside), as refuse_order_sharded does with order_inside.
 inline void refuse_wide_sharded(const vdl_plan *p, const char *entry) {
-    if (p && p->wide)
+    if (!p || !p->wide) return;
+    if (!p->wide_sharded)
         throw Error(VDL_ERR_UNSUPPORTED, std::string(entry) + ": wide sums are on for this plan (vdl_plan_set_wide_sums), and the sharded routes merge the ranks' partial words "
                                          "with 64-bit operators (the merge has no add-with-carry); run it on one GPU with vdl_run, or clear the switch");
+    if (!p->wide_inside)
+        throw Error(VDL_ERR_UNSUPPORTED, std::string(entry) + ": wide sums are on for this plan and switched on for sharded runs (vdl_plan_set_wide_sums_sharded), but this entry "
+                                         "point leaves the collectives to its caller: the merge of the ranks' (lo, hi) pairs with carry lives in vdl_run_sharded; run the "
+                                         "plan through vdl_run_sharded / vdl_run_sharded_begin, or clear the switch");
+}
+// vdl_plan_wide_note of a sharded run ends in "; merged over N ranks" (world > 0); an unsharded run takes that away again (world 0)
+inline void wide_note_merged(vdl_plan *p, int world) {
+    const size_t at = p->wide_note.find("; merged over ");
+    if (at != std::string::npos) p->wide_note.erase(at);
+    if (world > 0 && !p->wide_note.empty()) p->wide_note += "; merged over " + std::to_string(world) + (world == 1 ? " rank" : " ranks");
 }
 void wide_check_outputs(vdl_plan *p);                                             // vdl_engine.cpp: checked sums, VDL_ERR_OVERFLOW on the first value outside int64
 std::string wide_decimal(int64_t lo, int64_t hi);

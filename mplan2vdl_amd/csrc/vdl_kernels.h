@@ -167,6 +167,25 @@ VDL_HD inline int64_t merge_word(const int64_t *g, int world, int64_t n_words, i
     }
     return acc;
 }
+// The wide form (vdl_plan_set_wide_sums_sharded; DESIGN.md section 5.17 "Sharded runs"): a rank's block carries, BEHIND the status word,
+// the high words of its raw words -- hi of word i at 2 * n_words + 1 + i, stride >= 3 * n_words + 1.  A word that merge_word adds is
+// added as a (lo, hi) pair with carry, rank after rank (a fixed order: deterministic); a MIN, MAX or FIRST word is merged as above and
+// its high word is the sign extension of the merged low word.  The value returned is merge_word's in every case.
+VDL_HD inline int64_t merge_word_wide(const int64_t *g, int world, int64_t n_words, int op, int64_t i, int64_t stride, int64_t *hi_out) {
+    if (op == 2 || op == 3 || op == 4) {
+        const int64_t v = merge_word(g, world, n_words, op, i, stride);
+        *hi_out = v >> 63;
+        return v;
+    }
+    uint64_t lo = 0, hi = 0;
+    for (int r = 0; r < world; r++) {
+        const uint64_t xl = (uint64_t)g[(int64_t)r * stride + i], xh = (uint64_t)g[(int64_t)r * stride + 2 * n_words + 1 + i];
+        lo += xl;
+        hi += xh + (lo < xl ? 1u : 0u);
+    }
+    *hi_out = (int64_t)hi;
+    return (int64_t)lo;
+}
 // gathered: `stride` words per rank = n_words raw, n_words resolved, then (stride > 2 * n_words) the rank's status word.
 // status_out (may be null; needs that word): [0] = the first non-zero status over the ranks (0 = every rank's local phase
 // succeeded), [1] = that rank.
@@ -176,6 +195,9 @@ VDL_HD inline int64_t merge_word(const int64_t *g, int world, int64_t n_words, i
 hipError_t launch_or_sets(const uint64_t *gathered, int world, int64_t words, uint64_t *out, hipStream_t s);
 hipError_t launch_merge_words(const int64_t *gathered, int world, int64_t n_words, int64_t stride, const int32_t *ops, int64_t *out,
                               int64_t *status_out, hipStream_t s);
+// the wide merge (vdl_mscan_wide.hip): out / out_hi = merge_word_wide of every word, status_out as launch_merge_words; one lane per word
+hipError_t launch_merge_words_wide(const int64_t *gathered, int world, int64_t n_words, int64_t stride, const int32_t *ops, int64_t *out,
+                                   int64_t *out_hi, int64_t *status_out, hipStream_t s);
 hipError_t launch_fold_words(const int64_t *rec, int reduce, int64_t row0, int64_t *out, hipStream_t s);
 hipError_t launch_fold_record(const int64_t *words, int64_t *rec, hipStream_t s);
 // Gather out of a sparse vector without densifying it: counts[w] = popcount of bitmap word w (the caller turns them into

@@ -50,6 +50,26 @@ __global__ __launch_bounds__(256) void k_mscan_finish_wide(const MScanDesc *__re
     if (lane == 0) { out[i] = x; out_hi[i] = x >> 63; }
 }
 
+// The merge of the ranks' gathered partial words of a sharded wide run (vdl_comm.cpp): one lane per word, merge_word_wide of
+// vdl_kernels.h; the status as k_merge_words leaves it.  A few hundred words: a latency kernel.
+__global__ __launch_bounds__(256) void k_merge_words_wide(const int64_t *__restrict__ g, int world, int64_t n_words, int64_t stride, const int32_t *__restrict__ ops,
+                                                          int64_t *out, int64_t *out_hi, int64_t *status_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_words) {
+        int64_t hi = 0;
+        out[i] = merge_word_wide(g, world, n_words, ops[i], i, stride, &hi);
+        out_hi[i] = hi;
+    }
+    if (i == 0 && status_out) {
+        int64_t st = 0, who = -1;
+        for (int r = world - 1; r >= 0; r--) {
+            const int64_t x = g[(int64_t)r * stride + 2 * n_words];
+            if (x != 0) { st = x; who = r; }
+        }
+        status_out[0] = st; status_out[1] = who;
+    }
+}
+
 typedef void (*mscan_fn)(const MsArgs, const MScanDesc *);
 #define VDL_MS(NC, U, VEC, NT, GR) k_mscan_wide<NC, U, VEC, NT, GR, false>
 #define VDL_MSJ(NC, U, VEC, NT, GR) k_mscan_wide<NC, U, VEC, NT, GR, true>
@@ -72,6 +92,16 @@ hipError_t launch_mscan_finish_wide(const MScanDesc &d, const MScanDesc *dev_des
     if (!out || !out_hi) return hipErrorInvalidValue;
     const int64_t words = grouped ? d.pcount * (d.nagg + 1) + 1 : d.nagg + 1;
     k_mscan_finish_wide<<<(int)((words + 3) / 4), 256, 0, s>>>(dev_desc, nblocks, grouped ? 1 : 0, out, out_hi);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_words_wide(const int64_t *gathered, int world, int64_t n_words, int64_t stride, const int32_t *ops, int64_t *out,
+                                   int64_t *out_hi, int64_t *status_out, hipStream_t s) {
+    (void)hipGetLastError();
+    if (world < 1 || n_words < 0 || stride < 3 * n_words + 1 || !gathered || (n_words && (!ops || !out || !out_hi))) return hipErrorInvalidValue;
+    if (n_words == 0 && !status_out) return hipSuccess;
+    const int64_t lanes = n_words > 0 ? n_words : 1;
+    k_merge_words_wide<<<(int)((lanes + 255) / 256), 256, 0, s>>>(gathered, world, n_words, stride, ops, out, out_hi, status_out);
     return hipGetLastError();
 }
 

@@ -40,8 +40,11 @@
 //   ... | vdlrun --wide-sums ...  |  vdlrun --checked-sums ...                       exact 128-bit SUM results
 // --wide-sums (vdl_plan_set_wide_sums 1): the reply keeps its shape and every value is printed as the exact decimal integer, of any
 // size (JSON has no limit; Python's json reads them as ints and resolve.py passes ints through).  --checked-sums (mode 2): a value
-// outside int64 fails the run, the message naming output, group and value, and vdlrun exits non-zero.  Fused plans only; not with
-// --gpus (every sharded entry point refuses the switch).  VDL_WIDE_SUMS=1|2 in the environment does the same when no option is given.
+// outside int64 fails the run, the message naming output, group and value, and vdlrun exits non-zero.  Fused plans only.
+// VDL_WIDE_SUMS=1|2 in the environment does the same when no option is given.  With --gpus only together with --wide-sharded
+// (vdl_plan_set_wide_sums_sharded; VDL_WIDE_SHARDED=1 does the same): the ranks merge their (lo, hi) partial words with carry, every rank
+// ends with the exact answer of the whole table and ONE reply is printed, in exact decimals; --checked-sums is then checked on the merged
+// values.  Without it --gpus refuses the switch before any rank starts, as every sharded entry point does.
 // --batch-grouped: programs whose one scan is a GROUP BY over table columns share a grouped batch too (vdl_set_batch_grouped); without it
 // they run alone, as "grouped scans are not batched".
 #include <signal.h>
@@ -184,6 +187,8 @@ bool write_reply(const std::string &path, const Reply &r) {
     for (const auto &o : r.outs) {
         f << o.name << "\n" << o.tmp << "\n" << o.vals.size() << "\n";
         f.write((const char *)o.vals.data(), (std::streamsize)(sizeof(int64_t) * o.vals.size()));
+        f << "\n" << o.hi.size() << "\n";                      // (wide sums: the high words travel with their values)
+        f.write((const char *)o.hi.data(), (std::streamsize)(sizeof(int64_t) * o.hi.size()));
         f << "\n";
     }
     f << r.timings.size() << "\n";
@@ -205,6 +210,9 @@ bool read_reply(const std::string &path, Reply &r) {
         o.vals.resize((size_t)num());
         f.read((char *)o.vals.data(), (std::streamsize)(sizeof(int64_t) * o.vals.size()));
         std::getline(f, line);
+        o.hi.resize((size_t)num());
+        f.read((char *)o.hi.data(), (std::streamsize)(sizeof(int64_t) * o.hi.size()));
+        std::getline(f, line);
         r.outs.push_back(std::move(o));
     }
     const long long nt = num();
@@ -217,6 +225,7 @@ struct Options {
     uint64_t seed = 0x5EED0006ULL;
     int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0, lookup_images = 0;
     int wide = -1;                  // --wide-sums 1 / --checked-sums 2; -1: as the plan was parsed (VDL_WIDE_SUMS)
+    int wide_sharded = 0;           // --wide-sharded: vdl_plan_set_wide_sums_sharded
     std::string data_dir, shard = "lineitem";
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
@@ -287,6 +296,7 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
         if (o.jit) vdl_plan_set_jit(one, o.jit);
         if (o.jit_share) vdl_plan_set_jit_bounds(one, 1);
         if (o.wide >= 0 && (rc = vdl_plan_set_wide_sums(one, o.wide))) return die(ctx, "vdl_plan_set_wide_sums", rc);
+        if (o.wide_sharded && (rc = vdl_plan_set_wide_sums_sharded(one, 1))) return die(ctx, "vdl_plan_set_wide_sums_sharded", rc);
         if (!o.order_fields.empty() || o.limit > 0) {
             std::vector<const char *> fields;
             for (const std::string &f : o.order_fields) fields.push_back(f.c_str());
@@ -387,6 +397,7 @@ int main(int argc, char **argv) {
         else if (a == "--lookup-images") o.lookup_images = 1;
         else if (a == "--wide-sums") o.wide = 1;
         else if (a == "--checked-sums") o.wide = 2;
+        else if (a == "--wide-sharded") o.wide_sharded = 1;
         else if (a == "--order-by" && i + 1 < argc && parse_order_by(argv[i + 1], o)) i++;
         else if (a == "--order-sharded") o.order_sharded = 1;
         else if (a == "--limit" && i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]) &&
@@ -400,7 +411,7 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--lookup-images] [--wide-sums | --checked-sums] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--lookup-images] [--wide-sums | --checked-sums] [--wide-sharded] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }
@@ -416,6 +427,18 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "vdlrun: --order-by / --limit are not served with --gpus: the ranks hold disjoint result rows and the merge of per-rank "
                              "top-N results is not built; run the ordered query on one GPU\n");
         return 3;
+    }
+    {
+        // wide sums with --gpus: only with the wide merge switched on -- refused here, before any rank starts, in the words of the entry point
+        const char *we = std::getenv("VDL_WIDE_SUMS"), *se = std::getenv("VDL_WIDE_SHARDED");
+        const bool wide_on = o.wide > 0 || (o.wide < 0 && we && (!std::strcmp(we, "1") || !std::strcmp(we, "2")));
+        const bool merge_on = o.wide_sharded || (se && !std::strcmp(se, "1"));
+        if (sharded && !o.describe && wide_on && !merge_on) {
+            std::fprintf(stderr, "vdlrun: --wide-sums / --checked-sums are not served with --gpus unless --wide-sharded is given: wide sums are on for this plan "
+                                 "(vdl_plan_set_wide_sums), and the sharded routes merge the ranks' partial words with 64-bit operators (the merge has no "
+                                 "add-with-carry); add --wide-sharded, or run it on one GPU\n");
+            return 3;
+        }
     }
     if (sharded && !o.describe && !o.batch_files.empty()) {
         std::fprintf(stderr, "vdlrun: --batch is not served with --gpus: a sharded run takes one plan; run the batch on one GPU\n");
@@ -469,8 +492,10 @@ int main(int argc, char **argv) {
         if (!read_reply(std::string(dir) + "/out." + std::to_string(r), part)) { failed++; break; }
         if (r == 0) { all = part; continue; }
         if (part.replicated) continue;                       // fold plans: every rank printed the same answer
-        for (size_t k = 0; k < all.outs.size() && k < part.outs.size(); k++)
+        for (size_t k = 0; k < all.outs.size() && k < part.outs.size(); k++) {
             all.outs[k].vals.insert(all.outs[k].vals.end(), part.outs[k].vals.begin(), part.outs[k].vals.end());
+            all.outs[k].hi.insert(all.outs[k].hi.end(), part.outs[k].hi.begin(), part.outs[k].hi.end());
+        }
     }
     for (int r = 0; r < o.gpus; r++) std::remove((std::string(dir) + "/out." + std::to_string(r)).c_str());
     std::remove((std::string(dir) + "/id").c_str());

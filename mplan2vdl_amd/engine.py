@@ -137,17 +137,26 @@ class Plan:
         to the plan until its next run."""
         self._e._check(self._e._L.vdl_plan_set_device_outputs(self._h, int(bool(enabled))))
 
-    def set_wide_sums(self, mode):
+    def set_wide_sums(self, mode, sharded=False):
         """Exact 128-bit SUM results (vdl.h: vdl_plan_set_wide_sums).  0: off -- sums wrap around in int64 and results have the
         types they always had.  1: wide -- `run()` / `collect()` return every output as a list of exact Python ints of any size
         (as_numpy=True: an object-dtype array of them); `collect_words()` hands out the (lo, hi) int64 pairs instead.  2: checked
         -- as 1, and a run in which a value does not fit int64 raises VdlError with code VDL_ERR_OVERFLOW naming output, group and
-        value.  Only plans that fuse as a whole are served; every other route raises VDL_ERR_UNSUPPORTED with its reason."""
+        value.  Only plans that fuse as a whole are served; every other route raises VDL_ERR_UNSUPPORTED with its reason.
+        `sharded=True` (with mode 1 or 2) switches the wide merge of sharded runs on (vdl_plan_set_wide_sums_sharded):
+        `run_sharded` and the `run_sharded_begin` / `_end` pair then accept the plan on the fold route, every rank ends with the
+        exact answer of the whole table, and mode 2 is checked on the merged values.  Every call passes it down, so a later plain
+        set_wide_sums(..) switches it off again."""
         self._e._check(self._e._L.vdl_plan_set_wide_sums(self._h, int(mode)))
+        self._e._check(self._e._L.vdl_plan_set_wide_sums_sharded(self._h, int(bool(sharded) and int(mode) != 0)))
 
     @property
     def wide_sums(self):
         return int(self._e._L.vdl_plan_wide_sums(self._h))
+
+    @property
+    def wide_sums_sharded(self):
+        return bool(self._e._L.vdl_plan_wide_sums_sharded(self._h))
 
     def wide_note(self):
         """What served the plan's scans in the last wide run ("wide: k_mscan<...> grouped, 7 sums"), or "refused: <reason>"."""
@@ -391,6 +400,27 @@ def order_merge_host(counts, words, limit=0):
     if rc != _lib.VDL_OK or got.value != keep:
         raise VdlError(rc, "vdl_order_merge_host: bad argument")
     return run, idx
+
+
+def comm_merge_host_wide(world, ops, gathered, stride_words=0):
+    """vdl_comm_merge_host_wide: the merge of a sharded wide run's gathered blocks, device-free.  `gathered` holds `world` blocks
+    of `stride_words` int64 (0 = 3 * len(ops) + 1): the raw words, the words with FIRST entries resolved, the rank's status, the
+    high words of the raw words.  Returns (lo, hi, (status, rank)) -- int64 arrays of len(ops) values each; rank -1 = no rank
+    failed."""
+    L = _lib.load()
+    n = len(ops)
+    g = np.ascontiguousarray(gathered, dtype=np.int64)
+    stride = int(stride_words) or 3 * n + 1
+    if len(g) < world * stride:
+        raise ValueError("gathered holds fewer than world * stride_words values")
+    c_ops = (ctypes.c_int32 * max(n, 1))(*[int(o) for o in ops])
+    lo, hi, status = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(2, np.int64)
+    p64 = ctypes.POINTER(ctypes.c_int64)
+    rc = L.vdl_comm_merge_host_wide(int(world), n, c_ops, g.ctypes.data_as(p64), int(stride_words), lo.ctypes.data_as(p64), hi.ctypes.data_as(p64),
+                                    status.ctypes.data_as(p64))
+    if rc != _lib.VDL_OK:
+        raise VdlError(rc, "vdl_comm_merge_host_wide: bad argument")
+    return lo, hi, (int(status[0]), int(status[1]))
 
 
 def collate_host(heap, codes):

@@ -11,6 +11,16 @@ also reports the largest sum_charge of Q1 as a fraction of INT64_MAX.
 in mode 1 (the exact values).  A child that fails ends the whole measurement: nothing more is started on the device.
 
     python tools/wide_bench.py --sf sf100 --repeats 3 --steps 20 --parent /path/to/parent/tree --out profiles/r20/wide_bench.txt
+
+--sharded: the sharded leg (DESIGN.md section 5.17 "Sharded runs") instead: every process opens a ONE-RANK RCCL communicator and steps
+through vdl_run_sharded_begin / _end over two slots, query k + 1 begun before query k is collected; a step is one begin plus the
+collection of the query before it, timed on the host.  Five sides: the parent's plain sharded step (with --parent), this tree's with
+the switch off -- the same path, so the two must agree within the spread of the repeats --, this tree's wide sharded step (mode 1 with
+vdl_plan_set_wide_sums_sharded), one vdl_run_sharded call per query in mode 1, and vdl_run in mode 1 on the same rows.  Against
+vdl_run the single call shows what the wider block, the merge kernel and the second copy cost with nothing hidden, and the pipelined
+step what is left of it once the copy-out runs behind the next scan.  One rank on one device: no multi-GPU timing is taken.
+
+    python tools/wide_bench.py --sharded --rows 75004738 --repeats 3 --steps 40 --parent /path/to/parent/tree --out profiles/r21/wide_sharded.txt
 """
 import argparse
 import json
@@ -37,9 +47,13 @@ def child(args):
     plan = eng.parse(open(os.path.join(ROOT, "tests", "golden", args.query + ".vdl")).read())
     plan.set_profiling(True)
     plan.set_jit(True, tune=True)
-    if args.mode:
+    if args.mode and args.leg.startswith("sharded"):
+        plan.set_wide_sums(args.mode, sharded=True)
+    elif args.mode:
         plan.set_wide_sums(args.mode)                          # (never called on the parent's package: it has no such switch)
     out = {"query": args.query, "mode": args.mode, "rows": rows, "root": root}
+    if args.leg.startswith("sharded"):
+        return sharded_child(args, eng, plan, out)
     try:
         res = plan.run()                                       # builds, tunes
     except m.VdlError as exc:
@@ -63,6 +77,103 @@ def child(args):
     return 0
 
 
+def sharded_child(args, eng, plan, out):
+    """the pipelined sharded step on a one-rank RCCL communicator: begin(k), then collect k - 1"""
+    import mplan2vdl_amd as m
+
+    eng.comm_init_rccl(0, 1, eng.comm_unique_id())
+    try:
+        res = plan.run_sharded()                               # builds, tunes
+    except m.VdlError as exc:
+        out.update({"error_code": exc.code, "message": str(exc)})
+        print(json.dumps(out))
+        return 0
+    L, c, h = eng._L, eng._c, plan._h
+    if args.leg == "sharded1":                                 # one vdl_run_sharded per step: local phase, merge and finalisation, nothing overlapped
+        for _ in range(args.warmup):
+            eng._check(L.vdl_run_sharded(c, h))
+        wall = []
+        for _ in range(args.steps):
+            t0 = time.perf_counter()
+            eng._check(L.vdl_run_sharded(c, h))
+            wall.append((time.perf_counter() - t0) * 1e6)
+        fields = {name[1:]: [int(x) for x in vals] for f in res["results"].values() for name, vals in f.items()}
+        out.update({"scan_us": [plan.scan_stats()[2]], "wall_us": wall, "bytes_moved": 0, "traffic": "", "kernel": [k for k in plan.collect()["timings"] if "FusedScan_" in k],
+                    "jit_note": plan.jit_note(), "wide_note": plan.wide_note() if args.mode else "", "results": fields})
+        print(json.dumps(out))
+        eng.close()
+        return 0
+
+    def step(k):                                               # (the C calls alone: converting the outputs to Python is no part of a step)
+        eng._check(L.vdl_run_sharded_begin(c, h, k & 1))
+        if k:
+            eng._check(L.vdl_run_sharded_end(c, h, 1 - (k & 1)))
+
+    for k in range(args.warmup + 1):
+        step(k)
+    wall = []
+    for k in range(args.warmup + 1, args.warmup + 1 + args.steps):
+        t0 = time.perf_counter()
+        step(k)
+        wall.append((time.perf_counter() - t0) * 1e6)
+    eng._check(L.vdl_run_sharded_end(c, h, (args.warmup + args.steps) & 1))
+    last = plan.collect()
+    fields = {name[1:]: [int(x) for x in vals] for f in res["results"].values() for name, vals in f.items()}
+    same = {name[1:]: [int(x) for x in vals] for f in last["results"].values() for name, vals in f.items()} == fields
+    out.update({"scan_us": [plan.scan_stats()[2]], "wall_us": wall, "bytes_moved": 0, "traffic": "", "kernel": [k for k in last["timings"] if "FusedScan_" in k],
+                "jit_note": plan.jit_note(), "wide_note": plan.wide_note() if args.mode else "", "results": fields, "last_equals_first": same})
+    print(json.dumps(out))
+    eng.close()
+    return 0
+
+
+def sharded_main(args, say, spawn):
+    """--sharded: alternating fresh processes, five sides"""
+    sides = ([("parent", 0, args.parent, "sharded")] if args.parent else []) + [("off", 0, None, "sharded"), ("wide", 1, None, "sharded"), ("wide1", 1, None, "sharded1"), ("run", 1, None, "")]
+    names = {"parent": "parent, plain sharded step", "off": "this tree, switch off, sharded step", "wide": "this tree, wide sharded step (mode 1)",
+             "wide1": "this tree, vdl_run_sharded in mode 1", "run": "this tree, vdl_run in mode 1"}
+    queries = [q for q in args.queries.split(",") if q]
+    got = {}
+    for rep in range(args.repeats):
+        for query in queries:
+            for side, mode, root, leg in sides:
+                r = spawn(query, mode, root, args.rows, leg)
+                if "error_code" in r:
+                    say("FAILED: %s %s: [%d] %s" % (query, side, r["error_code"], r["message"]))
+                    raise SystemExit(1)
+                got.setdefault((query, side), []).append(r)
+                say("round %d %s %-6s step %s us  %s" % (rep, query, side, spread(r["wall_us"]), r["kernel"]))
+    say()
+    say("One rank on one device (a one-rank RCCL communicator: no gather, the merge kernel reads the send buffer).  No multi-GPU timing exists")
+    say("or was taken: what a wider all-gather costs between devices is not in these numbers.")
+    say()
+    for query in queries:
+        say("%s at %d rows, %d processes per side, %d timed steps each: median over processes of the process medians (min .. max), host microseconds per step" %
+            (query, got[(query, "off")][0]["rows"], args.repeats, args.steps))
+        med, spreads = {}, {}
+        for side, _, _, _ in sides:
+            xs = [statistics.median(r["wall_us"]) for r in got[(query, side)]]
+            med[side], spreads[side] = statistics.median(xs), max(xs) - min(xs)
+            say("  %-40s %s   %s" % (names[side], spread(xs), got[(query, side)][-1]["kernel"]))
+        if args.parent:
+            d = med["off"] - med["parent"]
+            say("  switch off - parent: %+.1f us (ratio %.4f); spread of the repeats: parent %.1f us, switch off %.1f us -> %s" %
+                (d, med["off"] / med["parent"], spreads["parent"], spreads["off"], "within the spread" if abs(d) <= max(spreads["parent"], spreads["off"]) else "OUTSIDE the spread"))
+        say("  wide sharded step - vdl_run in mode 1: %+.1f us (ratio %.4f): what the wider block, the merge kernel and the second copy add, less what the" %
+            (med["wide"] - med["run"], med["wide"] / med["run"]))
+        say("      pipelined step hides (vdl_run waits for its copy-out; a sharded step collects the query before, whose copy ran behind this one's scan)")
+        say("  vdl_run_sharded in mode 1 (one call per query, nothing overlapped) - vdl_run in mode 1: %+.1f us (ratio %.4f): the wider block, the merge" %
+            (med["wide1"] - med["run"], med["wide1"] / med["run"]))
+        say("      kernel, the second copy and the hop to the communication stream, with nothing hidden")
+        say("  wide sharded step / switch-off sharded step: %.4f" % (med["wide"] / med["off"]))
+        wide, off, run = (got[(query, s)][-1]["results"] for s in ("wide", "off", "run"))
+        say("  wide sharded results == vdl_run's in mode 1: %s; low words == the switch-off sharded results: %s; every pipelined answer its own: %s" %
+            (wide == run, all([(x & ((1 << 64) - 1)) for x in wide[k]] == [(x & ((1 << 64) - 1)) for x in off[k]] for k in off),
+             all(r.get("last_equals_first", True) for s in ("off", "wide") for r in got[(query, s)])))
+        say("  wide note: %s" % got[(query, "wide")][-1]["wide_note"])
+        say()
+
+
 def spread(xs):
     return "%.1f (%.1f .. %.1f)" % (statistics.median(xs), min(xs), max(xs))
 
@@ -83,6 +194,8 @@ def main():
     ap.add_argument("--queries", default="q6,q1")
     ap.add_argument("--timeout", type=int, default=600)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sharded", action="store_true", help="the sharded leg: begin / end steps on a one-rank RCCL communicator")
+    ap.add_argument("--leg", default="", help="(child) sharded: the pipelined sharded step instead of vdl_run")
     args = ap.parse_args()
     if args.child:
         return child(args)
@@ -93,9 +206,9 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    def spawn(query, mode, root, rows):
+    def spawn(query, mode, root, rows, leg=""):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", "--query", query, "--mode", str(mode), "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--sf", args.sf, "--rows", str(rows)] + (["--root", root] if root else [])
+               "--sf", args.sf, "--rows", str(rows), "--leg", leg] + (["--root", root] if root else [])
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=args.timeout)
         if p.returncode != 0:
             say("FAILED (%d): %s\n%s" % (p.returncode, " ".join(cmd), p.stderr.decode()[-2000:]))
@@ -106,6 +219,9 @@ def main():
     queries = [q for q in args.queries.split(",") if q] if args.repeats > 0 else []      # (--repeats 0: the --wrap-rows part alone)
     got = {}
     try:
+        if args.sharded:
+            sharded_main(args, say, spawn)
+            return 0
         for rep in range(args.repeats):                        # alternating: every side once per round
             for query in queries:
                 for side, mode, root in sides:
