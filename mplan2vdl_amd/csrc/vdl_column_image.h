@@ -1,5 +1,5 @@
 // vdl_column_image.h -- frame-of-reference images of catalog columns: the rules only (pure functions, no device, no context;
-// tests/test_column_images_cpu.py checks them against brute force under ASan + UBSan).  Used by vdl_engine.cpp.
+// tests/test_column_images_cpu.py checks them against brute force under ASan + UBSan).  Used by vdl_bind.cpp.
 //
 // A column whose values span few significant digits is kept a second time, narrow: v = base + scale * e with e stored in 1, 2 or
 // 4 bytes.  An aggregate scan reads the image instead of the column where every use of the column there can be rewritten into the
@@ -81,37 +81,29 @@ inline void compose(const Image &im, int64_t a, int64_t s, int64_t *a2, int64_t 
 // the factor is the bare value (MAggDesc::plain)
 inline bool plain(int64_t a, int64_t s) { return a == 0 && s == 1; }
 
-// Uses of a column inside one aggregate scan (bit masks over the scan's columns), gathered by the binder: an affine image may be
-// read only when every use is a range filter, a formula test or an aggregate factor (other than a FIRST); a pure narrowing always.
-inline bool usable(const Image &im, bool raw_use) { return im.width > 0 && (im.pure() || !raw_use); }
-
-// Uses of a column inside a scan with derived columns -- a fused front, a dimension scan, a semi-join scan.  A column whose values the
-// select pass needs only for its filters and formula tests stays in the encoded domain there (bounds rewritten as above).  A column
-// whose values it needs per row -- the source of a lookup or a difference, the position of a semi-join -- is decoded with the tile,
-// and that may only cost an add: such a column is read from its image only when the scale is 1 (its filters stay as planned).  The
-// take side of a front decodes whatever it loads for a survivor, base + scale * e in wrapping 64-bit arithmetic (outputs, operands of
-// row expressions), once per survivor, at any scale; a carried column travels decoded, or is not carried.  A pure narrowing decodes
-// to itself and costs nothing.
-inline bool usable_in_vscan(const Image &im, bool per_row_value) { return im.width > 0 && (im.scale == 1 || !per_row_value); }
-// The target of a lookup (VC_GATHER: dimension column `name` at row v[idx]) read from its image -- a lookup image -- is bound by the
-// very rules of a streamed column, applied to the use of the LOOKED-UP value: usable() in an aggregate scan (a source of another
-// derived column, a load of the group key and a FIRST column are raw uses: pure narrowings only), usable_in_vscan() in a scan with
-// derived columns (the source of a further lookup or of a difference and a semi-join position are per-row values: scale 1, decoded
-// right after the lookup, filters as planned).  Every other lookup stays encoded: map_range over its filter and formula tests,
-// compose over its aggregate factors.  The index is checked against the target's row count as before; the image has as many entries.
-// What the binder does with a lookup image it may read (tests/test_lookup_images_cpu.py checks both ways against brute force):
-enum LookupUse { LOOKUP_CATALOG = 0,      // not readable here: the catalog column
-                 LOOKUP_ENCODED = 1,      // read and left encoded: bounds through map_range, factors through compose
-                 LOOKUP_DECODED = 2 };    // read and decoded after the lookup (MsArgs::decode): bounds and tests as planned
-// in an aggregate scan (raw_use: as usable()) -- never decoded: a raw use admits only a pure narrowing, whose encoded values are the column's
-inline LookupUse lookup_use(const Image &im, bool raw_use) { return usable(im, raw_use) ? LOOKUP_ENCODED : LOOKUP_CATALOG; }
-// in a scan with derived columns (per_row_value: as usable_in_vscan())
-inline LookupUse lookup_use_in_vscan(const Image &im, bool per_row_value) {
-    if (!usable_in_vscan(im, per_row_value)) return LOOKUP_CATALOG;
-    return per_row_value && !im.pure() ? LOOKUP_DECODED : LOOKUP_ENCODED;
+// ---- the use rules ---------------------------------------------------------------------------------------------------------
+// What a scan does with the image of a column it reads -- a streamed table column, or the target of a lookup (VC_GATHER: dimension
+// column `name` at row v[idx]; its image read in its place is a lookup image, with as many entries as the column, the index checked
+// against the row count as before).  The rules speak of the use of the VALUE, streamed or looked up, so one statement serves both
+// (tests/test_lookup_images_cpu.py checks them against brute force; the kernel headers' comments call use_in_vscan "usable_in_vscan"):
+enum Use { USE_CATALOG = 0,      // not readable here: the catalog column
+           USE_ENCODED = 1,      // read and left encoded: bounds and formula tests through map_range, factors through compose
+           USE_DECODED = 2 };    // read and decoded where it is loaded (MsArgs::decode): bounds and tests as planned
+// In an aggregate scan, which cannot decode with the tile.  raw_use: the scan needs the stored value itself -- the source of a
+// derived column other than a formula test, a load of the group key, the column of a FIRST aggregate.  An affine image may be read
+// only when every use is a range filter, a formula test or an aggregate factor; a pure narrowing always, and its encoded values are
+// the column's: never decoded.
+inline Use use_in_aggregate(const Image &im, bool raw_use) { return im.width > 0 && (im.pure() || !raw_use) ? USE_ENCODED : USE_CATALOG; }
+// In a scan with derived columns -- a fused front, a dimension scan, a semi-join scan.  A value the select pass needs only for its
+// filters and formula tests stays in the encoded domain there (bounds rewritten as above).  A value it needs per row -- the source of
+// a lookup or a difference, the position of a semi-join -- is decoded as it is loaded, and that may only cost an add: it is read from
+// the image only when the scale is 1 (its filters stay as planned).  A pure narrowing decodes to itself and costs nothing.  (The take
+// side of a front reads what these rules let the select side read and decodes whatever it loads for a survivor, base + scale * e in
+// wrapping 64-bit arithmetic, once per survivor, at any scale; a carried column travels decoded, or is not carried.)
+inline Use use_in_vscan(const Image &im, bool per_row_value) {
+    if (im.width <= 0 || (im.scale != 1 && per_row_value)) return USE_CATALOG;
+    return per_row_value && !im.pure() ? USE_DECODED : USE_ENCODED;
 }
-// the kernels must decode the column's values (MsArgs::decode)
-inline bool needs_decode(const Image &im) { return im.width > 0 && !im.pure(); }
 
 // ---- bit-packed images ---------------------------------------------------------------------------------------------------
 // A column's byte image (base, scale, e) is kept a third time with e' = e - emin in exactly `bits` bits per row, bits = the bit

@@ -5,6 +5,7 @@
 //               per table (vdl_fuse.cpp decides, k_scan executes);
 //   * general : any other program runs statement by statement with one kernel per operator;
 //               RangeV/RangeC, Project, Shuffle and identity Gathers never touch memory.
+// This file runs things; how a planned scan and the catalog's columns become kernel arguments is vdl_bind.cpp.
 #include <chrono>
 
 #include "vdl_genexec.h"
@@ -69,208 +70,6 @@ int64_t plan_words(const vdl_plan *p, std::vector<int32_t> *ops, bool *shardable
     return off;
 }
 
-}  // namespace
-
-namespace vdl {
-namespace eng {
-
-// single-aggregate scans over <= 4 columns take the tuned k_scan; everything else k_mscan
-bool use_kscan(const ScanPlan &sp) {
-    for (const ScanColumn &c : sp.cols) if (c.kind != VC_DIRECT) return false;       // derived columns (fused join scans): k_mscan
-    if (getenv("VDL_NO_KSCAN")) return false;                                         // experiments: everything through k_mscan
-    return sp.aggs.size() == 1 && sp.cols.size() <= 4;
-}
-
-// A comparison of two columns is planned as a range of their difference (vdl_fuse.cpp mk_cmp_diff: a > b as a - b in [1, max]), read
-// for its sign and its zero.  The wrap-around difference (VC_SUB) has them right while a - b stays inside int64: certain when both
-// operands are table columns, or lookups of columns, stored in fewer than 8 bytes (TPC-H compares int32 dates this way: those scans
-// are what they were).  Over anything wider the bound scan computes the saturated difference instead (VC_SUBS), whose sign and zero
-// are those of the exact one for any operands.  (A Subtract the program wrote itself means its wrap-around value and carries no mark.)
-static int bound_kind(vdl_ctx *c, const std::vector<ScanColumn> &sc, const ScanColumn &s) {
-    if (s.kind != VC_SUB || !s.order_diff) return s.kind;
-    for (int src : {s.idx, s.idx2}) {
-        const ScanColumn *o = src >= 0 && (size_t)src < sc.size() ? &sc[(size_t)src] : nullptr;
-        if (!(o && (o->kind == VC_DIRECT || o->kind == VC_GATHER) && find_col(c, o->name).width < 8)) return VC_SUBS;
-    }
-    return VC_SUB;
-}
-
-// formula columns (VC_FORM) into the descriptor's pool, in the kernels' layout (MScanDesc::form): the range tests sorted by
-// column, then the postfix program with every test replaced by a reference to its result bit
-static void bind_forms(const std::vector<ScanColumn> &sc, MScanDesc &d) {
-    int used = 0;
-    for (size_t k = 0; k < sc.size(); k++) {
-        if (sc[k].kind != VC_FORM) continue;
-        const std::vector<FormStep> &prog = sc[k].form;
-        std::vector<int> tests;
-        for (size_t i = 0; i < prog.size(); i++) if (prog[i].op == FormStep::LEAF) tests.push_back((int)i);
-        std::stable_sort(tests.begin(), tests.end(), [&](int x, int y) { return prog[(size_t)x].col < prog[(size_t)y].col; });
-        if (tests.size() > 64 || used + (int)(tests.size() + prog.size()) > kMaxFormPool)
-            throw Error(VDL_ERR_UNSUPPORTED, "the scan's conditions do not fit the descriptor (" + std::to_string(kMaxFormPool) + " steps in all, 64 tests per condition)");
-        std::vector<int> bit_of(prog.size(), -1);
-        d.dsrc[k] = used;
-        d.dtests[k] = (int)tests.size();
-        for (size_t t = 0; t < tests.size(); t++) { bit_of[(size_t)tests[t]] = (int)t; d.form[used++] = prog[(size_t)tests[t]]; }
-        for (size_t i = 0; i < prog.size(); i++) {
-            FormStep f = prog[i];
-            if (f.op == FormStep::LEAF) { f.op = FormStep::REF; f.col = bit_of[i]; f.lo = f.hi = 0; }
-            d.form[used++] = f;
-        }
-        d.dsrc2[k] = used - d.dsrc[k];
-    }
-}
-
-// A row-id column that only CONDITIONS read (the reference's anti-join shape `k - row id` as a truth value: every row but row k)
-// means the row's number in the table: on a rank of a sharded run it counts from the table's first row.  One that INDEXES a lookup
-// (the bit of the row's own id in a set built over this shard's rows: co-partitioned placements) keeps counting from the shard's.
-static bool rowid_counts_from_the_table(const std::vector<ScanColumn> &sc) {
-    bool any = false, as_index = false;
-    for (const ScanColumn &c : sc) any |= c.kind == VC_ROWID;
-    for (const ScanColumn &c : sc) {
-        if (c.kind == VC_DIRECT || c.kind == VC_FORM || c.kind == VC_ROWID) continue;
-        for (int src : {c.idx, c.idx2}) if (src >= 0 && (size_t)src < sc.size() && sc[(size_t)src].kind == VC_ROWID) as_index = true;
-    }
-    return any && !as_index;
-}
-
-// Columns of an aggregate scan that must be read with their stored values, so that only a pure narrowing may stand in for them
-// (vdl_column_image.h): sources of derived columns other than formula tests, loads of the group key, the column of a FIRST aggregate
-static uint32_t raw_value_uses(const std::vector<ScanColumn> &sc, const std::vector<ScanAgg> &aggs, const std::vector<KeyStep> *key) {
-    uint32_t m = 0;
-    for (const ScanColumn &c : sc)
-        if (c.kind != VC_DIRECT && c.kind != VC_FORM) for (int src : {c.idx, c.idx2}) if (src >= 0 && src < 32) m |= 1u << src;
-    if (key) for (const KeyStep &k : *key) if (k.kind == KeyStep::LOAD && k.col >= 0 && k.col < 32) m |= 1u << k.col;
-    for (const ScanAgg &ag : aggs) if (ag.kind == AGG_FIRST) for (const ScanFactor &f : ag.fac) if (f.col >= 0 && f.col < 32) m |= 1u << f.col;
-    return m;
-}
-static const std::vector<KeyStep> *key_of(const ScanPlan &) { return nullptr; }
-static const std::vector<KeyStep> *key_of(const GroupScanPlan &gp) { return &gp.key; }
-// the grouped scan's key program and pivots
-static void bind_key(const ScanPlan &, MScanDesc &) {}
-static void bind_key(const GroupScanPlan &gp, MScanDesc &d) {
-    d.nkey = (int)gp.key.size();
-    for (int k = 0; k < d.nkey; k++) d.key[k] = gp.key[(size_t)k];
-    d.pmin = gp.pmin; d.pcount = gp.pcount;
-}
-
-// "name:width ..." of the columns (bits of `which`) a bound scan reads from their images: its entry in vdl_plan_image_columns
-std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which) {
-    std::string t;
-    for (int k = 0; k < cols.ncol && (size_t)k < sc.size(); k++)
-        if (((cols.image & which) >> k) & 1u) t += (t.empty() ? "" : " ") + sc[(size_t)k].name + ":" + std::to_string(cols.width[k]);
-    return t;
-}
-// ... the target columns its lookups read from their images (MScanCols::limage): its entry in vdl_plan_lookup_columns
-std::string lookup_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which) {
-    std::string t;
-    for (int k = 0; k < cols.ncol && (size_t)k < sc.size(); k++)
-        if (((cols.limage & which) >> k) & 1u) t += (t.empty() ? "" : " ") + sc[(size_t)k].name + ":" + std::to_string(cols.width[k]);
-    return t;
-}
-// the image a lookup may read in place of its target column: lookup images are on (vdl_set_lookup_images, under vdl_set_column_images)
-// and the column has a byte image -- built on the device, or declared on a context without one (vdl_declare_column_image)
-static bool has_lookup_image(const vdl_ctx *c, const Column &col) {
-    return c->images && c->lookup_images && col.image.width > 0 && (col.image_buf || c->device < 0);
-}
-// ... and from their step images, "name:s ...": its entry in vdl_plan_step_columns
-std::string step_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which) {
-    std::string t;
-    for (int k = 0; k < cols.ncol && (size_t)k < sc.size(); k++)
-        if (((cols.steps & which) >> k) & 1u) t += (t.empty() ? "" : " ") + sc[(size_t)k].name + ":s";
-    return t;
-}
-
-template <typename PlanT>
-// packed: 0 = byte images only; 1 = the filter columns from their bit-packed images (the packed form), 2 = every table column that has one
-int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0, int packed) {
-    cols = MScanCols{};
-    d = MScanDesc{};
-    cols.ncol = (int)sp.cols.size();
-    d.nagg = (int)sp.aggs.size();
-    int64_t n = -1;
-    *bytes_per_row = 0;
-    const uint32_t raw = raw_value_uses(sp.cols, sp.aggs, key_of(sp));
-    img::Image ims[kMaxVCols];
-    for (int k = 0; k < cols.ncol; k++) {
-        const ScanColumn &sc = sp.cols[(size_t)k];
-        cols.kind[k] = bound_kind(c, sp.cols, sc);
-        cols.lo[k] = sc.lo; cols.hi[k] = sc.hi;
-        cols.filtered[k] = (cols.lo[k] != INT64_MIN || cols.hi[k] != INT64_MAX) ? 1 : 0;
-        d.dkind[k] = cols.kind[k]; d.dsrc[k] = sc.idx; d.dsrc2[k] = sc.idx2;
-        if (sc.kind == VC_DIRECT) {
-            const Column &col = find_col(c, sc.name);
-            if (n >= 0 && col.n != n)
-                throw Error(VDL_ERR_SHAPE, "columns of table '" + sp.table + "' have different lengths in the catalog");
-            n = col.n;
-            cols.ptr[k] = col.dev; cols.width[k] = col.width;
-            if (c->images && (col.image_buf || c->device < 0) && img::usable(col.image, (raw >> k) & 1u)) {      // (no device: a declared image)
-                // the image instead of the column: its bounds in the encoded domain (the filtered bit stays what the plan says)
-                ims[k] = col.image;
-                cols.image |= 1u << k;
-                cols.ptr[k] = col.image_buf ? col.image_buf->p : nullptr; cols.width[k] = col.image.width;
-                img::map_range(col.image, sc.lo, sc.hi, &cols.lo[k], &cols.hi[k]);
-            }
-            img::Image pim;                                           // the packed image as an image: for the rules and compose
-            pim.width = 4; pim.base = col.packed.base; pim.scale = col.packed.scale;
-            if (packed && c->images && col.packed.bits && (packed == 2 || cols.filtered[k]) && img::usable(pim, (raw >> k) & 1u)) {
-                // the packed image: bounds on e' in [0, 2^bits - 1], factors composed with (base', scale)
-                ims[k] = pim;
-                cols.image |= 1u << k;
-                cols.packed |= 1u << k;
-                cols.pbits[k] = col.packed.bits;
-                cols.ptr[k] = col.packed_buf ? col.packed_buf->p : nullptr; cols.width[k] = 4;
-                img::map_range_packed(col.packed, sc.lo, sc.hi, &cols.lo[k], &cols.hi[k]);
-            }
-            *bytes_per_row += cols.width[k];
-        } else if (sc.kind == VC_GATHER || sc.kind == VC_INRANGE) {      // a column of another table, looked up / its length
-            const Column &col = find_col(c, sc.name);
-            cols.ptr[k] = col.dev; cols.width[k] = col.width;
-            d.dn[k] = col.n;
-            if (sc.kind == VC_GATHER && has_lookup_image(c, col) && img::lookup_use(col.image, (raw >> k) & 1u) == img::LOOKUP_ENCODED) {
-                // the lookup image: the looked-up value stays encoded, its bounds, tests and factors rewritten like a streamed column's
-                ims[k] = col.image;
-                cols.limage |= 1u << k;
-                cols.ptr[k] = col.image_buf ? col.image_buf->p : nullptr; cols.width[k] = col.image.width;
-                img::map_range(col.image, sc.lo, sc.hi, &cols.lo[k], &cols.hi[k]);
-            }
-        } else {                                                          // VC_BITS / VC_LUT: filled in by run_prelude before every launch
-            cols.ptr[k] = nullptr; cols.width[k] = 8;
-            d.dn[k] = 0;
-        }
-    }
-    for (int k = 0; k < cols.ncol; k++) { d.flo[k] = cols.lo[k]; d.fhi[k] = cols.hi[k]; }
-    bind_forms(sp.cols, d);
-    for (int k = 0; k < cols.ncol; k++)                               // a formula's tests of a column read from its image
-        if (cols.kind[k] == VC_FORM)
-            for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dtests[k]; f++)
-                if (d.form[f].col >= 0 && (((cols.image | cols.limage) >> d.form[f].col) & 1u)) img::map_range(ims[d.form[f].col], d.form[f].lo, d.form[f].hi, &d.form[f].lo, &d.form[f].hi);
-    cols.n = n;
-    cols.row0 = row0;
-    cols.rowid_global = rowid_counts_from_the_table(sp.cols);
-    for (int j = 0; j < d.nagg; j++) {
-        const ScanAgg &ag = sp.aggs[(size_t)j];
-        MAggDesc &m = d.agg[j];
-        m.kind = ag.kind;
-        m.constant = ag.constant;
-        for (const ScanFactor &f : ag.fac) {
-            int64_t a = f.a, s = f.s;
-            if (((cols.image | cols.limage) >> f.col) & 1u) img::compose(ims[f.col], f.a, f.s, &a, &s);     // a + s * (base + scale * e)
-            m.used |= 1u << f.col;
-            if (img::plain(a, s)) m.plain |= 1u << f.col;
-            m.fa[f.col] = a; m.fs[f.col] = s;
-        }
-    }
-    bind_key(sp, d);
-    return n;
-}
-template int64_t bind_mscan(vdl_ctx *, const ScanPlan &, MScanCols &, MScanDesc &, int64_t *, int64_t, int);
-template int64_t bind_mscan(vdl_ctx *, const GroupScanPlan &, MScanCols &, MScanDesc &, int64_t *, int64_t, int);
-
-}  // namespace eng
-}  // namespace vdl
-
-namespace {
-
 // the precompiled multi-aggregate kernel's name, ",img" where some columns are read from their images (as the specialised kernels' names: vdl_specialise.cpp)
 static std::string mscan_label(const ScanLaunch &cfg, const MScanCols &cols) {
     std::string n = mscan_kernel_name(cfg);
@@ -306,8 +105,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
     p->jit_note.clear();
     p->wide_note.clear();
     p->jit_builds.clear();
-    for (auto it = p->image_roles.begin(); it != p->image_roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->image_roles.erase(it) : std::next(it);
-    for (auto it = p->lookup_roles.begin(); it != p->lookup_roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->lookup_roles.erase(it) : std::next(it);
+    for (auto it = p->roles.begin(); it != p->roles.end();) it = it->first.compare(0, 4, "scan") == 0 ? p->roles.erase(it) : std::next(it);
     p->jit_tuned = false;
     p->gword_offset.assign(ng, 0);
     p->reduce_ops.clear();
@@ -325,26 +123,7 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         p->kscan[s] = eligible && !(p->use_jit && !sp.never) && !p->wide;    // specialising: the single-aggregate scan runs through the general body too
         if (eligible) {                                       // (bound either way: the tuner compares the two)
             ScanArgs &a = p->sargs[s];
-            a.ncol = (int)sp.cols.size(); a.nagg = 1; a.never = sp.never ? 1 : 0;
-            n = -1;
-            for (int k = 0; k < a.ncol; k++) {
-                const Column &col = find_col(c, sp.cols[(size_t)k].name);
-                if (n >= 0 && col.n != n)
-                    throw Error(VDL_ERR_SHAPE, "columns of table '" + sp.table + "' have different lengths in the catalog");
-                n = col.n;
-                a.ptr[k] = col.dev; a.width[k] = col.width;
-                a.lo[k] = sp.cols[(size_t)k].lo; a.hi[k] = sp.cols[(size_t)k].hi;
-                a.filtered[k] = (a.lo[k] != INT64_MIN || a.hi[k] != INT64_MAX) ? 1 : 0;
-                bpr += col.width;
-            }
-            a.n = n;
-            const ScanAgg &ag = sp.aggs[0];
-            a.kind[0] = ag.kind; a.constant[0] = ag.constant;
-            for (const ScanFactor &f : ag.fac) {
-                a.used[0] |= 1u << f.col;
-                if (f.a == 0 && f.s == 1) a.plain[0] |= 1u << f.col;
-                a.fa[0][f.col] = f.a; a.fs[0][f.col] = f.s;
-            }
+            n = bind_kscan(c, sp, a, &bpr);
             p->scfg[s] = scan_launch_config(a, c->num_cus);
             if (p->scfg[s].variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no scan kernel variant for this shape");
             p->block_partials[s] = dev_alloc(c, sizeof(int64_t) * (size_t)p->scfg[s].grid * 2);
@@ -352,11 +131,9 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
             kname = std::string(scan_kernel_name(p->scfg[s])) + "_grid" + std::to_string(p->scfg[s].grid);
         }
         if (!p->kscan[s]) {
-            bpr = 0;
-            n = bind_mscan(c, sp, p->mcols[s], p->mdesc[s], &bpr, p->row_offset);
+            n = bind_scan(c, p, s, p->mcols[s], p->mdesc[s], &bpr, p->row_offset);
             p->mdesc[s].wide = p->wide ? 1 : 0;
-            p->image_roles["scan" + std::to_string(s)] = image_text(sp.cols, p->mcols[s]);
-            p->lookup_roles["scan" + std::to_string(s)] = lookup_text(sp.cols, p->mcols[s]);
+            note_roles(p, "scan" + std::to_string(s), sp.cols, p->mcols[s]);
             p->mcfg[s] = mscan_launch_config(p->mcols[s], p->mdesc[s], false, c->num_cus);
             if (p->mcfg[s].variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no multi-aggregate scan kernel variant for this shape");
             std::string jname;
@@ -377,9 +154,8 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
         const GroupScanPlan &gp = F.gscans[g];
         const size_t m = ns + g;
         int64_t bpr = 0;
-        const int64_t n = bind_mscan(c, gp, p->mcols[m], p->mdesc[m], &bpr, p->row_offset);
-        p->image_roles["scan" + std::to_string(m)] = image_text(gp.cols, p->mcols[m]);
-        p->lookup_roles["scan" + std::to_string(m)] = lookup_text(gp.cols, p->mcols[m]);
+        const int64_t n = bind_scan(c, p, m, p->mcols[m], p->mdesc[m], &bpr, p->row_offset);
+        note_roles(p, "scan" + std::to_string(m), gp.cols, p->mcols[m]);
         MScanDesc &d = p->mdesc[m];
         d.wide = p->wide ? 1 : 0;
         p->mcfg[m] = mscan_launch_config(p->mcols[m], d, true, c->num_cus);
@@ -405,86 +181,6 @@ void bind_fused(vdl_ctx *c, vdl_plan *p) {
                                      std::to_string(mscan_sums(d)) + " sums";
     }
     p->bound = true;
-}
-
-void patch_prelude(const vdl_plan *p, const std::vector<ScanColumn> &sc, MScanCols &cols, MScanDesc &d);
-// The columns of a scan with derived columns (fused front, dimension scans) as kernel arguments; the table's row count.
-// Tables of the prelude are patched in later (patch_prelude); `wanted` collects which ones.
-// A table column with an image is read from it where the use rules allow (vdl_column_image.h usable_in_vscan), ibase / iscale its
-// decode.  One whose values the select pass needs per row (`per_row`: the sources of lookups and differences, plus what the caller
-// names -- the position of a semi-join) and that is not a pure narrowing is decoded with the tile (MsArgs::decode, one add) and
-// keeps the plan's filters; every other one has its filter and formula tests rewritten into the encoded domain.  (The take side of a
-// front decodes everything it loads: bind_front.)  A step image (vdl_column_image.h Steps) goes before the byte image: it decodes to
-// the column's own values wherever it is loaded, so every use is legal and the plan's filters and formula tests stay.
-static int64_t bind_vcols(vdl_ctx *c, const std::string &table, const std::vector<ScanColumn> &sc, MScanCols &cols, MScanDesc &d, std::vector<char> &wanted,
-                          uint32_t per_row = 0) {
-    cols.ncol = (int)sc.size();
-    int64_t n = -1;
-    for (const ScanColumn &s : sc)                                    // sources of lookups and differences
-        if (s.kind != VC_DIRECT && s.kind != VC_FORM) for (int src : {s.idx, s.idx2}) if (src >= 0 && src < 32) per_row |= 1u << src;
-    img::Image ims[kMaxVCols];
-    for (int k = 0; k < cols.ncol; k++) {
-        const ScanColumn &s = sc[(size_t)k];
-        cols.kind[k] = bound_kind(c, sc, s);
-        cols.lo[k] = s.lo; cols.hi[k] = s.hi;
-        cols.filtered[k] = (s.lo != INT64_MIN || s.hi != INT64_MAX) ? 1 : 0;
-        d.flo[k] = s.lo; d.fhi[k] = s.hi;
-        d.dkind[k] = cols.kind[k]; d.dsrc[k] = s.idx; d.dsrc2[k] = s.idx2;
-        if (s.kind == VC_DIRECT) {
-            const Column &col = find_col(c, s.name);
-            if (n >= 0 && col.n != n) throw Error(VDL_ERR_SHAPE, "columns of table '" + table + "' have different lengths in the catalog");
-            n = col.n;
-            cols.ptr[k] = col.dev; cols.width[k] = col.width;
-            if (c->images && c->step_images && col.steps.present && (col.steps_buf || c->device < 0)) {
-                cols.steps |= 1u << k;
-                cols.ptr[k] = col.steps_buf ? col.steps_buf->p : nullptr;
-                d.ibase[k] = col.steps.base;
-                // (its values are base .. base + n - 1 at most: where they fit 32 signed bits the kernels make the sum in 32)
-                cols.width[k] = col.steps.base >= INT32_MIN && col.steps.base <= (int64_t)INT32_MAX - col.n ? 4 : 8;
-            } else if (c->images && (col.image_buf || c->device < 0) && img::usable_in_vscan(col.image, (per_row >> k) & 1u)) {
-                ims[k] = col.image;
-                cols.image |= 1u << k;
-                cols.ptr[k] = col.image_buf ? col.image_buf->p : nullptr; cols.width[k] = col.image.width;
-                d.ibase[k] = col.image.base; d.iscale[k] = col.image.scale;
-                if (img::needs_decode(col.image) && ((per_row >> k) & 1u)) {
-                    cols.decode |= 1u << k;
-                } else {
-                    img::map_range(col.image, s.lo, s.hi, &cols.lo[k], &cols.hi[k]);
-                    d.flo[k] = cols.lo[k]; d.fhi[k] = cols.hi[k];
-                }
-            }
-        } else if (s.kind == VC_GATHER || s.kind == VC_INRANGE) {
-            const Column &col = find_col(c, s.name);
-            cols.ptr[k] = col.dev; cols.width[k] = col.width;
-            d.dn[k] = col.n;
-            const img::LookupUse use = s.kind == VC_GATHER && has_lookup_image(c, col) ? img::lookup_use_in_vscan(col.image, (per_row >> k) & 1u) : img::LOOKUP_CATALOG;
-            if (use != img::LOOKUP_CATALOG) {
-                // the lookup image: a looked-up value the pass needs per row is decoded after the lookup (scale 1) and keeps the plan's
-                // filters; every other one stays encoded, its filter (and, below, its formula tests) rewritten
-                ims[k] = col.image;
-                cols.limage |= 1u << k;
-                cols.ptr[k] = col.image_buf ? col.image_buf->p : nullptr; cols.width[k] = col.image.width;
-                d.ibase[k] = col.image.base; d.iscale[k] = col.image.scale;
-                if (use == img::LOOKUP_DECODED) {
-                    cols.decode |= 1u << k;
-                } else {
-                    img::map_range(col.image, s.lo, s.hi, &cols.lo[k], &cols.hi[k]);
-                    d.flo[k] = cols.lo[k]; d.fhi[k] = cols.hi[k];
-                }
-            }
-        } else {
-            cols.ptr[k] = nullptr; cols.width[k] = 8;
-            if (s.prelude >= 0) wanted[(size_t)s.prelude] = 1;
-        }
-    }
-    bind_forms(sc, d);
-    for (int k = 0; k < cols.ncol; k++)                               // a formula's tests of a column read from its image
-        if (cols.kind[k] == VC_FORM)
-            for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dtests[k]; f++)
-                if (d.form[f].col >= 0 && ((((cols.image | cols.limage) & ~cols.decode) >> d.form[f].col) & 1u))
-                    img::map_range(ims[d.form[f].col], d.form[f].lo, d.form[f].hi, &d.form[f].lo, &d.form[f].hi);
-    cols.n = n;
-    return n;
 }
 
 // One specialised pass of the projection scan: its translation unit, its entry point and what the note calls it
@@ -597,12 +293,7 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         MScanCols cols;
         host_descs.push_back(std::make_shared<MScanDesc>());
         MScanDesc *d = host_descs.back().get();
-        std::vector<char> unused(F.prelude.size(), 0);
-        const uint32_t pos = semi && it.index_col >= 0 && it.index_col < 32 ? 1u << it.index_col : 0u;      // (the semi-join's positions)
-        const int64_t n = bind_vcols(c, it.table, it.cols, cols, *d, unused, pos);
-        p->image_roles[(semi ? "semi" : "dim") + std::to_string(k)] = image_text(it.cols, cols);
-        p->step_roles[(semi ? "semi" : "dim") + std::to_string(k)] = step_text(it.cols, cols);
-        p->lookup_roles[(semi ? "semi" : "dim") + std::to_string(k)] = lookup_text(it.cols, cols);
+        const int64_t n = bind_prelude_scan(c, p, k, cols, *d);
         patch_prelude(p, it.cols, cols, *d);
         if (semi) {
             // the set of rows of another table that a selected row of this one points at: one scan, atomic ORs
@@ -615,9 +306,6 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
             HIP_CHECK(hipMemsetAsync(p->prelude_buf[k]->p, 0, sizeof(uint64_t) * words, c->stream));
             p->prelude_rows[k] = std::max<int64_t>(n, 0);
             if (it.never || n <= 0) continue;
-            d->bitmap_only = 2;
-            d->pmin = it.modulus;
-            d->nout = 1; d->out_col[0] = it.index_col;
             // the Scatter this set stands for writes into a vector as long as ITS table (the fold operand, Vlite.hs:1212-1222):
             // positions at or beyond that length are dropped like any out-of-range Scatter position, also when the indexed
             // table is the longer one
@@ -634,31 +322,21 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         p->prelude_n[k] = n;
         if (it.never || n <= 0) { HIP_CHECK(hipMemsetAsync(p->prelude_buf[k]->p, 0, sizeof(uint64_t) * words, c->stream)); continue; }
         d->out_ptr[0] = (int64_t *)p->prelude_buf[k]->p;           // bitmap only: no positions, no counts
-        d->bitmap_only = 1;
         HIP_CHECK(launch_project_select(cols, desc_on_device(c, p, "dim" + std::to_string(k), *d), c->num_cus, c->stream,
                                         front_kernel(c, p, "dim" + std::to_string(k), [&] { return select_pass(cols, *d, p->jit_rt_bounds); })));
-    }
-}
-// hand the tables to a scan that looks them up
-void patch_prelude(const vdl_plan *p, const std::vector<ScanColumn> &sc, MScanCols &cols, MScanDesc &d) {
-    for (size_t k = 0; k < sc.size(); k++) {
-        if (sc[k].kind != VC_BITS && sc[k].kind != VC_LUT) continue;
-        const BufP &b = p->prelude_buf[(size_t)sc[k].prelude];
-        cols.ptr[k] = b ? b->p : nullptr;
-        d.dn[k] = p->prelude_n[(size_t)sc[k].prelude];
     }
 }
 void run_prelude(vdl_ctx *c, vdl_plan *p) {
     const FusedPlan &F = p->fused;
     if (F.prelude.empty()) return;
     std::vector<char> wanted(F.prelude.size(), 0);
-    const size_t ns = F.scans.size();
-    for (size_t s = 0; s < ns + F.gscans.size(); s++)
-        for (const ScanColumn &sc : (s < ns ? F.scans[s].cols : F.gscans[s - ns].cols))
+    const size_t nscans = F.scans.size() + F.gscans.size();
+    for (size_t s = 0; s < nscans; s++)
+        for (const ScanColumn &sc : scan_columns(p, s))
             if (sc.prelude >= 0) wanted[(size_t)sc.prelude] = 1;
     run_prelude_items(c, p, wanted);
     if (p->after_prelude) p->after_prelude(c, p);
-    for (size_t s = 0; s < ns + F.gscans.size(); s++) patch_prelude(p, s < ns ? F.scans[s].cols : F.gscans[s - ns].cols, p->mcols[s], p->mdesc[s]);
+    for (size_t s = 0; s < nscans; s++) patch_prelude(p, scan_columns(p, s), p->mcols[s], p->mdesc[s]);
 }
 
 void run_fused_local(vdl_ctx *c, vdl_plan *p, int64_t *dev_words, bool single_rank) {
@@ -678,10 +356,8 @@ void run_fused_local(vdl_ctx *c, vdl_plan *p, int64_t *dev_words, bool single_ra
     run_prelude(c, p);
     if (p->use_jit && p->jit_tune && !p->jit_tuned) {
         p->jit_tuned = true;
-        for (size_t s = 0; s < p->mcols.size(); s++) {            // (the lookup tables of this run are in place)
-            const size_t ns0 = p->fused.scans.size();
-            if (p->mjit[s]) patch_prelude(p, s < ns0 ? p->fused.scans[s].cols : p->fused.gscans[s - ns0].cols, p->mcols[s], p->mdesc[s]);
-        }
+        for (size_t s = 0; s < p->mcols.size(); s++)              // (the lookup tables of this run are in place)
+            if (p->mjit[s]) patch_prelude(p, scan_columns(p, s), p->mcols[s], p->mdesc[s]);
         tune_specialised(c, p, dev_words);
     }
     const int ei = (int)(p->run_seq++ % (unsigned)vdl_plan::kEvRing);
@@ -986,133 +662,6 @@ void order_outputs_on_host(vdl_ctx *c, vdl_plan *p) {
 // The fused front of a plan that does not fuse as a whole (ProjPlan, vdl_fuse.h): one scan over the fact table -- two
 // passes: count per tile, then write -- produces the statements of `proj.nodes` as SPARSE vectors on one shared selection;
 // the per-operator executor starts from them (`over`).  false: the plan has no such front (or it is switched off).
-// What is known of the fused front before anything runs: the columns of both passes (the select pass sees only the columns
-// that decide a row's survival, renumbered), which columns the take pass needs and which it writes.  Pointers and sizes of
-// the prelude's tables are patched in by the caller once they exist (patch_front).
-struct FrontBound {
-    MScanCols cols, scols;
-    std::unique_ptr<MScanDesc> d = std::make_unique<MScanDesc>(), sdesc = std::make_unique<MScanDesc>();
-    std::vector<int> renum, distinct;
-    std::vector<char> wanted;
-    int64_t n = 0;
-};
-static void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b) {
-    const ProjPlan &J = p->fused.proj;
-    MScanCols &cols = b.cols;
-    MScanDesc &d = *b.d;
-    b.wanted.assign(p->fused.prelude.size(), 0);
-    b.n = bind_vcols(c, J.table, J.cols, cols, d, b.wanted);
-    cols.row0 = b.scols.row0 = p->row_offset;
-    cols.rowid_global = b.scols.rowid_global = p->front_rowid_global || rowid_counts_from_the_table(J.cols);      // (the sharded front route: every row id is the table's)
-    // columns that decide a row's survival: the filtered ones and what they are derived from; a lookup whose range check is
-    // done by another deciding column through the same index (the dimension bitmap, an INRANGE) decides nothing itself.
-    // Everything else is read for the surviving rows only, in the write pass.
-    {
-        std::vector<char> decides((size_t)cols.ncol, 0);
-        for (int k = 0; k < cols.ncol; k++) decides[(size_t)k] = cols.filtered[k] || J.cols[(size_t)k].kind == VC_INRANGE;
-        for (int k = 0; k < cols.ncol; k++) {
-            const ScanColumn &sc = J.cols[(size_t)k];
-            if (sc.kind != VC_GATHER || decides[(size_t)k]) continue;
-            bool checked = false;
-            for (int j = 0; j < cols.ncol; j++) {
-                const ScanColumn &o = J.cols[(size_t)j];
-                checked |= j != k && o.idx == sc.idx && (o.kind == VC_INRANGE || o.kind == VC_BITS || (o.kind == VC_GATHER && decides[(size_t)j] && j < k));
-            }
-            if (!checked) decides[(size_t)k] = 1;                     // its own range check can drop the row
-        }
-        for (int k = cols.ncol - 1; k >= 0; k--) {
-            if (!decides[(size_t)k]) continue;
-            for (int src : J.cols[(size_t)k].sources()) decides[(size_t)src] = 1;
-        }
-        for (int k = 0; k < cols.ncol; k++) cols.lazy[k] = decides[(size_t)k] ? 0 : 1;
-    }
-    // the select pass: deciding columns only, renumbered (its register use grows with the column count)
-    MScanCols &scols = b.scols;
-    MScanDesc *sdesc = b.sdesc.get();
-    b.renum.assign((size_t)cols.ncol, -1);
-    std::vector<int> &renum = b.renum;
-    for (int k = 0; k < cols.ncol; k++) {
-        if (cols.lazy[k]) continue;
-        const int j = scols.ncol++;
-        renum[(size_t)k] = j;
-        scols.ptr[j] = cols.ptr[k]; scols.width[j] = cols.width[k]; scols.filtered[j] = cols.filtered[k];
-        scols.lo[j] = cols.lo[k]; scols.hi[j] = cols.hi[k]; scols.kind[j] = cols.kind[k];
-        sdesc->flo[j] = d.flo[k]; sdesc->fhi[j] = d.fhi[k]; sdesc->dkind[j] = d.dkind[k]; sdesc->dn[j] = d.dn[k]; sdesc->dtests[j] = d.dtests[k];
-        scols.image |= ((cols.image >> k) & 1u) << j; scols.decode |= ((cols.decode >> k) & 1u) << j; scols.steps |= ((cols.steps >> k) & 1u) << j;
-        scols.limage |= ((cols.limage >> k) & 1u) << j;
-        sdesc->ibase[j] = d.ibase[k]; sdesc->iscale[j] = d.iscale[k];
-        if (d.dkind[k] == VC_FORM) {                          // its steps stay where they are in the pool; the tests' columns are
-            sdesc->dsrc[j] = d.dsrc[k]; sdesc->dsrc2[j] = d.dsrc2[k];      // renumbered (monotonic: they stay sorted by column)
-            for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dsrc2[k]; f++) {
-                sdesc->form[f] = d.form[f];
-                if (d.form[f].op == FormStep::LEAF) sdesc->form[f].col = renum[(size_t)d.form[f].col];
-            }
-            continue;
-        }
-        sdesc->dsrc[j] = d.dsrc[k] >= 0 ? renum[(size_t)d.dsrc[k]] : -1;
-        sdesc->dsrc2[j] = d.dsrc2[k] >= 0 ? renum[(size_t)d.dsrc2[k]] : -1;
-    }
-    scols.n = b.n;
-    // the take side decodes what it loads from an image (MsArgs::decode): its own filters and formula tests go back to the columns' values
-    const uint32_t sel_decode = cols.decode;
-    cols.decode = 0;
-    for (int k = 0; k < cols.ncol; k++) {
-        if (!(((cols.image | cols.limage) >> k) & 1u)) continue;       // (a lookup image too: decoded right after the lookup)
-        d.flo[k] = J.cols[(size_t)k].lo; d.fhi[k] = J.cols[(size_t)k].hi;
-        if (d.ibase[k] != 0 || d.iscale[k] != 1) cols.decode |= 1u << k;
-    }
-    bind_forms(J.cols, d);
-    // the take pass: one packed vector per produced column (statements that are the same column share it), and what those
-    // columns are derived from
-    // (`distinct` holds output codes: a column, or -2 - e for the row expression e the pass evaluates: ProjPlan::exprs)
-    for (int oc : J.node_col) if (oc != -1 && std::find(b.distinct.begin(), b.distinct.end(), oc) == b.distinct.end()) b.distinct.push_back(oc);
-    d.nout = (int)b.distinct.size();
-    d.take = 0;
-    d.nexpr = (int)J.exprs.size();
-    d.nkey = 0;
-    for (size_t e = 0; e < J.exprs.size(); e++) {
-        d.expr_at[e] = d.nkey; d.expr_len[e] = (int)J.exprs[e].size();
-        for (const KeyStep &st : J.exprs[e]) {
-            if (d.nkey >= kMaxKeySteps) throw Error(VDL_ERR_UNSUPPORTED, "internal: the front's expressions exceed the descriptor's step pool");
-            d.key[d.nkey++] = st;
-            if (st.kind == KeyStep::LOAD) d.take |= 1u << st.col;
-        }
-    }
-    for (size_t o = 0; o < b.distinct.size(); o++) { d.out_col[o] = b.distinct[o]; if (b.distinct[o] >= 0) d.take |= 1u << b.distinct[o]; }
-    for (int k = cols.ncol - 1; k >= 0; k--) {
-        if (!((d.take >> k) & 1u)) continue;
-        for (int src : J.cols[(size_t)k].sources()) d.take |= 1u << src;
-    }
-    // table columns both sides of the front read (they decide survival AND the outputs need them: the join index of a fact table whose
-    // dimension is filtered) stay in LDS for the survivors (MScanDesc::carry)
-    d.carry = 0; sdesc->carry = 0;
-    int taken = 0;
-    for (int k = 0; k < cols.ncol && taken < kMaxCarry; k++) {
-        if (cols.lazy[k] || cols.kind[k] != VC_DIRECT || !((d.take >> k) & 1u) || renum[(size_t)k] < 0) continue;
-        if (((cols.decode & ~sel_decode) >> k) & 1u) continue;       // the select side holds its encoded values: the take side loads it
-        d.carry |= 1u << k;
-        sdesc->carry |= 1u << renum[(size_t)k];
-        taken++;
-    }
-    uint32_t deciding = 0;
-    for (int k = 0; k < cols.ncol; k++) if (renum[(size_t)k] >= 0) deciding |= 1u << k;
-    p->image_roles["front.select"] = image_text(J.cols, cols, deciding);
-    p->image_roles["front.take"] = image_text(J.cols, cols, d.take);
-    p->step_roles["front.select"] = step_text(J.cols, cols, deciding);
-    p->step_roles["front.take"] = step_text(J.cols, cols, d.take);
-    p->lookup_roles["front.select"] = lookup_text(J.cols, cols, deciding);
-    p->lookup_roles["front.take"] = lookup_text(J.cols, cols, d.take);
-}
-// the prelude's tables of this run, in both passes' arguments
-static void patch_front(const vdl_plan *p, FrontBound &b) {
-    patch_prelude(p, p->fused.proj.cols, b.cols, *b.d);
-    for (int k = 0; k < b.cols.ncol; k++) {
-        if (b.renum[(size_t)k] < 0) continue;
-        b.scols.ptr[b.renum[(size_t)k]] = b.cols.ptr[k];
-        b.sdesc->dn[b.renum[(size_t)k]] = b.d->dn[k];
-    }
-}
-
 bool run_projection(vdl_ctx *c, vdl_plan *p, std::map<int, DVec> &over) {
     const ProjPlan &J = p->fused.proj;
     if (!J.ok || (p->use_fusion && p->fused.ok) || !p->use_fusion || getenv("VDL_NO_PROJECTION")) return false;
@@ -1685,30 +1234,18 @@ int vdl_plan_set_jit_bounds(vdl_plan *p, int at_run_time) {
 }
 void vdl_jit_counters(int64_t *compiled, int64_t *from_disk, int64_t *from_memory) { vdl::jit::counters(compiled, from_disk, from_memory); }
 const char *vdl_plan_jit_note(const vdl_plan *p) { return p ? p->jit_note.c_str() : ""; }
-int vdl_plan_image_columns(const vdl_plan *p, const char **list) {
+// "role: columns; role: columns" of the roles that have some, out of one of the three texts the plan keeps per role
+static int role_columns(const vdl_plan *p, const char **list, std::string vdl_plan::RoleColumns::*text, std::string &out) {
     if (!p || !list) return VDL_ERR_ARG;
-    p->image_list.clear();
-    for (const auto &r : p->image_roles)
-        if (!r.second.empty()) p->image_list += (p->image_list.empty() ? "" : "; ") + r.first + ": " + r.second;
-    *list = p->image_list.c_str();
+    out.clear();
+    for (const auto &r : p->roles)
+        if (!(r.second.*text).empty()) out += (out.empty() ? "" : "; ") + r.first + ": " + r.second.*text;
+    *list = out.c_str();
     return VDL_OK;
 }
-int vdl_plan_lookup_columns(const vdl_plan *p, const char **list) {
-    if (!p || !list) return VDL_ERR_ARG;
-    p->lookup_list.clear();
-    for (const auto &r : p->lookup_roles)
-        if (!r.second.empty()) p->lookup_list += (p->lookup_list.empty() ? "" : "; ") + r.first + ": " + r.second;
-    *list = p->lookup_list.c_str();
-    return VDL_OK;
-}
-int vdl_plan_step_columns(const vdl_plan *p, const char **list) {
-    if (!p || !list) return VDL_ERR_ARG;
-    p->step_list.clear();
-    for (const auto &r : p->step_roles)
-        if (!r.second.empty()) p->step_list += (p->step_list.empty() ? "" : "; ") + r.first + ": " + r.second;
-    *list = p->step_list.c_str();
-    return VDL_OK;
-}
+int vdl_plan_image_columns(const vdl_plan *p, const char **list) { return role_columns(p, list, &vdl_plan::RoleColumns::image, p->image_list); }
+int vdl_plan_lookup_columns(const vdl_plan *p, const char **list) { return role_columns(p, list, &vdl_plan::RoleColumns::lookup, p->lookup_list); }
+int vdl_plan_step_columns(const vdl_plan *p, const char **list) { return role_columns(p, list, &vdl_plan::RoleColumns::steps, p->step_list); }
 // Builds (hiprtc; no GPU needed) the specialised kernel of every multi-aggregate scan of the plan against the columns
 // registered now, without loading or running anything: the note lists each kernel with its code size, or why it failed.
 int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
@@ -1729,16 +1266,8 @@ int vdl_plan_jit_check(vdl_ctx *c, vdl_plan *p) {
                 if (!(semi || it.kind == PreludeItem::DIM_BITMAP) || !it.scan) continue;
                 MScanCols cols;
                 auto d = std::make_unique<MScanDesc>();
-                std::vector<char> unused(F.prelude.size(), 0);
-                const uint32_t pos = semi && it.index_col >= 0 && it.index_col < 32 ? 1u << it.index_col : 0u;
-                bind_vcols(c, it.table, it.cols, cols, *d, unused, pos);
-                const std::string role = (semi ? "semi" : "dim") + std::to_string(k);
-                p->image_roles[role] = image_text(it.cols, cols);
-                p->step_roles[role] = step_text(it.cols, cols);
-                p->lookup_roles[role] = lookup_text(it.cols, cols);
-                d->bitmap_only = semi ? 2 : 1;
-                if (semi) { d->pmin = it.modulus; d->nout = 1; d->out_col[0] = it.index_col; }
-                build_pass(c, p, role, select_pass(cols, *d, p->jit_rt_bounds), true);
+                bind_prelude_scan(c, p, k, cols, *d);
+                build_pass(c, p, (semi ? "semi" : "dim") + std::to_string(k), select_pass(cols, *d, p->jit_rt_bounds), true);
             }
             FrontBound fb;
             bind_front(c, p, fb);

@@ -349,16 +349,13 @@ struct vdl_plan {
     std::string batch_note;                  // what the last vdl_run_batch / vdl_batch_jit_check did with this plan ("" after a plain vdl_run)
     size_t batch_code_bytes = 0;             // the code size of the batch kernel that served the plan in that call, 0 = none did
     bool batch_words = false;                // vdl_run_batch: n_words / word_offset are set for a finalisation although the plan is not bound
-    // by scan role ("scan<k>", "front.select", "front.take", "dim<k>", "semi<k>"): the catalog columns the scan bound last read from their
-    // images, "name:width ..." (vdl_plan_image_columns); roles without one hold ""
-    std::map<std::string, std::string> image_roles;
-    mutable std::string image_list;          // what vdl_plan_image_columns handed out last
-    // likewise the columns read from their step images, "name:s ..." (vdl_plan_step_columns): such a column is not in image_roles
-    std::map<std::string, std::string> step_roles;
-    // ... and the target columns its lookups read from their images, "name:width ..." (vdl_plan_lookup_columns): not in image_roles either
-    std::map<std::string, std::string> lookup_roles;
-    mutable std::string lookup_list;
-    mutable std::string step_list;
+    // by scan role ("scan<k>", "front.select", "front.take", "dim<k>", "semi<k>"), of the scan bound last (note_roles): the catalog
+    // columns it read from their byte or packed images, "name:width ..." (vdl_plan_image_columns); those it read from their step
+    // images, "name:s ..." (vdl_plan_step_columns); the target columns its lookups read from their images, "name:width ..."
+    // (vdl_plan_lookup_columns).  A column is in one of the three at most; a role without any holds ""
+    struct RoleColumns { std::string image, steps, lookup; };
+    std::map<std::string, RoleColumns> roles;
+    mutable std::string image_list, step_list, lookup_list;      // what the three entry points handed out last
     std::vector<BufP> prelude_buf;           // fused join scans: dimension bitmaps / LIKE tables of the current run (FusedPlan::prelude)
     std::vector<int64_t> prelude_n;
     std::vector<int64_t> prelude_rows;       // SEMI_BITMAP items: rows of the (local) source table the set was built from
@@ -521,15 +518,31 @@ inline const Column &find_col(vdl_ctx *c, const std::string &name) {
 }
 
 std::string describe_plan(const vdl_plan *p);
-// vdl_engine.cpp, for vdl_specialise.cpp: a scan's binding (packed: 0 = byte images only; 1 = the filter columns from their bit-packed
-// images, 2 = every table column that has one; instantiated there for ScanPlan and GroupScanPlan), which scans the hand-tuned k_scan
-// serves, and a binding's entry in vdl_plan_image_columns
-template <typename PlanT>
-int64_t bind_mscan(vdl_ctx *c, const PlanT &sp, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0, int packed = 0);
-bool use_kscan(const ScanPlan &sp);
-std::string image_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
-std::string step_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
-std::string lookup_text(const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
+// ---- binding (vdl_bind.cpp): planned scans and catalog columns into kernel arguments; every one returns the scanned table's row count ----
+const std::vector<ScanColumn> &scan_columns(const vdl_plan *p, size_t s);      // of fused scan s: the global scans first, then the grouped ones
+// fused scan s for k_mscan and the specialised scans (packed: 0 = byte images only; 1 = the filter columns from their bit-packed
+// images, 2 = every table column that has one)
+int64_t bind_scan(vdl_ctx *c, const vdl_plan *p, size_t s, MScanCols &cols, MScanDesc &d, int64_t *bytes_per_row, int64_t row0, int packed = 0);
+bool use_kscan(const ScanPlan &sp);                                             // the scans the hand-tuned single-aggregate k_scan serves
+int64_t bind_kscan(vdl_ctx *c, const ScanPlan &sp, ScanArgs &a, int64_t *bytes_per_row);
+// the prelude's dimension or semi-join scan k, with its entry in the plan's roles; patch_prelude: the prelude's tables of this run
+// into the arguments of a scan that looks them up
+int64_t bind_prelude_scan(vdl_ctx *c, vdl_plan *p, size_t k, MScanCols &cols, MScanDesc &d);
+void patch_prelude(const vdl_plan *p, const std::vector<ScanColumn> &sc, MScanCols &cols, MScanDesc &d);
+// What is known of the fused front (ProjPlan, vdl_fuse.h) before anything runs: the columns of both sides (the select side sees only
+// the columns that decide a row's survival, renumbered), which columns the take side needs and which it writes, and the prelude's
+// items it looks up (wanted).  Pointers and sizes of the prelude's tables are patched in once they exist (patch_front).
+struct FrontBound {
+    MScanCols cols, scols;
+    std::unique_ptr<MScanDesc> d = std::make_unique<MScanDesc>(), sdesc = std::make_unique<MScanDesc>();
+    std::vector<int> renum, distinct;
+    std::vector<char> wanted;
+    int64_t n = 0;
+};
+void bind_front(vdl_ctx *c, vdl_plan *p, FrontBound &b);
+void patch_front(const vdl_plan *p, FrontBound &b);
+// a bound scan's entry in the plan's roles: of the columns in `which`, what it reads from which images
+void note_roles(vdl_plan *p, const std::string &role, const std::vector<ScanColumn> &sc, const MScanCols &cols, uint32_t which = ~0u);
 // Sharded entry points and a plan with an order set.  merges = the entry point runs the collectives itself (vdl_run_sharded*): it
 // accepts the plan once vdl_plan_set_order_sharded has switched the merged order on.  The others (vdl_run_local, vdl_exchange_begin)
 // leave the collectives to their caller and refuse it either way -- except inside vdl_run_sharded's own calls (order_inside).

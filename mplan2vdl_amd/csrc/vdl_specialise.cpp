@@ -45,10 +45,6 @@ static std::string jit_name(const jit::Shape &sh, const MScanCols &cols) {
 // 5 | 6: the packed form, at 2 row pairs per slice unless VDL_JIT_U says otherwise)
 static ScanForm form_asked_for() { return getenv("VDL_JIT_LATE") ? ScanForm::from_code(std::max(1, atoi(getenv("VDL_JIT_LATE")))) : ScanForm{}; }
 
-static const std::vector<ScanColumn> &scan_columns(const vdl_plan *p, size_t s) {
-    const size_t ns = p->fused.scans.size();
-    return s < ns ? p->fused.scans[s].cols : p->fused.gscans[s - ns].cols;
-}
 // a column's name without its table
 static std::string short_name(const std::string &name) { return name.substr(name.find('.') == std::string::npos ? 0 : name.find('.') + 1); }
 // "l_discount@1 l_quantity@2 l_extendedprice@last": which table columns a staged scan reads when (MsArgs::stages)
@@ -178,7 +174,7 @@ static bool bind_form(vdl_ctx *c, const vdl_plan *p, size_t s, bool grouped, con
     MScanCols &pc = *out.own_cols;
     MScanDesc &pd = *out.own_desc;
     int64_t bpr = 0;
-    bind_mscan(c, sp, pc, pd, &bpr, p->row_offset, f.every_column ? 2 : 1);
+    bind_scan(c, p, s, pc, pd, &bpr, p->row_offset, f.every_column ? 2 : 1);
     pd.block_partials = d.block_partials;
     pd.wide = d.wide;
     out.cols = &pc;
@@ -354,7 +350,7 @@ void tune_specialised(vdl_ctx *c, vdl_plan *p, int64_t *dev_words) {
         if (p->mjit_form[s].kind == ScanForm::PACKED) {
             plain_desc = std::make_unique<MScanDesc>();
             int64_t bpr = 0;
-            bind_mscan(c, p->fused.scans[s], plain_cols, *plain_desc, &bpr, p->row_offset);
+            bind_scan(c, p, s, plain_cols, *plain_desc, &bpr, p->row_offset);
             plain_desc->block_partials = p->mdesc[s].block_partials;
             plain_desc->wide = p->mdesc[s].wide;
             cols = &plain_cols;
@@ -475,11 +471,9 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
         MScanCols cols;
         auto d = std::make_unique<MScanDesc>();
         int64_t bpr = 0;
-        if (grouped) bind_mscan(c, F.gscans[s - ns], cols, *d, &bpr, 0);
-        else bind_mscan(c, F.scans[s], cols, *d, &bpr, 0);
+        bind_scan(c, p, s, cols, *d, &bpr, 0);
         d->wide = p->wide ? 1 : 0;                                   // (the wide units build without a device like the others)
-        p->image_roles["scan" + std::to_string(s)] = image_text(scan_columns(p, s), cols);
-        p->lookup_roles["scan" + std::to_string(s)] = lookup_text(scan_columns(p, s), cols);
+        note_roles(p, "scan" + std::to_string(s), scan_columns(p, s), cols);
         const ScanLaunch cfg = mscan_launch_config(cols, *d, grouped, c->num_cus);
         if (cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no scan kernel variant for this shape");
         // the staged, queue or packed form of the same scan (VDL_JIT_LATE as in specialise_scan), refused where the tuner refuses it
@@ -516,19 +510,12 @@ std::string batch_alone_reason(const vdl_plan *p, bool grouped_on) {
     if (!p->use_jit) return "specialisation is off";
     const FusedPlan &F = p->fused;
     if (!F.gscans.empty() && !grouped_on) return "grouped scans are not batched";
-    if (!F.gscans.empty()) {
-        if (F.gscans.size() + F.scans.size() != 1) return "the plan has " + std::to_string(F.gscans.size() + F.scans.size()) + " scans, a batch shares exactly one";
-        if (!F.prelude.empty()) return "scans with lookup tables or semi-join sets are not batched";
-        for (const ScanColumn &sc : F.gscans[0].cols)
-            if (sc.kind != VC_DIRECT) return "scans with derived columns are not batched";
-        if (F.gscans[0].never) return "its filters can hold for no row: there is nothing to scan";
-        return "";
-    }
-    if (F.scans.size() != 1) return "the plan has " + std::to_string(F.scans.size()) + " scans, a batch shares exactly one";
+    const size_t nscans = F.scans.size() + F.gscans.size();
+    if (nscans != 1) return "the plan has " + std::to_string(nscans) + " scans, a batch shares exactly one";
     if (!F.prelude.empty()) return "scans with lookup tables or semi-join sets are not batched";
-    for (const ScanColumn &sc : F.scans[0].cols)
+    for (const ScanColumn &sc : scan_columns(p, 0))
         if (sc.kind != VC_DIRECT) return "scans with derived columns are not batched";
-    if (F.scans[0].never) return "its filters can hold for no row: there is nothing to scan";
+    if (F.gscans.empty() ? F.scans[0].never : F.gscans[0].never) return "its filters can hold for no row: there is nothing to scan";
     return "";
 }
 int batch_cap(int nagg) { return std::min(kMaxBatch, kMaxBatchWords / (1 + std::max(nagg, 0))); }
@@ -570,8 +557,7 @@ void batch_bind(vdl_ctx *c, vdl_plan *p, BatchMember &m) {
     m.desc = std::make_shared<MScanDesc>();
     int64_t bpr = 0;
     m.grouped = !p->fused.gscans.empty();
-    if (m.grouped) bind_mscan(c, p->fused.gscans[0], m.cols, *m.desc, &bpr, p->row_offset);
-    else bind_mscan(c, p->fused.scans[0], m.cols, *m.desc, &bpr, p->row_offset);
+    bind_scan(c, p, 0, m.cols, *m.desc, &bpr, p->row_offset);      // (a batched plan has exactly one scan: batch_alone_reason)
     m.cfg = mscan_launch_config(m.cols, *m.desc, m.grouped, c->num_cus);      // (grouped: the key's canonical form and the replicas the scan has alone)
     m.replicas_alone = m.desc->replicas;
     if (m.cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no multi-aggregate scan kernel variant for this shape");

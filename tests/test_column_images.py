@@ -1,4 +1,4 @@
-"""Frame-of-reference column images on the GPU (csrc/vdl_column_image.h, vdl_image.hip, bind_mscan): aggregate scans that read
+"""Frame-of-reference column images on the GPU (csrc/vdl_column_image.h, vdl_image.hip, bind_scan): aggregate scans that read
 the narrow images instead of the catalog columns give the oracle's answers bit for bit -- Q6, Q1, every compiled TPC-H plan and
 random fused programs, with images on and off, precompiled and specialised, one GPU and sharded -- and the census of a staged
 scan over images counts the lines of the image widths."""

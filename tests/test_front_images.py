@@ -1,4 +1,4 @@
-"""Column images read by the scans with derived columns (bind_vcols, project_front_body, project_select_body): fused fronts,
+"""Column images read by the scans with derived columns (csrc/vdl_bind.cpp, project_front_body, project_select_body): fused fronts,
 dimension scans and semi-join scans over encoded columns give the oracle's answers bit for bit -- Q3 over the columns the benchmark
 registers, every compiled TPC-H plan, random front / join / semi-join programs over columns shaped to break a wrong decode, sharded
 runs, the pipe end (`vdlrun --encode`) -- with images on and off, precompiled and specialised, and Plan.image_columns() names what

@@ -160,7 +160,7 @@ def _build(tmp_path, sanitize):
 
 def test_lookup_rules_match_brute_force_under_sanitizers(tmp_path):
     """widths 1 / 2, bases -3 .. 3, scales 1, 10, 1000: map_range followed by a lookup of e admits exactly the rows whose decoded
-    value lies in [lo, hi], compose gives the factor's value mod 2^64, and lookup_use / lookup_use_in_vscan say what the comments do"""
+    value lies in [lo, hi], compose gives the factor's value mod 2^64, and use_in_aggregate / use_in_vscan say what the comments do"""
     exe = _build(tmp_path, True) or _build(tmp_path, False)       # (a compiler without the sanitizer runtimes still checks the rules)
     assert exe, "the checker of the lookup rules does not build"
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")

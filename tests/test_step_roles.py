@@ -1,5 +1,5 @@
 """Step images decoded in every scan role and at both sum widths (vdl_mscan_body.h: step_tile through load_tile, the partial-tile
-branches of project_select_body and project_front_body, step_load on the front's take side; vdl_engine.cpp: bind_vcols' choice of a
+branches of project_select_body and project_front_body, step_load on the front's take side; vdl_bind.cpp: the binder's choice of a
 32- or 64-bit sum, bind_front's renumbered select descriptor).  Every comparison is exact: the reference is the oracle on the same
 program text and the same host columns, and for a column read straight back, the numpy column.  The programs, their tables and the
 floors that keep a role from passing unexercised are in tests/test_step_roles_cpu.py, which checks them without a device."""

@@ -1,7 +1,7 @@
 """Step images in every scan role, without a GPU (tests/test_step_roles.py runs the same programs on one).  This file holds what
 both share -- the hand-written front over synthetic tables, the random generators in their stepped mode, the compiled plans'
 catalogs -- and the checks a device-less engine can make: a step image declared on it (Engine.declare_steps) is bound by the very
-binder a run uses (bind_vcols, bind_front through Plan.jit_check), so Plan.step_columns() says which scan role of which program
+binder a run uses (csrc/vdl_bind.cpp: bind_prelude_scan, bind_front through Plan.jit_check), so Plan.step_columns() says which scan role of which program
 would decode one.  That is what keeps the GPU tests from passing vacuously: the floors below are conditions on the programs."""
 import os
 import re
@@ -38,7 +38,7 @@ def qualifies(v):
 
 
 def sum_width(v):
-    """the width bind_vcols gives a stepped column: 4 where base .. base + n - 1 fits 32 signed bits, else 8"""
+    """the width the binder gives a stepped column: 4 where base .. base + n - 1 fits 32 signed bits, else 8"""
     return 4 if I32_MIN <= int(v[0]) <= I32_MAX - len(v) else 8
 
 

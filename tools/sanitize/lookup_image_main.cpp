@@ -1,4 +1,4 @@
-// lookup_image_main.cpp -- the rules for lookup images (vdl_column_image.h: lookup_use, lookup_use_in_vscan, and map_range / compose
+// lookup_image_main.cpp -- the rules for lookup images (vdl_column_image.h: use_in_aggregate, use_in_vscan, and map_range / compose
 // applied to a looked-up value) against brute force over small images; built with ASan + UBSan by tests/test_lookup_images_cpu.py.
 //
 // A dimension table of every encoded value e the image's width holds (1 byte: all 256; 2 bytes: a band around both ends and zero),
@@ -34,20 +34,18 @@ int main() {
                 im.width = width; im.base = base; im.scale = scale;
                 // ---- the use rules
                 for (int raw = 0; raw <= 1; raw++) {
-                    const LookupUse u = lookup_use(im, raw != 0);
+                    const Use u = use_in_aggregate(im, raw != 0);
                     const bool want = im.pure() || !raw;
-                    if ((u != LOOKUP_CATALOG) != want || u == LOOKUP_DECODED) fail("lookup_use", im, raw, u, 0);
-                    if ((u != LOOKUP_CATALOG) != usable(im, raw != 0)) fail("lookup_use vs usable", im, raw, u, 0);
-                    const LookupUse v = lookup_use_in_vscan(im, raw != 0);
+                    if ((u != USE_CATALOG) != want || u == USE_DECODED) fail("use_in_aggregate", im, raw, u, 0);
+                    const Use v = use_in_vscan(im, raw != 0);
                     const bool wantv = scale == 1 || !raw;
-                    if ((v != LOOKUP_CATALOG) != wantv) fail("lookup_use_in_vscan", im, raw, v, 0);
-                    if ((v != LOOKUP_CATALOG) != usable_in_vscan(im, raw != 0)) fail("lookup_use_in_vscan vs usable_in_vscan", im, raw, v, 0);
-                    if (wantv && (v == LOOKUP_DECODED) != (raw && !im.pure())) fail("decoded exactly when needed per row and not pure", im, raw, v, 0);
-                    if (v == LOOKUP_DECODED && scale != 1) fail("a per-row decode costs an add", im, raw, v, 0);
-                    checks += 6;
+                    if ((v != USE_CATALOG) != wantv) fail("use_in_vscan", im, raw, v, 0);
+                    if (wantv && (v == USE_DECODED) != (raw && !im.pure())) fail("decoded exactly when needed per row and not pure", im, raw, v, 0);
+                    if (v == USE_DECODED && scale != 1) fail("a per-row decode costs an add", im, raw, v, 0);
+                    checks += 4;
                 }
                 Image none;
-                if (lookup_use(none, false) != LOOKUP_CATALOG || lookup_use_in_vscan(none, false) != LOOKUP_CATALOG) fail("no image", none, 0, 0, 0);
+                if (use_in_aggregate(none, false) != USE_CATALOG || use_in_vscan(none, false) != USE_CATALOG) fail("no image", none, 0, 0, 0);
                 // ---- the dimension table and its image
                 std::vector<int64_t> column, image;
                 for (int64_t e : es) { image.push_back(e); column.push_back(decode(im, e)); }
