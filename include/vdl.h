@@ -324,6 +324,33 @@ int  vdl_plan_wide_sums(const vdl_plan *plan);
 int  vdl_output_high(const vdl_plan *plan, int k, const int64_t **hi, size_t *n);
 const char *vdl_plan_wide_note(const vdl_plan *plan);
 int  vdl_wide_eval_bin(int op, int64_t alo, int64_t ahi, int64_t blo, int64_t bhi, int64_t *lo, int64_t *hi);
+/* ---- wide sums in the GROUP BY tail and the per-operator folds ----
+ * vdl_plan_set_wide_sums_tail(plan, on): with on != 0 and vdl_plan_set_wide_sums at 1 or 2, vdl_run also serves the plans the switch
+ * above refuses on ONE GPU: a plan that does not fuse as a whole (a fused front or a semi-join set, then the GROUP BY tail), a plan
+ * whose fusion is off, and the statement-by-statement rerun of a fused plan whose rows carry keys outside the pivots.  Off by default
+ * (VDL_WIDE_TAIL=1 sets it at vdl_parse; vdl_plan_set_wide_sums(plan, 0) clears it, and on a plan in mode 0 the call leaves it off);
+ * with it off every refusal is what it was.  The
+ * sharded entry points refuse such a plan whatever this switch says.
+ *   - A FoldSum result is the exact two's-complement sum of its int64 per-entry terms (the term itself still wraps); bits 0..63 are
+ *     bit for bit the switch-off result.  A fold over more than 2^31 entries is refused with VDL_ERR_UNSUPPORTED naming the count.
+ *   - Wide where delivered: a wide sum that reaches an output through Project / Shuffle / MaterializeCompact carries its high words
+ *     to vdl_output_high; every other output's high words are the sign extension.  Mode 2 checks the delivered values as above.
+ *   - Checked where consumed: a wide sum read by any other statement (an element-wise operator, another fold, Gather, Scatter,
+ *     Partition; a RangeV only takes its shape and does not count) must fit int64 in EITHER mode: if not, the run fails with
+ *     VDL_ERR_OVERFLOW naming the consuming statement's id and operator, the first offending position and the exact value, and
+ *     delivers nothing.  The checks' flags are read once, when the run ends.
+ *   - With an order set the device order step permutes and cuts the high vectors with the low ones; a key output whose value does
+ *     not fit int64 fails the run with VDL_ERR_OVERFLOW naming the key.
+ *   - vdl_output_high_device: under vdl_plan_set_device_outputs, the high words of an output that stayed in HBM (beside
+ *     vdl_output_device's pointer; vdl_output_high then hands out NULL for it); *dev_hi is NULL, with VDL_OK, for an output that is
+ *     on the host or of a run without wide sums.
+ *   - vdl_plan_wide_note names the route ("tail: k_group_fold ...").
+ * vdl_wide_join_halves: the join of the two half sums the folds accumulate -- sl = the sum of the terms' low 32 bits (0 <= sl < 2^63),
+ * sh = the sum of their arithmetic high halves (|sh| < 2^62) -- into bits 0..63 and 64..127 of sh * 2^32 + sl; host only. */
+int  vdl_plan_set_wide_sums_tail(vdl_plan *plan, int on);
+int  vdl_plan_wide_sums_tail(const vdl_plan *plan);
+int  vdl_output_high_device(const vdl_plan *plan, int k, const int64_t **dev_hi, size_t *n);
+int  vdl_wide_join_halves(int64_t sl, int64_t sh, int64_t *lo, int64_t *hi);
 int  vdl_n_timings(const vdl_plan *plan);
 int  vdl_timing(const vdl_plan *plan, int k, const char **label, double *usec);
 

@@ -95,6 +95,10 @@ def load():
         "vdl_plan_set_wide_sums_sharded": (i32, [vp, i32]),
         "vdl_plan_wide_sums_sharded": (i32, [vp]),
         "vdl_output_high": (i32, [vp, i32, P(P(i64)), P(ctypes.c_size_t)]),
+        "vdl_plan_set_wide_sums_tail": (i32, [vp, i32]),
+        "vdl_plan_wide_sums_tail": (i32, [vp]),
+        "vdl_output_high_device": (i32, [vp, i32, P(P(i64)), P(ctypes.c_size_t)]),
+        "vdl_wide_join_halves": (i32, [i64, i64, P(i64), P(i64)]),
         "vdl_plan_wide_note": (cp, [vp]),
         "vdl_wide_eval_bin": (i32, [i32, i64, i64, i64, i64, P(i64), P(i64)]),
         "vdl_plan_set_order": (i32, [vp, i32, P(cp), P(i32), i64]),
@@ -160,6 +164,7 @@ ABI_SYMBOLS = [
     "vdl_run_sharded_begin", "vdl_run_sharded_end", "vdl_comm_merge_host",
     "vdl_plan_set_wide_sums", "vdl_plan_wide_sums", "vdl_output_high", "vdl_plan_wide_note", "vdl_wide_eval_bin",
     "vdl_plan_set_wide_sums_sharded", "vdl_plan_wide_sums_sharded", "vdl_comm_merge_host_wide",
+    "vdl_plan_set_wide_sums_tail", "vdl_plan_wide_sums_tail", "vdl_output_high_device", "vdl_wide_join_halves",
 ]
 
 

@@ -579,8 +579,9 @@ std::string wide_decimal(int64_t lo, int64_t hi) {
 }
 // the first value of output o whose high word is not the sign extension of its low word: -1 = every value fits int64
 static int64_t wide_first_overflow(const Output &o) {
-    if (!o.has_hi) return -1;
-    for (size_t i = 0; i < o.vals.size() && i < o.hi.size(); i++) if (o.hi[i] != (o.vals[i] >> 63)) return (int64_t)i;
+    const int64_t *lo = o.ptr(), *hi = o.hi_ptr();             // (an output kept in HBM was checked there: GenExec::copy_out_hi)
+    if (!lo || !hi) return -1;
+    for (size_t i = 0; i < o.count(); i++) if (hi[i] != (lo[i] >> 63)) return (int64_t)i;
     return -1;
 }
 // checked sums (mode 2): the run fails on the first such value, and delivers nothing
@@ -589,7 +590,7 @@ void wide_check_outputs(vdl_plan *p) {
         const int64_t i = wide_first_overflow(o);
         if (i < 0) continue;
         const std::string msg = "checked sums: output '" + o.name + "' (" + o.tmp + "), group " + std::to_string(i) + ": the exact value " +
-                                wide_decimal(o.vals[(size_t)i], o.hi[(size_t)i]) + " does not fit int64 (vdl_plan_set_wide_sums(plan, 1) delivers it as two words)";
+                                wide_decimal(o.ptr()[(size_t)i], o.hi_ptr()[(size_t)i]) + " does not fit int64 (vdl_plan_set_wide_sums(plan, 1) delivers it as two words)";
         p->outs.clear();
         throw Error(VDL_ERR_OVERFLOW, msg);
     }
@@ -603,7 +604,7 @@ void order_outputs_on_host(vdl_ctx *c, vdl_plan *p) {
         const int64_t i = wide_first_overflow(p->outs[k]);
         if (i < 0) continue;
         const std::string msg = "wide sums: the order key '" + p->outs[k].name + "' (" + p->outs[k].tmp + ") holds, in group " + std::to_string(i) + ", the exact value " +
-                                wide_decimal(p->outs[k].vals[(size_t)i], p->outs[k].hi[(size_t)i]) + ", which does not fit the int64 that keys are compared as";
+                                wide_decimal(p->outs[k].ptr()[(size_t)i], p->outs[k].hi_ptr()[(size_t)i]) + ", which does not fit the int64 that keys are compared as";
         p->outs.clear();
         throw Error(VDL_ERR_OVERFLOW, msg);
     }
@@ -648,8 +649,10 @@ void order_outputs_on_host(vdl_ctx *c, vdl_plan *p) {
         o.big = nullptr; o.big_n = 0;
         if (o.has_hi) {                                        // wide sums: the high words go with their low words
             std::vector<int64_t> cut_hi((size_t)L);
-            for (int64_t i = 0; i < L; i++) cut_hi[(size_t)i] = o.hi[(size_t)index[(size_t)i]];
+            const int64_t *src_hi = o.big_hi ? o.big_hi : o.hi.data();
+            for (int64_t i = 0; i < L; i++) cut_hi[(size_t)i] = src_hi[(size_t)index[(size_t)i]];
             o.hi.swap(cut_hi);
+            o.big_hi = nullptr;
         }
     }
     p->order_note = "host m=" + std::to_string(m) + " rows=" + std::to_string(L);
@@ -1193,6 +1196,7 @@ int vdl_parse(vdl_ctx *c, const char *text, size_t len, vdl_plan **out) {
         { const char *b = getenv("VDL_JIT_BOUNDS"); p->jit_rt_bounds = b && strcmp(b, "runtime") == 0; }
         { const char *w = getenv("VDL_WIDE_SUMS"); p->wide = w && (strcmp(w, "1") == 0 || strcmp(w, "2") == 0) ? atoi(w) : 0; }
         { const char *w = getenv("VDL_WIDE_SHARDED"); p->wide_sharded = w && strcmp(w, "1") == 0; }
+        { const char *w = getenv("VDL_WIDE_TAIL"); p->wide_tail = p->wide && w && strcmp(w, "1") == 0; }
         p->description = describe_plan(p.get());
         *out = p.release();
     });
@@ -1388,7 +1392,25 @@ int vdl_plan_set_wide_sums(vdl_plan *p, int mode) {
         p->wide_note.clear();
     }
     p->wide = mode;
-    if (mode == 0) p->wide_sharded = false;                    // (the sharded switch says how a WIDE plan is sharded: it goes with the mode)
+    if (mode == 0) p->wide_sharded = p->wide_tail = false;     // (the sharded and tail switches say how a WIDE plan runs: they go with the mode)
+    return VDL_OK;
+}
+int vdl_plan_set_wide_sums_tail(vdl_plan *p, int on) {
+    if (!p) return VDL_ERR_ARG;
+    p->wide_tail = p->wide != 0 && on != 0;                   // (it says how a WIDE plan runs: in mode 0 there is nothing to switch)
+    return VDL_OK;
+}
+int vdl_plan_wide_sums_tail(const vdl_plan *p) { return p && p->wide_tail ? 1 : 0; }
+int vdl_output_high_device(const vdl_plan *p, int k, const int64_t **dev_hi, size_t *n) {
+    if (!p || k < 0 || k >= (int)p->outs.size()) return VDL_ERR_ARG;
+    const Output &o = p->outs[(size_t)k];
+    if (dev_hi) *dev_hi = o.has_hi && o.dev ? o.dev_hi : nullptr;
+    if (n) *n = o.count();
+    return VDL_OK;
+}
+int vdl_wide_join_halves(int64_t sl, int64_t sh, int64_t *lo, int64_t *hi) {
+    if (!lo || !hi) return VDL_ERR_ARG;
+    wide_join_halves(sl, sh, lo, hi);
     return VDL_OK;
 }
 int vdl_plan_wide_sums(const vdl_plan *p) { return p ? p->wide : 0; }
@@ -1401,7 +1423,7 @@ int vdl_plan_wide_sums_sharded(const vdl_plan *p) { return p && p->wide_sharded 
 int vdl_output_high(const vdl_plan *p, int k, const int64_t **hi, size_t *n) {
     if (!p || k < 0 || k >= (int)p->outs.size()) return VDL_ERR_ARG;
     const Output &o = p->outs[(size_t)k];
-    if (hi) *hi = o.has_hi ? o.hi.data() : nullptr;
+    if (hi) *hi = o.hi_ptr();
     if (n) *n = o.count();
     return VDL_OK;
 }
@@ -1468,7 +1490,7 @@ static int run_plan(vdl_ctx *c, vdl_plan *p, const std::string *abandoned) {
             } catch (const NeedGeneralPath &e) {
                 p->fallback_note = e.what();          // exact for any data: rerun statement by statement
             }
-            if (p->wide) {
+            if (p->wide && !p->wide_tail) {
                 const std::string why = "wide sums are on, and this run of the fused plan cannot stand: " + p->fallback_note + ".  The statement-by-statement rerun computes its sums with "
                                         "k_group_fold / k_seg_fold / k_fold_global, which have no wide form; clear the switch (vdl_plan_set_wide_sums(plan, 0)) to run it";
                 p->wide_note = "refused: " + why;
@@ -1487,9 +1509,14 @@ static int run_plan(vdl_ctx *c, vdl_plan *p, const std::string *abandoned) {
         } else front = run_projection(c, p, over);
         GenExec g(c, p);
         g.ordering = p->order.set;
+        g.wide_on = p->wide != 0 && p->wide_tail && !p->after_front;      // (a wide plan without the tail switch was refused above)
         g.run_nodes(p->prog.outputs, front ? &over : nullptr);
         if (front) p->timings.push_back({p->front_note, p->front_usec});
         if (!p->fallback_note.empty()) { p->timings.push_back({"fusedPlanAbandoned: " + p->fallback_note, 0.0}); p->fallback_note.clear(); }
+        if (g.wide_on) {
+            p->wide_note = g.wide_note();
+            if (p->wide == 2) wide_check_outputs(p);           // (outputs on the host; those kept in HBM were checked there)
+        }
     });
 }
 

@@ -156,6 +156,9 @@ struct DVec {
     BufP keep;                  // COLUMN: keeps an engine-owned column alive
     BufP sorted_keys, sorted_keys_src;   // with `order`: the partitioned values themselves in rank order, and the buffer they are the values of
                                 // (a Scatter of that very vector by these positions -- the key of a GROUP BY -- is then already written)
+    BufP hi;                    // wide sums in the tail (vdl_plan_set_wide_sums_tail): the values are exact sums and this holds their bits 64..127, laid out as
+                                // `data` is (SPARSE: the entries; DENSE: the slots; ONEHOT: one word).  Carried by Project / Shuffle / MaterializeCompact;
+                                // any other reader checks that the values fit int64 and drops it (GenExec::wide_consume)
     BufP order;                 // Partition positions whose only readers are Scatters: the slots in RANK order (order[pos[slot]] = slot); `data` (the
                                 // positions themselves) is filled in only if somebody asks (GenExec::need_positions)
 };
@@ -182,6 +185,11 @@ struct Output {
     size_t big_n = 0;
     std::shared_ptr<void> dev_keep;    // vdl_plan_set_device_outputs: large results stay in HBM, owned by the plan until its next run
     const int64_t *dev = nullptr;
+    // the high words where the low ones are: pinned (big_hi) beside `big`, in HBM (dev_hi, vdl_output_high_device) beside `dev`, else `hi`
+    const int64_t *big_hi = nullptr;
+    std::shared_ptr<void> dev_hi_keep;
+    const int64_t *dev_hi = nullptr;
+    const int64_t *hi_ptr() const { return !has_hi || dev ? nullptr : big_hi ? big_hi : hi.data(); }
     const int64_t *ptr() const { return dev ? nullptr : big ? big : vals.data(); }
     size_t count() const { return (dev || big) ? big_n : vals.size(); }
 };
@@ -287,6 +295,9 @@ struct vdl_plan {
     // are written on the engine's stream ahead of the event the gather waits for, and no buffer is shared between two queries in
     // flight); wide_hi_src is what finalize_begin copies instead of wide_hi (the slot's MERGED high words)
     bool wide_sharded = false, wide_inside = false;
+    // vdl_plan_set_wide_sums_tail: vdl_run also serves a wide plan whose sums run through the per-operator folds (a GROUP BY tail behind a
+    // fused front, fusion off, the rerun of a fused plan that found keys outside the pivots); the sharded entry points refuse as ever
+    bool wide_tail = false;
     int64_t *wide_hi_out = nullptr;
     const int64_t *wide_hi_src = nullptr;
     // the high words of a finalisation in flight: one pinned buffer per slot beside host_words, slot_wide = the slot's run made them
@@ -436,10 +447,11 @@ struct vdl_plan {
     const void *ev_buf[kEvRing] = {};   // partial-word buffer each event pair's run wrote (pipelined callers finalise out of order)
     int slot_ev_idx[2] = {-1, -1};
     // pinned result buffers of the general path, one per output ordinal, grown on demand
-    std::vector<std::pair<int64_t *, size_t>> out_pinned;
-    int64_t *pinned_out(size_t ordinal, size_t count) {
-        if (out_pinned.size() <= ordinal) out_pinned.resize(ordinal + 1, {nullptr, 0});
-        auto &b = out_pinned[ordinal];
+    std::vector<std::pair<int64_t *, size_t>> out_pinned, out_pinned_hi;      // (_hi: the outputs' high words, wide sums in the tail)
+    int64_t *pinned_out(size_t ordinal, size_t count, bool high = false) {
+        std::vector<std::pair<int64_t *, size_t>> &pins = high ? out_pinned_hi : out_pinned;
+        if (pins.size() <= ordinal) pins.resize(ordinal + 1, {nullptr, 0});
+        auto &b = pins[ordinal];
         if (b.second < count) {
             if (b.first) (void)hipHostFree(b.first);
             b.first = nullptr; b.second = 0;
@@ -450,6 +462,7 @@ struct vdl_plan {
     }
     ~vdl_plan() {
         for (auto &b : out_pinned) if (b.first) (void)hipHostFree(b.first);
+        for (auto &b : out_pinned_hi) if (b.first) (void)hipHostFree(b.first);
         for (hipEvent_t e : stmt_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : order_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : merge_ev) if (e) (void)hipEventDestroy(e);
@@ -560,6 +573,7 @@ inline void refuse_order_sharded(const vdl_plan *p, bool merges = false) {
 // are; else the reason vdl_run refuses it with, naming the route its sums would take
 inline std::string wide_refusal(const vdl_plan *p) {
     if (!p->wide) return "";
+    if (p->wide_tail) return "";                               // (vdl_plan_set_wide_sums_tail: the per-operator folds deliver wide sums too)
     if (!p->fused.ok)
         return "wide sums are on for this plan (vdl_plan_set_wide_sums), but it does not fuse as a whole into aggregate scans (" + p->fused.why_not + "): " +
                (p->fused.proj.ok ? "its fused front feeds a GROUP BY tail whose sums run through k_group_fold / k_seg_fold"

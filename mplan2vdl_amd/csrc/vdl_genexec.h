@@ -583,18 +583,23 @@ struct GenExec {
     std::vector<BufP> kept;                 // ... their device buffers, by output ordinal
     size_t out_override = SIZE_MAX;         // order_outputs() copies output `out_override` out after the fact
     size_t out_ordinal() const { return out_override != SIZE_MAX ? out_override : p->outs.size(); }
-    void copy_out(Output &o, const BufP &dev, size_t count) {
+    // high: the output's high words (wide sums in the tail), which go where its low words went: kept for the order step, left in HBM,
+    // into a pinned buffer of their own, or through the small stage
+    void copy_out(Output &o, const BufP &dev, size_t count, bool high = false) {
         if (ordering) {
-            kept.resize(out_ordinal() + 1);
-            kept[out_ordinal()] = dev; o.dev = (const int64_t *)dev->p; o.big_n = count;
+            std::vector<BufP> &k = high ? kept_hi : kept;
+            k.resize(out_ordinal() + 1);
+            k[out_ordinal()] = dev;
+            if (!high) { o.dev = (const int64_t *)dev->p; o.big_n = count; }
             return;
         }
-        if (p->device_outputs && count >= kBigOutput) {  // the caller reads it where it is
-            o.dev_keep = dev; o.dev = (const int64_t *)dev->p; o.big_n = count;
+        if (high ? o.dev != nullptr : (p->device_outputs && count >= kBigOutput)) {  // the caller reads it where it is
+            if (high) { o.dev_hi_keep = dev; o.dev_hi = (const int64_t *)dev->p; }
+            else { o.dev_keep = dev; o.dev = (const int64_t *)dev->p; o.big_n = count; }
             return;
         }
-        int64_t *dst = host_out(o, count);
-        if (!o.big) {
+        int64_t *dst = host_out(o, count, high);
+        if (!(high ? o.big_hi : o.big)) {
             // small: through the context's pinned staging area, in stream order, ONE synchronise for all of them when the run ends
             // (a copy into pageable memory blocks the host until the GPU has caught up: six result columns of a few rows each were
             // six idle gaps of 30-40 us)
@@ -602,7 +607,7 @@ struct GenExec {
             if (stage && count <= vdl_ctx::kSmallStageWords) {
                 if (stage_used + count > vdl_ctx::kSmallStageWords) flush_small();
                 HIP_CHECK(hipMemcpyAsync(stage + stage_used, dev->p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, s));
-                small_copies.push_back({out_ordinal(), stage_used, count});
+                small_copies.push_back({dst, stage_used, count});
                 stage_used += count;
                 return;
             }
@@ -619,14 +624,14 @@ struct GenExec {
         HIP_CHECK(hipMemcpyAsync(dst, dev->p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, c->copy_stream));
         copies_in_flight.push_back(dev);                // the pool must not hand the buffer out again before the copy ran
     }
-    struct SmallCopy { size_t out, at, count; };
+    struct SmallCopy { int64_t *dst; size_t at, count; };      // dst: the output's host vector (it keeps its place when the Output moves into the plan)
     std::vector<SmallCopy> small_copies;
     size_t stage_used = 0;
     void flush_small() {
         if (small_copies.empty()) return;
         HIP_CHECK(hipStreamSynchronize(s));
         const int64_t *stage = c->small_stage();
-        for (const SmallCopy &k : small_copies) std::memcpy(p->outs[k.out].vals.data(), stage + k.at, sizeof(int64_t) * k.count);
+        for (const SmallCopy &k : small_copies) std::memcpy(k.dst, stage + k.at, sizeof(int64_t) * k.count);
         small_copies.clear();
         stage_used = 0;
     }
@@ -638,13 +643,15 @@ struct GenExec {
     }
 
     // where the values of an output go on the host: a pinned buffer of the plan when large
-    int64_t *host_out(Output &o, size_t count) {
+    int64_t *host_out(Output &o, size_t count, bool high = false) {
         if (count >= kBigOutput) {
-            int64_t *pin = p->pinned_out(out_ordinal(), count);
+            int64_t *pin = p->pinned_out(out_ordinal(), count, high);
+            if (pin && high) { o.big_hi = pin; return pin; }
             if (pin) { o.big = pin; o.big_n = count; return pin; }
         }
-        o.vals.resize(count);
-        return o.vals.data();
+        std::vector<int64_t> &v = high ? o.hi : o.vals;
+        v.resize(count);
+        return v.data();
     }
 
     void materialize(const Node &n, const DVec &v0) {
@@ -655,14 +662,18 @@ struct GenExec {
         DVec v = v0;
         if (v.kind == DVec::SPARSE) {                       // every entry holds a value: the output is the entries
             if (v.sel->m > 0) copy_out(o, v.data, (size_t)v.sel->m);
+            if (wide_on && v.sel->m > 0) copy_out_hi(o, v.data, v.hi, (size_t)v.sel->m);
+            o.has_hi = wide_on;
             p->outs.push_back(std::move(o));
             return;
         }
         if (v.kind == DVec::OHCONST) v = densify(v);
+        o.has_hi = wide_on;
         if (v.kind == DVec::ONEHOT) {
-            int64_t h[3];
-            fetch_words(v.data->p, 3, h);
+            int64_t h[4];
+            fetch_words(v.data->p, v.hi ? 4 : 3, h);           // (a wide global sum's record has its high word as fourth word: one fetch)
             if (h[2] > 0) o.vals.push_back(h[0]);
+            if (wide_on && h[2] > 0) o.hi.push_back(v.hi ? h[3] : h[0] >> 63);
         } else {
             const int64_t nb = (v.n + compact_tile() - 1) / compact_tile();
             if (nb > 0) {
@@ -674,6 +685,14 @@ struct GenExec {
                     BufP outb = dev_alloc(c, sizeof(int64_t) * (size_t)total);
                     HIP_CHECK(launch_compact_write(src_of(v), vp(v), v.n, (const int64_t *)counts->p, (int64_t *)outb->p, s));
                     copy_out(o, outb, (size_t)total);
+                    if (wide_on) {
+                        BufP outh;
+                        if (v.hi) {
+                            outh = dev_alloc(c, sizeof(int64_t) * (size_t)total);
+                            HIP_CHECK(launch_compact_write(i64_src(v.hi), vp(v), v.n, (const int64_t *)counts->p, (int64_t *)outh->p, s));
+                        }
+                        copy_out_hi(o, outb, outh, (size_t)total);
+                    }
                 }
             }
         }
@@ -942,6 +961,100 @@ struct GenExec {
         return o;
     }
 
+    // ---- wide sums in the tail (vdl_plan_set_wide_sums_tail; DESIGN.md section 5.17 "The tail") ----------------------------------------
+    // A FoldSum result carries bits 64..127 of its exact sum in DVec::hi.  The accumulation is the split of vdl_fold_wide.hip: every
+    // FoldSum site launches the wide form of its kernel (launch_wide_group_fold / _fold_runs / _fold_global) INSTEAD of the plain one;
+    // it loads each term once and keeps the wrapped sum and the sum of the high halves x >> 32 side by side, and the join makes the
+    // high word per result (at the packed results, at the heads, in the finish step).  Project, Shuffle and
+    // MaterializeCompact carry the high words; a RangeV takes the shape only; every other reader goes through wide_consume, which
+    // queues the fits check and drops them.  The checks' flags are read once, at the run's end (wide_read_checks).
+    bool wide_on = false;
+    struct WideCheck { BufP lo, hi, valid; int64_t n = 0; bool record = false; int what = 0; std::string who; };   // what: 0 a consuming statement, 1 an order key, 2 an output kept in HBM (mode 2)
+    std::vector<WideCheck> wide_checks;
+    BufP wide_flags;
+    static constexpr int kWideFlags = 64;                       // checks per fetch (fetch_words takes 64 words)
+    std::map<std::string, int> wide_routes;                     // kernel -> wide sums it served in this run
+    std::string wide_note() const {
+        std::string t;
+        for (const auto &r : wide_routes) t += (t.empty() ? "tail: " : ", ") + r.first + " (" + std::to_string(r.second) + (r.second == 1 ? " sum)" : " sums)");
+        return t.empty() ? "tail: no FoldSum ran" : t + "; the wide forms: one load per term, the high halves summed beside it, joined per result";
+    }
+    // a wide FoldSum over `count` entries is about to launch on `route`: refused beyond what the split is exact for, counted otherwise
+    void wide_fold_begin(const Node &n, int64_t count, const char *route) {
+        if (count > kWideFoldMaxEntries)
+            throw Error(VDL_ERR_UNSUPPORTED, "wide sums: FoldSum (Id " + std::to_string(n.id) + ") folds " + std::to_string(count) + " entries, more than the 2^31 the split of "
+                                             "the terms into 32-bit halves is exact for; clear the switch to run it");
+        wide_routes[route]++;
+    }
+    // a global FoldSum, wide: the record {value, slot, count} in o.data as ever with the value's high word as its fourth word, and that
+    // word again in o.hi
+    void wide_fold_global(const Node &n, DVec &o, Src d, const uint64_t *vd, const uint64_t *vc, int64_t count) {
+        wide_fold_begin(n, count, "k_fold_global");
+        o.data = dev_alloc(c, 4 * sizeof(int64_t));
+        BufP scratch = dev_alloc(c, sizeof(int64_t) * 4 * (size_t)wide_fold_scratch_blocks());
+        o.hi = dev_alloc(c, sizeof(int64_t));
+        HIP_CHECK(launch_wide_fold_global(d, vd, vc, count, (int64_t *)scratch->p, (int64_t *)o.data->p, (int64_t *)o.hi->p, s));
+    }
+    void wide_queue_check(const DVec &v, int what, const std::string &who) {
+        if ((int)wide_checks.size() == kWideFlags) wide_read_checks();      // (a round trip of its own: 64 consumed sums in one run)
+        if (!wide_flags) wide_flags = dev_alloc(c, sizeof(int64_t) * kWideFlags);
+        if (wide_checks.empty()) HIP_CHECK(launch_fill_words((uint64_t *)wide_flags->p, (uint64_t)INT64_MAX, kWideFlags, s));
+        int64_t *flag = (int64_t *)wide_flags->p + wide_checks.size();
+        WideCheck k;
+        k.lo = v.data; k.hi = v.hi; k.valid = v.valid; k.what = what; k.who = who;
+        k.record = v.kind == DVec::ONEHOT;
+        k.n = k.record ? 1 : v.kind == DVec::SPARSE ? v.sel->m : v.n;
+        if (k.record) HIP_CHECK(launch_wide_fits_record((const int64_t *)k.lo->p, (const int64_t *)k.hi->p, flag, s));
+        else HIP_CHECK(launch_wide_fits((const int64_t *)k.lo->p, (const int64_t *)k.hi->p, vp(v), k.n, flag, s));
+        wide_checks.push_back(std::move(k));
+    }
+    void wide_read_checks() {
+        if (wide_checks.empty()) return;
+        int64_t f[kWideFlags];
+        fetch_words(wide_flags->p, (int)wide_checks.size(), f);
+        for (size_t k = 0; k < wide_checks.size(); k++) {
+            if (f[k] == INT64_MAX) continue;
+            const WideCheck &w = wide_checks[k];
+            int64_t pair[2];
+            fetch_words((const int64_t *)w.lo->p + f[k], 1, &pair[0]);
+            fetch_words((const int64_t *)w.hi->p + f[k], 1, &pair[1]);
+            const std::string value = wide_decimal(pair[0], pair[1]), at = std::to_string(f[k]);
+            const std::string msg = w.what == 1 ? "wide sums: the order key " + w.who + " holds, in group " + at + ", the exact value " + value + ", which does not fit the int64 that keys are compared as"
+                                  : w.what == 2 ? "checked sums: output " + w.who + ", group " + at + ": the exact value " + value + " does not fit int64 (vdl_plan_set_wide_sums(plan, 1) delivers it as two words)"
+                                                : "wide sums: " + w.who + " reads a sum that holds, at position " + at + ", the exact value " + value +
+                                                      ", which does not fit the int64 the statement computes on; nothing is delivered";
+            wide_checks.clear();
+            p->outs.clear();
+            throw Error(VDL_ERR_OVERFLOW, msg);
+        }
+        wide_checks.clear();
+    }
+    // statement n is about to read its operands: those that are wide sums must fit int64 from here on (checked) and lose their high words
+    void wide_consume(const Node &n) {
+        if (n.op == Op::Project || n.op == Op::Shuffle || n.op == Op::Materialize || n.op == Op::RangeV) return;
+        for (int opnd : {n.a, n.b, n.c}) {
+            if (opnd <= 0 || !vec[(size_t)opnd].hi) continue;
+            wide_queue_check(vec[(size_t)opnd], 0, std::string(op_name(n.op, n.bin)) + " (Id " + std::to_string(n.id) + ")");
+            vec[(size_t)opnd].hi = nullptr;
+        }
+    }
+    // the high words of output `o`, whose `count` low words went out of `dev` (copy_out): the vector's own (hi), else the sign extension
+    // (under an order: made after the cut, for the rows that are left)
+    std::vector<BufP> kept_hi;
+    void copy_out_hi(Output &o, const BufP &dev, BufP hi, size_t count) {
+        o.has_hi = true;
+        if (!hi && ordering) return;
+        if (!hi) {
+            hi = dev_alloc(c, sizeof(int64_t) * std::max<size_t>(count, 1));
+            HIP_CHECK(launch_wide_sign((const int64_t *)dev->p, (int64_t *)hi->p, (int64_t)count, s));
+        }
+        copy_out(o, hi, count, true);
+        if (o.dev_hi && p->wide == 2) {                         // (checked sums: an output that stays in HBM is judged there)
+            DVec v; v.kind = DVec::DENSE; v.n = (int64_t)count; v.data = dev; v.hi = hi;
+            wide_queue_check(v, 2, "'" + o.name + "' (" + o.tmp + ")");
+        }
+    }
+
     // Fold `n` over m ENTRIES (every one holds a value, entry 0 starts the first run): control values at ctl, this fold's data at
     // dsrc.  sel = the selection the entries sit on (a prefix selection for vectors scattered into key order, or all n slots).
     // Results: SPARSE on the child selection of the run heads, packed.  Every fold of one GROUP BY shares the heads; with the
@@ -980,6 +1093,7 @@ struct GenExec {
                 if (f.op != Op::FoldSum && f.op != Op::FoldMin && f.op != Op::FoldMax && f.op != Op::FoldCount && f.op != Op::FoldChoose) continue;
                 if (cur_over && cur_over->count(id)) continue;
                 ensure(f.b);
+                if (wide_on) wide_consume(f);                        // (a sibling runs here, not through exec)
                 DVec fd = V(f.b);
                 if (!sel->idx && sel->m == sel->n && fd.kind == DVec::EXPR && !fd.sel) { fd = expr_force(fd); vec[(size_t)f.b] = fd; }
                 if (fd.kind == DVec::SPARSE && fd.sel == sel) srcs.push_back(i64_src(fd.data));
@@ -988,27 +1102,40 @@ struct GenExec {
                 else continue;
                 members.push_back(id);
             }
-            std::vector<BufP> outs(members.size());
+            std::vector<BufP> outs(members.size()), his(members.size());
             const int64_t G = rh.count;
             for (size_t at = 0; at < members.size(); at += kMaxGroupFolds) {
-                GroupFoldArgs ga;
+                WideGroupFoldArgs wa;
+                GroupFoldArgs &ga = wa.g;
                 for (size_t k = at; k < members.size() && k < at + kMaxGroupFolds; k++) {
                     const Op fop = p->prog.at(members[k]).op;
                     const int fk = fop == Op::FoldSum ? 0 : fop == Op::FoldMin ? 1 : fop == Op::FoldMax ? 2 : fop == Op::FoldCount ? 3 : 4;
                     outs[k] = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(G, 1));
                     if (fk != 4 && G > 0)
                         HIP_CHECK(launch_fill_words((uint64_t *)outs[k]->p, fk == 1 ? (uint64_t)INT64_MAX : fk == 2 ? (uint64_t)INT64_MIN : 0ull, G, s));
+                    if (wide_on && fk == 0) {                      // (wide sums: the sum of the high halves lands beside the sum)
+                        wide_fold_begin(p->prog.at(members[k]), m, "k_group_fold");
+                        his[k] = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(G, 1));
+                        if (G > 0) HIP_CHECK(launch_fill_words((uint64_t *)his[k]->p, 0ull, G, s));
+                        wa.out_hi[ga.nfold] = (int64_t *)his[k]->p;
+                    }
                     ga.kind[ga.nfold] = fk; ga.data[ga.nfold] = srcs[k]; ga.out[ga.nfold] = (int64_t *)outs[k]->p;
                     ga.nfold++;
                 }
-                if (G > 0) HIP_CHECK(launch_group_fold(ga, (const uint64_t *)rh.heads->p, m, (const int64_t *)rh.offsets->p, s));
+                if (G > 0 && wide_on) HIP_CHECK(launch_wide_group_fold(wa, (const uint64_t *)rh.heads->p, m, (const int64_t *)rh.offsets->p, s));
+                else if (G > 0) HIP_CHECK(launch_group_fold(ga, (const uint64_t *)rh.heads->p, m, (const int64_t *)rh.offsets->p, s));
             }
+            for (size_t k = 0; k < members.size(); k++)
+                if (his[k]) HIP_CHECK(launch_wide_join((const int64_t *)outs[k]->p, (int64_t *)his[k]->p, G, s));
             for (size_t k = 1; k < members.size(); k++) {
                 vec[(size_t)members[k]] = make_sparse(rh.child, outs[k]);
+                vec[(size_t)members[k]].hi = his[k];
                 done[(size_t)members[k]] = 1;
                 if (p->tracing) snapshot(p->prog.at(members[k]), vec[(size_t)members[k]]);
             }
-            return make_sparse(rh.child, outs[0]);
+            DVec first = make_sparse(rh.child, outs[0]);
+            first.hi = his[0];
+            return first;
         }
         if (!rh.wordhd) {                                   // (heads adopted from the Partition: the per-word lookup k_seg_fold wants)
             rh.wordhd = dev_alloc(c, sizeof(int64_t) * (nw + (size_t)maxscan_blocks((int64_t)nw) + 1));
@@ -1019,6 +1146,15 @@ struct GenExec {
         if (kind == 4) return make_sparse(rh.child, compact_write(dsrc, rh.heads, m, rh.offsets, rh.count));
         BufP data = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(m, 1));
         BufP vout = zero_bitmap(m);
+        if (wide_on && kind == 0) {                         // the wide form: both sums in one pass, joined at the heads, packed like the values
+            wide_fold_begin(n, m, "k_seg_fold");
+            BufP high = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(m, 1));
+            HIP_CHECK(launch_wide_fold_runs(dsrc, nullptr, nullptr, (const uint64_t *)rh.heads->p, (const int64_t *)rh.wordhd->p, m,
+                                            (int64_t *)data->p, (int64_t *)high->p, (uint64_t *)vout->p, s));
+            DVec r = make_sparse(rh.child, compact_write(i64_src(data), rh.heads, m, rh.offsets, rh.count));
+            r.hi = compact_write(i64_src(high), rh.heads, m, rh.offsets, rh.count);
+            return r;
+        }
         HIP_CHECK(launch_fold_runs(kind, dsrc, nullptr, nullptr, (const uint64_t *)rh.heads->p, (const int64_t *)rh.wordhd->p, m,
                                    (int64_t *)data->p, (uint64_t *)vout->p, s));
         return make_sparse(rh.child, compact_write(i64_src(data), rh.heads, m, rh.offsets, rh.count));
@@ -1039,6 +1175,7 @@ struct GenExec {
     DVec exec(const Node &n) {
         auto V = [&](int id) -> const DVec & { return vec[(size_t)id]; };
         DVec o;
+        if (wide_on && !column_filter(n)) wide_consume(n);
         switch (n.op) {
         case Op::Load: {
             const Column &col = find_col(c, n.column);
@@ -1319,9 +1456,10 @@ struct GenExec {
                 // fold the entries; the result sits at the run's first slot = the selection's first slot
                 const DVec &sd = V(n.b);
                 const int kind = n.op == Op::FoldSum ? 0 : n.op == Op::FoldMin ? 1 : n.op == Op::FoldMax ? 2 : n.op == Op::FoldCount ? 3 : 4;
-                BufP scratch = dev_alloc(c, sizeof(int64_t) * 3 * (size_t)fold_scratch_blocks());
                 o.kind = DVec::ONEHOT; o.n = sd.n;
                 o.data = dev_alloc(c, 3 * sizeof(int64_t));
+                if (wide_on && kind == 0) { wide_fold_global(n, o, i64_src(sd.data), nullptr, nullptr, sd.sel->m); return o; }
+                BufP scratch = dev_alloc(c, sizeof(int64_t) * 3 * (size_t)fold_scratch_blocks());
                 // (the record's slot is 0: the run starts at slot 0 of the vector, not at the selection's first slot)
                 HIP_CHECK(launch_fold_global(kind, i64_src(sd.data), nullptr, nullptr, sd.sel->m, (int64_t *)scratch->p, (int64_t *)o.data->p, s));
                 return o;
@@ -1372,19 +1510,35 @@ struct GenExec {
                         dh.wordhd = dev_alloc(c, sizeof(int64_t) * (nw + (size_t)maxscan_blocks((int64_t)nw) + 1));
                         HIP_CHECK(launch_fold_heads(src_of(ctl), vp(ctl), d.n, (uint64_t *)dh.heads->p, (int64_t *)dh.wordhd->p, s));
                     }
+                    if (wide_on && kind == 0) {                     // the wide form: both sums in one pass, joined at the heads
+                        wide_fold_begin(n, d.n, "k_seg_fold");
+                        o.hi = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(d.n, 1));
+                        HIP_CHECK(launch_wide_fold_runs(src_of(d), vp(d), vp(ctl), (const uint64_t *)dh.heads->p, (const int64_t *)dh.wordhd->p, d.n,
+                                                        (int64_t *)o.data->p, (int64_t *)o.hi->p, (uint64_t *)o.valid->p, s));
+                        return o;
+                    }
                     HIP_CHECK(launch_fold_runs(kind, src_of(d), vp(d), vp(ctl), (const uint64_t *)dh.heads->p, (const int64_t *)dh.wordhd->p, d.n,
                                                (int64_t *)o.data->p, (uint64_t *)o.valid->p, s));
                     return o;
                 }
                 BufP heads = dev_alloc(c, sizeof(uint64_t) * nw);
                 BufP wordhd = dev_alloc(c, sizeof(int64_t) * (nw + (size_t)maxscan_blocks((int64_t)nw) + 1));
+                if (wide_on && kind == 0) {                         // the wide form over heads made here
+                    wide_fold_begin(n, d.n, "k_seg_fold");
+                    o.hi = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(d.n, 1));
+                    HIP_CHECK(launch_fold_heads(src_of(ctl), vp(ctl), d.n, (uint64_t *)heads->p, (int64_t *)wordhd->p, s));
+                    HIP_CHECK(launch_wide_fold_runs(src_of(d), vp(d), vp(ctl), (const uint64_t *)heads->p, (const int64_t *)wordhd->p, d.n,
+                                                    (int64_t *)o.data->p, (int64_t *)o.hi->p, (uint64_t *)o.valid->p, s));
+                    return o;
+                }
                 HIP_CHECK(launch_fold_segmented(kind, src_of(ctl), vp(ctl), src_of(d), vp(d), d.n, (uint64_t *)heads->p,
                                                 (int64_t *)wordhd->p, (int64_t *)o.data->p, (uint64_t *)o.valid->p, s));
                 return o;
             }
-            BufP scratch = dev_alloc(c, sizeof(int64_t) * 3 * (size_t)fold_scratch_blocks());
             o.kind = DVec::ONEHOT; o.n = d.n;
             o.data = dev_alloc(c, 3 * sizeof(int64_t));
+            if (wide_on && kind == 0) { wide_fold_global(n, o, src_of(d), vp(d), vp(ctl), d.n); return o; }
+            BufP scratch = dev_alloc(c, sizeof(int64_t) * 3 * (size_t)fold_scratch_blocks());
             HIP_CHECK(launch_fold_global(kind, src_of(d), vp(d), vp(ctl), d.n, (int64_t *)scratch->p, (int64_t *)o.data->p, s));
             return o;
         }
@@ -1646,6 +1800,7 @@ struct GenExec {
                 if (opnd > 0 && last_use[(size_t)opnd] == (int)k) vec[(size_t)opnd] = DVec{};
         }
         if (ordering) order_outputs();
+        if (wide_on) wide_read_checks();                               // every consumed or ordered-by sum fits int64, or nothing is delivered
         HIP_CHECK(hipStreamSynchronize(s));
         finish_copies();
         if (order_timed) {
@@ -1758,15 +1913,34 @@ struct GenExec {
         const int64_t L = p->order.limit > 0 ? std::min<int64_t>(p->order.limit, m) : m;
         bool on_device = false;
         for (const Output &o : p->outs) on_device |= o.dev != nullptr;
-        if (!on_device) { order_outputs_on_host(c, p); return; }          // (m = 0 included: nothing was kept)
+        if (!on_device) {                                              // (m = 0 included: nothing was kept)
+            if (wide_on && p->wide == 2) wide_check_outputs(p);
+            order_outputs_on_host(c, p);
+            return;
+        }
         kept.resize(p->outs.size());
+        if (wide_on) kept_hi.resize(p->outs.size());
         for (size_t k = 0; k < p->outs.size(); k++) {                  // a result a statement assembled on the host joins the others
             Output &o = p->outs[k];
             if (o.dev) continue;
             kept[k] = dev_alloc(c, sizeof(int64_t) * (size_t)m);
             HIP_CHECK(hipMemcpyAsync(kept[k]->p, o.vals.data(), sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, s));
+            if (wide_on && o.hi.size() == (size_t)m) {                 // ... with its high words
+                kept_hi[k] = dev_alloc(c, sizeof(int64_t) * (size_t)m);
+                HIP_CHECK(hipMemcpyAsync(kept_hi[k]->p, o.hi.data(), sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, s));
+            }
             HIP_CHECK(hipStreamSynchronize(s));                        // (pageable source)
             o.dev = (const int64_t *)kept[k]->p;
+        }
+        if (wide_on) {
+            // keys are compared as the int64 they are, and mode 2 judges what the statements delivered: both on the rows as they stand
+            for (size_t k = 0; k < p->outs.size(); k++) {
+                if (!kept_hi[k]) continue;
+                const bool is_key = std::find(keys.begin(), keys.end(), k) != keys.end();
+                if (!is_key && p->wide != 2) continue;
+                DVec v; v.kind = DVec::DENSE; v.n = m; v.data = kept[k]; v.hi = kept_hi[k];
+                wide_queue_check(v, is_key ? 1 : 2, "'" + p->outs[k].name + "' (" + p->outs[k].tmp + ")");
+            }
         }
         // text keys: an index that has to be built is built (and timed) before the order step's own events
         const int n_text = p->order.n_text();
@@ -1792,7 +1966,7 @@ struct GenExec {
         if (at != std::string::npos) note.replace(at, 1, std::to_string(L));
         if (n_text > 0) note += " text_keys=" + std::to_string(n_text);
         p->order_note = note;
-        std::vector<BufP> cut(p->outs.size());
+        std::vector<BufP> cut(p->outs.size()), cut_hi(p->outs.size());
         if (index) {
             for (size_t k0 = 0; k0 < p->outs.size(); k0 += kOrdGatherMax) {       // ONE launch for every plan with at most kOrdGatherMax outputs
                 OrdGather G;
@@ -1802,7 +1976,16 @@ struct GenExec {
                 }
                 HIP_CHECK(launch_order_gather(G, (const int64_t *)index->p, L, s));
             }
-        } else cut = kept;                                             // the first L rows as they stand
+            // wide sums: the high vectors of the sums follow the same index (an output that is no sum gets its sign extension after the cut)
+            OrdGather H;
+            for (size_t k = 0; wide_on && k < p->outs.size(); k++) {
+                if (!kept_hi[k]) continue;
+                cut_hi[k] = dev_alloc(c, sizeof(int64_t) * (size_t)L);
+                H.src[H.n] = (const int64_t *)kept_hi[k]->p; H.dst[H.n] = (int64_t *)cut_hi[k]->p;
+                if (++H.n == kOrdGatherMax) { HIP_CHECK(launch_order_gather(H, (const int64_t *)index->p, L, s)); H = OrdGather{}; }
+            }
+            if (H.n > 0) HIP_CHECK(launch_order_gather(H, (const int64_t *)index->p, L, s));
+        } else { cut = kept; if (wide_on) cut_hi = kept_hi; }         // the first L rows as they stand
         HIP_CHECK(hipEventRecord(p->order_ev[1], s));
         order_timed = true;
         for (size_t k = 0; k < p->outs.size(); k++) {
@@ -1810,9 +1993,11 @@ struct GenExec {
             o.dev = nullptr; o.dev_keep = nullptr; o.big = nullptr; o.big_n = 0; o.vals.clear();
             out_override = k;
             copy_out(o, cut[k], (size_t)L);
+            if (wide_on) { o.hi.clear(); o.big_hi = nullptr; copy_out_hi(o, cut[k], cut_hi[k], (size_t)L); }
         }
         out_override = SIZE_MAX;
         kept.clear();
+        kept_hi.clear();
     }
 
     // ---- the same step on the exchange route of a sharded run (vdl_plan_set_order_sharded; the collectives: vdl_comm.cpp) --------

@@ -186,6 +186,39 @@ VDL_HD inline int64_t merge_word_wide(const int64_t *g, int world, int64_t n_wor
     *hi_out = (int64_t)hi;
     return (int64_t)lo;
 }
+// Wide sums in the per-operator folds (vdl_plan_set_wide_sums_tail; DESIGN.md section 5.17 "The tail").  A term x is split as
+// x = H * 2^32 + L, L = x & 0xffffffff, H = x >> 32; over at most 2^31 terms the plain sums SL of the L (in [0, 2^63)) and SH of the H
+// (|SH| < 2^62) cannot wrap.  The exact sum SH * 2^32 + SL as a pair: lo = bits 0..63 -- the wrapped int64 sum of the terms, by
+// construction --, hi = bits 64..127.
+VDL_HD inline void wide_join_halves(int64_t sl, int64_t sh, int64_t *lo, int64_t *hi) {
+    const uint64_t base = (uint64_t)sh << 32, l = base + (uint64_t)sl;
+    *lo = (int64_t)l;
+    *hi = (sh >> 32) + (l < base ? 1 : 0);
+}
+// ... from the wrapped sum itself and SH: SL = wrapped - (SH << 32) modulo 2^64, exactly, because SL < 2^63
+VDL_HD inline void wide_join_low(int64_t wrapped, int64_t sh, int64_t *lo, int64_t *hi) {
+    wide_join_halves((int64_t)((uint64_t)wrapped - ((uint64_t)sh << 32)), sh, lo, hi);
+}
+constexpr int64_t kWideFoldMaxEntries = (int64_t)1 << 31;      // entries one wide fold takes: beyond it SH could wrap
+// vdl_fold_wide.hip: the wide forms of the FoldSum kernels -- one load per term, the wrapped sum and the sum of the high halves side by
+// side -- and what goes with them.
+//   fold_global: launch_fold_global for FoldSum; scratch 4 * wide_fold_scratch_blocks() int64; result = FOUR words, the record
+//       {value, slot, count} as ever and the value's high word behind it (0 when nothing was folded); result_hi[0] = that word again,
+//       for the readers that take a vector's high words as a buffer of their own.
+//   fold_runs: launch_fold_runs for FoldSum over the same heads / wordhd; out_hi[head] = the high word of out[head] (joined at the heads).
+//   group_fold: launch_group_fold; a FoldSum member with out_hi set (pre-filled with zeros like out) leaves the sum of its high halves
+//       there: launch_wide_join over the packed results afterwards.
+//   join: hi[i] (in: the SUM of the high halves of result i) becomes bits 64..127 of the exact sum whose low word is lo[i].
+//   sign: hi[i] = lo[i] >> 63.  fits: flag[0] (INT64_MAX before) = the first i < n holding a value (valid null = all do) with
+//   hi[i] != lo[i] >> 63; fits_record: flag[0] = 0 when the record's value does not fit.
+int wide_fold_scratch_blocks();
+hipError_t launch_wide_fold_global(Src d, const uint64_t *vd, const uint64_t *vc, int64_t n, int64_t *scratch, int64_t *result, int64_t *result_hi, hipStream_t s);
+hipError_t launch_wide_fold_runs(Src d, const uint64_t *vd, const uint64_t *vc, const uint64_t *heads, const int64_t *wordhd, int64_t n, int64_t *out, int64_t *out_hi,
+                                 uint64_t *vout /* pre-zeroed */, hipStream_t s);
+hipError_t launch_wide_join(const int64_t *lo, int64_t *hi, int64_t n, hipStream_t s);
+hipError_t launch_wide_sign(const int64_t *lo, int64_t *hi, int64_t n, hipStream_t s);
+hipError_t launch_wide_fits(const int64_t *lo, const int64_t *hi, const uint64_t *valid, int64_t n, int64_t *flag, hipStream_t s);
+hipError_t launch_wide_fits_record(const int64_t *rec, const int64_t *hi, int64_t *flag, hipStream_t s);
 // gathered: `stride` words per rank = n_words raw, n_words resolved, then (stride > 2 * n_words) the rank's status word.
 // status_out (may be null; needs that word): [0] = the first non-zero status over the ranks (0 = every rank's local phase
 // succeeded), [1] = that rank.
@@ -290,6 +323,12 @@ struct GroupFoldArgs {
     int64_t *out[kMaxGroupFolds] = {};
 };
 hipError_t launch_group_fold(const GroupFoldArgs &a, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s);
+// the wide form (vdl_fold_wide.hip, described with the other wide folds above)
+struct WideGroupFoldArgs {
+    GroupFoldArgs g;
+    int64_t *out_hi[kMaxGroupFolds] = {};
+};
+hipError_t launch_wide_group_fold(const WideGroupFoldArgs &a, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s);
 size_t partition_scratch_bytes(int64_t n, int64_t pcount);
 hipError_t launch_partition(Src data, const uint64_t *valid, int64_t n, int64_t pmin, int64_t pcount, void *scratch /* partition_scratch_bytes(n, pcount) */,
                             uint64_t *keys_a, int64_t *slots_a, uint64_t *keys_b, int64_t *slots_b,

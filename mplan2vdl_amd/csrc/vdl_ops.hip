@@ -365,6 +365,7 @@ hipError_t launch_select_bitmap(Src d, const uint64_t *vd, const uint64_t *vc, u
     return launch_status();
 }
 
+// (vdl_fold_wide.hip holds a copy of this kernel pair with a second sum, k_wide_fold_global: a fix here belongs there too.)
 // Global (single-run) fold (/root/reference/src/Vlite.hs:337-356 with an all-equal control
 // vector, Vlite.hs:636-639): two launches, per-block partials then one block.
 constexpr int kFoldBlocks = 2048;
@@ -770,6 +771,8 @@ __device__ __forceinline__ void atomic_combine(int rk, int64_t *addr, int64_t v)
 // 1.5 TB/s: 200 us for two folds over 18 M entries).  A wave covers 8 head words, a block half a compaction tile.
 // NF = folds handled per trip (their loads are issued together).  vec16 bit f: fold f's data is int64 at a 16-byte aligned
 // address -- four 16-byte loads per lane instead of eight scalar ones.
+// (vdl_fold_wide.hip holds a copy of this kernel with a second sum per FoldSum member, k_wide_group_fold, and repeats kGroupK, kGroupSplit
+// and kCompactWords as kWgK, kWgSplit and kWgWords -- its launcher refuses to run when the tile sizes differ: a fix here belongs there too.)
 constexpr int kGroupK = 8, kGroupSplit = 2;
 // The results of the runs that END inside a wave -- all but the wave's last one -- are staged in LDS at their group's place and stored by
 // consecutive lanes (round 4): a lane storing its own groups put 64 isolated 8-byte writes into every store instruction, nine of them per
@@ -1399,6 +1402,7 @@ __device__ __forceinline__ void atomic_combine(int rk, int64_t *addr, int64_t v)
     else atomicMax((long long *)addr, (long long)v);
 }
 
+// (vdl_fold_wide.hip holds a copy of this kernel for FoldSum with a second sum, k_wide_seg_fold: a fix here belongs there too.)
 // kind: 0 sum, 1 min, 2 max, 3 count, 4 choose-pass (min over slot index of the data)
 // Each wave walks a contiguous chunk of words and carries the value of the run that is open at a word's last lane
 // into the next word, so a run costs one atomic per wave it touches instead of one per 64 slots: with few long runs

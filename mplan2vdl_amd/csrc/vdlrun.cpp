@@ -45,6 +45,8 @@
 // (vdl_plan_set_wide_sums_sharded; VDL_WIDE_SHARDED=1 does the same): the ranks merge their (lo, hi) partial words with carry, every rank
 // ends with the exact answer of the whole table and ONE reply is printed, in exact decimals; --checked-sums is then checked on the merged
 // values.  Without it --gpus refuses the switch before any rank starts, as every sharded entry point does.
+// --wide-tail (vdl_plan_set_wide_sums_tail; only together with --wide-sums | --checked-sums, on one GPU): plans that do not fuse as a
+// whole run too -- their sums through the per-operator folds, exact where delivered and checked where another statement reads them.
 // --batch-grouped: programs whose one scan is a GROUP BY over table columns share a grouped batch too (vdl_set_batch_grouped); without it
 // they run alone, as "grouped scans are not batched".
 #include <signal.h>
@@ -226,6 +228,7 @@ struct Options {
     int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0, lookup_images = 0;
     int wide = -1;                  // --wide-sums 1 / --checked-sums 2; -1: as the plan was parsed (VDL_WIDE_SUMS)
     int wide_sharded = 0;           // --wide-sharded: vdl_plan_set_wide_sums_sharded
+    int wide_tail = 0;              // --wide-tail: vdl_plan_set_wide_sums_tail (only together with --wide-sums | --checked-sums)
     std::string data_dir, shard = "lineitem";
     std::vector<std::string> order_fields;
     std::vector<int> order_desc;
@@ -297,6 +300,7 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
         if (o.jit_share) vdl_plan_set_jit_bounds(one, 1);
         if (o.wide >= 0 && (rc = vdl_plan_set_wide_sums(one, o.wide))) return die(ctx, "vdl_plan_set_wide_sums", rc);
         if (o.wide_sharded && (rc = vdl_plan_set_wide_sums_sharded(one, 1))) return die(ctx, "vdl_plan_set_wide_sums_sharded", rc);
+        if (o.wide_tail && (rc = vdl_plan_set_wide_sums_tail(one, 1))) return die(ctx, "vdl_plan_set_wide_sums_tail", rc);
         if (!o.order_fields.empty() || o.limit > 0) {
             std::vector<const char *> fields;
             for (const std::string &f : o.order_fields) fields.push_back(f.c_str());
@@ -398,6 +402,7 @@ int main(int argc, char **argv) {
         else if (a == "--wide-sums") o.wide = 1;
         else if (a == "--checked-sums") o.wide = 2;
         else if (a == "--wide-sharded") o.wide_sharded = 1;
+        else if (a == "--wide-tail") o.wide_tail = 1;
         else if (a == "--order-by" && i + 1 < argc && parse_order_by(argv[i + 1], o)) i++;
         else if (a == "--order-sharded") o.order_sharded = 1;
         else if (a == "--limit" && i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]) &&
@@ -417,6 +422,10 @@ int main(int argc, char **argv) {
     }
     if (!o.batch_files.empty() && !o.jit) {                    // (only specialised scans are batched: without --jit every program would run alone)
         std::fprintf(stderr, "usage: vdlrun --batch FILE needs --jit or --jit-tune: a batch shares a scan specialised for its plans\n");
+        return 2;
+    }
+    if (o.wide_tail && o.wide <= 0) {                          // (the tail switch says how a WIDE plan runs)
+        std::fprintf(stderr, "usage: vdlrun --wide-tail needs --wide-sums or --checked-sums: it lets a plan with wide sums on run through the per-operator folds\n");
         return 2;
     }
     if (o.gpus < 1 || o.gpus > 128) { std::fprintf(stderr, "vdlrun: --gpus must be 1 .. 128\n"); return 2; }

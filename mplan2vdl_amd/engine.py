@@ -137,7 +137,7 @@ class Plan:
         to the plan until its next run."""
         self._e._check(self._e._L.vdl_plan_set_device_outputs(self._h, int(bool(enabled))))
 
-    def set_wide_sums(self, mode, sharded=False):
+    def set_wide_sums(self, mode, sharded=False, tail=False):
         """Exact 128-bit SUM results (vdl.h: vdl_plan_set_wide_sums).  0: off -- sums wrap around in int64 and results have the
         types they always had.  1: wide -- `run()` / `collect()` return every output as a list of exact Python ints of any size
         (as_numpy=True: an object-dtype array of them); `collect_words()` hands out the (lo, hi) int64 pairs instead.  2: checked
@@ -146,9 +146,15 @@ class Plan:
         `sharded=True` (with mode 1 or 2) switches the wide merge of sharded runs on (vdl_plan_set_wide_sums_sharded):
         `run_sharded` and the `run_sharded_begin` / `_end` pair then accept the plan on the fold route, every rank ends with the
         exact answer of the whole table, and mode 2 is checked on the merged values.  Every call passes it down, so a later plain
-        set_wide_sums(..) switches it off again."""
+        set_wide_sums(..) switches it off again.
+        `tail=True` (with mode 1 or 2) lets `run()` also serve the plans whose sums run through the per-operator folds
+        (vdl_plan_set_wide_sums_tail): a GROUP BY tail behind a fused front, fusion off, the rerun of a fused plan that found keys
+        outside the pivots.  A wide sum that reaches an output through Project / Shuffle / MaterializeCompact is delivered exact; one
+        that any other statement reads must fit int64, or the run raises VDL_ERR_OVERFLOW naming that statement.  Passed down by
+        every call like `sharded`; the sharded entry points refuse such a plan either way."""
         self._e._check(self._e._L.vdl_plan_set_wide_sums(self._h, int(mode)))
         self._e._check(self._e._L.vdl_plan_set_wide_sums_sharded(self._h, int(bool(sharded) and int(mode) != 0)))
+        self._e._check(self._e._L.vdl_plan_set_wide_sums_tail(self._h, int(bool(tail) and int(mode) != 0)))
 
     @property
     def wide_sums(self):
@@ -157,6 +163,21 @@ class Plan:
     @property
     def wide_sums_sharded(self):
         return bool(self._e._L.vdl_plan_wide_sums_sharded(self._h))
+
+    @property
+    def wide_sums_tail(self):
+        return bool(self._e._L.vdl_plan_wide_sums_tail(self._h))
+
+    def high_device(self):
+        """{tmpN: DeviceValues or None} of the last run: the high words of the outputs that stayed in device memory
+        (set_device_outputs with wide sums in the tail; vdl.h: vdl_output_high_device), None for every other output."""
+        L, out = self._e._L, {}
+        for k in range(L.vdl_n_outputs(self._h)):
+            tmp, dev, n = ctypes.c_char_p(), ctypes.POINTER(ctypes.c_int64)(), ctypes.c_size_t()
+            L.vdl_output(self._h, k, None, ctypes.byref(tmp), None, None)
+            self._e._check(L.vdl_output_high_device(self._h, k, ctypes.byref(dev), ctypes.byref(n)))
+            out[tmp.value.decode()] = DeviceValues(ctypes.cast(dev, ctypes.c_void_p).value, n.value, self) if dev else None
+        return out
 
     def wide_note(self):
         """What served the plan's scans in the last wide run ("wide: k_mscan<...> grouped, 7 sums"), or "refused: <reason>"."""
