@@ -2,6 +2,7 @@
 // element-wise operators, expression chains, column filters, selection, gathers and scatters, compaction, folds,
 // cross products, LIKE.  HBM-bound integer work: batched unconditional loads, one ballot per 64 slots.
 #include "vdl_device.h"
+#include "vdl_fold_body.h"
 
 namespace vdl {
 
@@ -365,110 +366,23 @@ hipError_t launch_select_bitmap(Src d, const uint64_t *vd, const uint64_t *vc, u
     return launch_status();
 }
 
-// (vdl_fold_wide.hip holds a copy of this kernel pair with a second sum, k_wide_fold_global: a fix here belongs there too.)
 // Global (single-run) fold (/root/reference/src/Vlite.hs:337-356 with an all-equal control
-// vector, Vlite.hs:636-639): two launches, per-block partials then one block.
-constexpr int kFoldBlocks = 2048;
+// vector, Vlite.hs:636-639): two launches, per-block partials (vdl_fold_global.inc) then one block (vdl_fold_body.h).
 int fold_scratch_blocks() { return kFoldBlocks; }
 
 __global__ __launch_bounds__(256) void k_fold_global(int kind, Src d, const uint64_t *vd, const uint64_t *vc, int64_t n,
                                                      int64_t *scratch) {
-    constexpr int U = 8;                                        // 4 KB of data per wave in flight: a cold stream needs it
-    const int rk = kind == 1 ? R_MIN : kind == 2 ? R_MAX : R_SUM;
-    const int ak = kind == 4 ? R_MIN : rk;
-    const int64_t nw = (n + 63) >> 6;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int64_t wstride = (int64_t)gridDim.x * (blockDim.x / kWave) * U;
-    // per lane: the fold of its data; per wave (kept uniform, lane 0 reports them): first control slot, number of data
-    // slots, and for count / choose the result itself -- all three come from the bitmap words, not from the rows
-    int64_t acc = r_identity(rk);
-    int64_t first = INT64_MAX, cnt = 0, chosen = INT64_MAX;
-    by_kind(d.kind, [&](auto kd) { by_reduction(rk, [&](auto rc) {
-        constexpr int RK = decltype(rc)::value;
-        for (int64_t w0 = wave_index() * U; w0 < nw; w0 += wstride) {
-            int64_t x[U];
-            uint64_t mc[U], md[U];
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const int64_t w = w0 + u < nw ? w0 + u : nw - 1;
-                const int64_t i = (w << 6) + lane;
-                x[u] = kind < 3 ? ldk_stream<decltype(kd)::value>(d, i < n ? i : 0) : 0;     // wave-uniform test; masked lanes read slot 0
-                const int64_t rem = n - (w << 6);
-                mc[u] = w0 + u < nw ? (rem < 64 ? (1ull << rem) - 1 : ~0ull) : 0ull;
-            }
-            if (vc) {
-                uint64_t t[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) t[u] = vc[w0 + u < nw ? w0 + u : nw - 1];
-#pragma unroll
-                for (int u = 0; u < U; u++) mc[u] &= t[u];
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) md[u] = mc[u];
-            if (vd) {
-                uint64_t t[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) t[u] = vd[w0 + u < nw ? w0 + u : nw - 1];
-#pragma unroll
-                for (int u = 0; u < U; u++) md[u] &= t[u];
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const int64_t wbase = (w0 + u) << 6;
-                if (mc[u] && first == INT64_MAX) first = wbase + __ffsll((long long)mc[u]) - 1;      // words come in ascending order per wave
-                if (md[u] && chosen == INT64_MAX) chosen = wbase + __ffsll((long long)md[u]) - 1;
-                cnt += __popcll(md[u]);
-                if ((md[u] >> lane) & 1ull) acc = r_combine(RK, acc, x[u]);
-            }
-        }
-    }); });
-    if (kind == 3) acc = lane == 0 ? cnt : 0;
-    else if (kind == 4) acc = lane == 0 ? chosen : INT64_MAX;
-    if (lane != 0) { first = INT64_MAX; cnt = 0; }
-    __shared__ int64_t red[3][256 / kWave];
-    acc = wave_reduce(acc, ak); first = wave_reduce(first, R_MIN); cnt = wave_reduce(cnt, R_SUM);
-    if (lane == 0) { red[0][wave] = acc; red[1][wave] = first; red[2][wave] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 256 / kWave; w++) {
-            acc = r_combine(ak, acc, red[0][w]); first = r_combine(R_MIN, first, red[1][w]); cnt += red[2][w];
-        }
-        scratch[3 * (int64_t)blockIdx.x + 0] = acc;
-        scratch[3 * (int64_t)blockIdx.x + 1] = first;
-        scratch[3 * (int64_t)blockIdx.x + 2] = cnt;
-    }
+    constexpr bool WIDE = false;
+#include "vdl_fold_global.inc"
 }
-
 __global__ __launch_bounds__(256) void k_fold_global_finish(int kind, Src d, const int64_t *scratch, int nblocks, int64_t *result) {
-    const int rk = kind == 1 ? R_MIN : kind == 2 ? R_MAX : R_SUM;
-    const int ak = kind == 4 ? R_MIN : rk;
-    int64_t acc = kind == 4 ? INT64_MAX : r_identity(rk), first = INT64_MAX, cnt = 0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-        acc = r_combine(ak, acc, scratch[3 * (int64_t)b]);
-        first = r_combine(R_MIN, first, scratch[3 * (int64_t)b + 1]);
-        cnt += scratch[3 * (int64_t)b + 2];
-    }
-    __shared__ int64_t red[3][256 / kWave];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    acc = wave_reduce(acc, ak); first = wave_reduce(first, R_MIN); cnt = wave_reduce(cnt, R_SUM);
-    if (lane == 0) { red[0][wave] = acc; red[1][wave] = first; red[2][wave] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 256 / kWave; w++) {
-            acc = r_combine(ak, acc, red[0][w]); first = r_combine(R_MIN, first, red[1][w]); cnt += red[2][w];
-        }
-        if (kind == 4) acc = cnt > 0 ? ld(d, acc) : 0;     // FoldChoose: the first datum of the run
-        result[0] = acc;
-        result[1] = first == INT64_MAX ? -1 : 0;     // the first (here: only) run of a vector starts at slot 0, whatever EPS slots precede its first member
-        result[2] = cnt;
-    }
+    fold_global_finish_body<false>(kind, d, scratch, nblocks, result, nullptr);
 }
 
 hipError_t launch_fold_global(int kind, Src d, const uint64_t *vd, const uint64_t *vc, int64_t n, int64_t *scratch,
                               int64_t *result, hipStream_t s) {
     (void)hipGetLastError();   // see launch_status()
-    int grid = grid_for(n, 256, 8);
-    if (grid > kFoldBlocks) grid = kFoldBlocks;
+    const int grid = fold_global_grid(n);
     k_fold_global<<<grid, 256, 0, s>>>(kind, d, vd, vc, n, scratch);
     k_fold_global_finish<<<1, 256, 0, s>>>(kind, d, scratch, grid, result);
     return launch_status();
@@ -574,7 +488,6 @@ hipError_t launch_onehot_dense(const int64_t *oh, int64_t *out, uint64_t *valid,
 
 // MaterializeCompact (/root/reference/src/Vdl.hs:452-453): stream compaction with the order kept.
 // count -> exclusive scan of tile counts -> write; a tile is 64 bitmap words = 4096 slots.
-constexpr int kCompactWords = 64;
 int64_t compact_tile() { return (int64_t)kCompactWords * 64; }
 
 __global__ __launch_bounds__(64) void k_compact_count(const uint64_t *valid, int64_t n, int64_t *counts) {
@@ -756,159 +669,19 @@ hipError_t launch_compact_write(Src v, const uint64_t *valid, int64_t n, const i
     return launch_status();
 }
 
-// ---- every fold of one GROUP BY in one launch, results packed per run ---------------------------------------------------------
-// (the tail of a plan whose front is fused: Partition -> Scatter x k -> Fold x k over the survivors, Vlite.hs:1056-1060,1082-1098.
-// Statement by statement that is a head pass, a count, a compaction per FoldChoose and fill + segmented fold + compaction per
-// aggregate -- a dozen launches of a few microseconds of work each; here: one pass over the entries for all of them.)
-// A block owns one compaction tile (64 head words = 4096 entries), a wave walks words of it, lane l holds entry 64 w + l.  Group of
-// an entry = heads before the tile (offsets) + heads before its word inside the tile + heads at or before its lane - 1.  Values are
-// folded along the lanes with a segmented shuffle scan bounded by the head word; the last lane of a segment hands the partial to
-// out[group]: a plain store when the run begins and ends inside the word (nobody else adds to it), an atomic otherwise.
-__device__ __forceinline__ void atomic_combine(int rk, int64_t *addr, int64_t v);
-// Layout: a lane owns kGroupK = 8 CONSECUTIVE entries and folds them serially (no cross-lane traffic inside its chunk: a run that
-// begins and ends there is stored at once); only what is open at the chunk's ends is combined across the lanes -- one segmented
-// shuffle scan per 512 entries and fold, where a lane-per-entry layout paid one per 64 (that version was instruction-bound at
-// 1.5 TB/s: 200 us for two folds over 18 M entries).  A wave covers 8 head words, a block half a compaction tile.
-// NF = folds handled per trip (their loads are issued together).  vec16 bit f: fold f's data is int64 at a 16-byte aligned
-// address -- four 16-byte loads per lane instead of eight scalar ones.
-// (vdl_fold_wide.hip holds a copy of this kernel with a second sum per FoldSum member, k_wide_group_fold, and repeats kGroupK, kGroupSplit
-// and kCompactWords as kWgK, kWgSplit and kWgWords -- its launcher refuses to run when the tile sizes differ: a fix here belongs there too.)
-constexpr int kGroupK = 8, kGroupSplit = 2;
-// The results of the runs that END inside a wave -- all but the wave's last one -- are staged in LDS at their group's place and stored by
-// consecutive lanes (round 4): a lane storing its own groups put 64 isolated 8-byte writes into every store instruction, nine of them per
-// fold and 512 entries, and the stores were 290 of the kernel's 506 us for Q3's 32 M survivors at SF100 (an ablation build without them:
-// 216 us; -DVDL_GF_ABLATE=1 still builds it).
-#if defined(VDL_GF_ABLATE) && VDL_GF_ABLATE == 1
-#define GF_STORE(g, v) do { if ((g) == -12345) stage[wave][0] = (v); } while (0)
-#else
-#define GF_STORE(g, v) do { stage[wave][(g) - Bw] = (v); } while (0)
-#endif
+// ---- every fold of one GROUP BY in one launch, results packed per run (vdl_group_fold.inc) ----
 template <int NF>
 __global__ __launch_bounds__(256) void k_group_fold(GroupFoldArgs a, unsigned vec16, const uint64_t *heads, int64_t m, const int64_t *offsets) {
-    __shared__ int wprefix[kCompactWords];
-    __shared__ uint64_t wmask[kCompactWords];
-    __shared__ int64_t stage[256 / kWave][kWave * kGroupK];               // per wave: the results of its groups, by group
-    constexpr int K = kGroupK, NW = 256 / kWave, WW = kWave * K / 64;          // WW = head words per wave (8)
-    static_assert(kCompactWords == kGroupSplit * NW * WW, "a block's waves cover its share of the tile");
-    const int64_t nw = (m + 63) >> 6;
-    const int64_t tile = blockIdx.x / kGroupSplit;
-    const int part = blockIdx.x % kGroupSplit;
-    const int64_t w0 = tile * kCompactWords;
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    if (tid < kCompactWords) {
-        const int64_t w = w0 + tid;
-        const uint64_t hm = w < nw ? heads[w] : 0ull;             // (bits past m are clear: launch_sorted_heads / k_seg_heads)
-        wmask[tid] = hm;
-        const int cnt = __popcll(hm);
-        int incl = cnt;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) { const int y = __shfl_up(incl, off, kWave); if (lane >= off) incl += y; }
-        wprefix[tid] = incl - cnt;
-    }
-    __syncthreads();
-    const int wfirst = part * (NW * WW) + wave * WW;              // this wave's first word inside the tile
-    if (((w0 + wfirst) << 6) >= m) return;                         // wave-uniform; no barrier below
-    const int64_t e0 = ((w0 + wfirst) << 6) + (int64_t)lane * K;   // my first entry
-    const int nv = m - e0 >= K ? K : (m - e0 > 0 ? (int)(m - e0) : 0);      // my entries inside the vector
-    const unsigned hb = (unsigned)(wmask[wfirst + (lane >> 3)] >> ((lane & 7) * 8)) & 0xffu;     // their head bits
-    const int c = __popc(hb);
-    int incl = c;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) { const int y = __shfl_up(incl, off, kWave); if (lane >= off) incl += y; }
-    const int64_t B = offsets[tile] + wprefix[wfirst] + (incl - c);           // run heads strictly before my first entry
-    const int64_t Bw = offsets[tile] + wprefix[wfirst];                       // ... before the wave's: its first group's number
-    const int ngw = __shfl(incl, kWave - 1, kWave);                           // run heads inside the wave
-    const uint64_t headlanes = __ballot(c != 0);
-    const uint64_t below = (1ull << lane) - 1;
-    // lanes whose open end my chunk continues: a segment of lanes starts behind every lane that holds a head
-    const uint64_t starts = (headlanes << 1) | 1ull;
-    const int seg0 = 63 - __clzll((long long)(starts & (below | (1ull << lane))));
-    const bool first_head_lane = c != 0 && (headlanes & below) == 0;
-    const uint64_t later = lane == kWave - 1 ? 0ull : headlanes >> (lane + 1);
-    const int next_head = later ? lane + __ffsll((long long)later) : -1;      // the next lane that holds a head
-    const bool open_to_end = c != 0 && !later;                                // my last run is still open when the wave ends
-    const int fetch_from = next_head >= 0 ? next_head : kWave - 1;
-#pragma unroll
-    for (int j0 = 0; j0 < kMaxGroupFolds; j0 += NF) {          // (constant indices into the argument block: scalar loads, no scratch copy)
-        if (j0 >= a.nfold) break;                              // wave-uniform
-        int64_t x[NF][K];
-#pragma unroll
-        for (int f = 0; f < NF; f++) {
-            if (j0 + f >= a.nfold) break;
-            const Src d = a.data[j0 + f];
-            if (a.kind[j0 + f] == 3) {
-#pragma unroll
-                for (int j = 0; j < K; j++) x[f][j] = 1;
-            } else if (((vec16 >> (j0 + f)) & 1u) && nv == K) {
-                const ll2 *q = (const ll2 *)((const int64_t *)d.p + e0);
-#pragma unroll
-                for (int j = 0; j < K; j += 2) { const ll2 t = q[j >> 1]; x[f][j] = t.x; x[f][j + 1] = t.y; }
-            } else {
-#pragma unroll
-                for (int j = 0; j < K; j++) x[f][j] = ld(d, j < nv ? e0 + j : (e0 < m ? e0 : 0));
-            }
-        }
-#pragma unroll
-        for (int f = 0; f < NF; f++) {
-            if (j0 + f >= a.nfold) break;
-            const int kind = a.kind[j0 + f];
-            int64_t *out = a.out[j0 + f];
-            if (kind == 4) {                                   // FoldChoose: the first value of every run
-                int64_t g = B - 1;
-#pragma unroll
-                for (int j = 0; j < K; j++)
-                    if ((hb >> j) & 1u) { g++; GF_STORE(g, x[f][j]); }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-                for (int k = lane; k < ngw; k += kWave) out[Bw + k] = stage[wave][k];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();      // (the area is the next fold's)
-                continue;
-            }
-            const int rk = kind == 1 ? R_MIN : kind == 2 ? R_MAX : R_SUM;
-            by_reduction(rk, [&](auto rc) {
-                constexpr int R = decltype(rc)::value;
-                int64_t acc = r_identity(R), pre = r_identity(R), g = B - 1;
-                bool started = false;
-#pragma unroll
-                for (int j = 0; j < K; j++) {
-                    if ((hb >> j) & 1u) {                      // (a head is always inside the vector)
-                        if (started) GF_STORE(g, acc); else pre = acc;          // a run that began and ended in my chunk: stored at once
-                        g++; acc = x[f][j]; started = true;
-                    } else if (j < nv) {
-                        acc = r_combine(R, acc, x[f][j]);
-                    }
-                }
-                const int64_t tail = started ? acc : r_identity(R);         // open at my chunk's end (group g)
-                int64_t S = started ? pre : acc;                            // continues what was open before my chunk (group B - 1)
-#pragma unroll
-                for (int off = 1; off < kWave; off <<= 1) {
-                    const int64_t y = __shfl_up(S, off, kWave);
-                    if (lane - off >= seg0) S = r_combine(R, S, y);
-                }
-                // S of a lane with a head (or of lane 63) = everything between the previous head lane and this lane's first head
-                const int64_t cont = __shfl(S, fetch_from, kWave);
-                if (c != 0) {
-                    if (next_head >= 0) GF_STORE(g, r_combine(R, tail, cont));                                  // the run ends inside the wave
-                    else atomic_combine(R, &out[g], lane == kWave - 1 ? tail : r_combine(R, tail, cont));    // it may go on in the next wave
-                    if (first_head_lane && B > 0) atomic_combine(R, &out[B - 1], S);                         // ... and this one came from an earlier wave
-                } else if (headlanes == 0 && lane == kWave - 1 && B > 0) {
-                    atomic_combine(R, &out[B - 1], S);                                                       // a wave inside one long run
-                }
-            });
-            // every group but the wave's last one has ended inside the wave and lies in the staging area: consecutive lanes store them
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-            for (int k = lane; k < ngw - 1; k += kWave) out[Bw + k] = stage[wave][k];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-        }
-    }
+    constexpr bool WIDE = false;
+    int64_t *const *const out_hi = nullptr;
+#include "vdl_group_fold.inc"
 }
 hipError_t launch_group_fold(const GroupFoldArgs &a, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s) {
     (void)hipGetLastError();
     const int64_t nb = (m + compact_tile() - 1) / compact_tile();
     if (nb <= 0 || a.nfold <= 0) return hipSuccess;
     if (a.nfold > kMaxGroupFolds) return hipErrorInvalidValue;
-    unsigned vec16 = 0;
-    for (int f = 0; f < a.nfold; f++)
-        if (a.data[f].kind == SRC_I64 && ((uintptr_t)a.data[f].p & 15u) == 0) vec16 |= 1u << f;
+    const unsigned vec16 = group_fold_vec16(a);
     if (a.nfold <= 2) k_group_fold<2><<<(int)(nb * kGroupSplit), 256, 0, s>>>(a, vec16, heads, m, offsets);
     else k_group_fold<4><<<(int)(nb * kGroupSplit), 256, 0, s>>>(a, vec16, heads, m, offsets);
     return launch_status();
@@ -1396,162 +1169,10 @@ static hipError_t launch_maxscan(int64_t *x, int64_t n, int64_t *scratch /* maxs
     return hipGetLastError();
 }
 
-__device__ __forceinline__ void atomic_combine(int rk, int64_t *addr, int64_t v) {
-    if (rk == R_SUM) atomicAdd((unsigned long long *)addr, (unsigned long long)v);
-    else if (rk == R_MIN) atomicMin((long long *)addr, (long long)v);
-    else atomicMax((long long *)addr, (long long)v);
-}
-
-// (vdl_fold_wide.hip holds a copy of this kernel for FoldSum with a second sum, k_wide_seg_fold: a fix here belongs there too.)
-// kind: 0 sum, 1 min, 2 max, 3 count, 4 choose-pass (min over slot index of the data)
-// Each wave walks a contiguous chunk of words and carries the value of the run that is open at a word's last lane
-// into the next word, so a run costs one atomic per wave it touches instead of one per 64 slots: with few long runs
-// (dense GROUP BY domains) the per-word atomics all landed on the same handful of addresses and serialised.
+// the segmented fold (vdl_fold_body.h); kind: 0 sum, 1 min, 2 max, 3 count, 4 choose-pass (min over slot index of the data)
 __global__ __launch_bounds__(256) void k_seg_fold(int kind, Src d, const uint64_t *vd, const uint64_t *vc, const uint64_t *heads,
                                                   const int64_t *wordhd, int64_t n, int64_t *out, uint64_t *vout) {
-    constexpr int U = kGatherUnroll;
-    const int rk_rt = (kind == 1 || kind == 4) ? R_MIN : kind == 2 ? R_MAX : R_SUM;
-    const int64_t nw = (n + 63) >> 6;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x / kWave);
-    const int64_t g = wave_index();
-    const int64_t per = (nw + nwaves - 1) / nwaves;
-    const int64_t w_end = (g + 1) * per < nw ? (g + 1) * per : nw;
-    const uint64_t upto = lane == 63 ? ~0ull : ((2ull << lane) - 1);        // lanes at or before mine
-    by_kind(d.kind, [&](auto kd) { by_reduction(rk_rt, [&](auto rc) {
-        constexpr int rk = decltype(rc)::value;
-        int64_t carry_h = -1, carry_x = r_identity(rk);       // wave-uniform: the run still open after the previous word
-        for (int64_t w0 = g * per; w0 < w_end; w0 += U) {
-            // A long run (a dense-domain GROUP BY has a handful over millions of slots): while the next 16 (or 8) words begin no
-            // run, hold a value in every slot and continue the run this wave carries, their 1024 (512) values are simply reduced --
-            // lanes 0..15 look one word each, then every lane loads 16 (8) consecutive values with 16-byte loads: 8 (4) KB per wave
-            // in flight instead of the 2 KB of the word-by-word path below, whose lane = slot layout the segments need
-            // (60 M rows in 32 runs: 175 -> ~110 us).
-            if (carry_h >= 0 && (kind >= 3 || (decltype(kd)::value == SRC_I64 && ((uintptr_t)d.p & 15u) == 0))) {
-                bool fast = false;
-                if (lane < 16) {
-                    const int64_t w = w0 + lane;
-                    if (w < w_end && ((w + 1) << 6) <= n)
-                        fast = heads[w] == 0 && (!vc || vc[w] == ~0ull) && (!vd || vd[w] == ~0ull) && w > 0 && wordhd[w - 1] == carry_h;
-                }
-                const unsigned fm = (unsigned)(__ballot(fast) & 0xFFFFull);
-                const int K = fm == 0xFFFFu ? 16 : (fm & 0xFFu) == 0xFFu ? 8 : 0;
-                if (K) {
-                    int64_t t = r_identity(rk);
-                    if (kind < 3) {
-                        typedef long long i64x2 __attribute__((ext_vector_type(2)));
-                        const i64x2 *base = (const i64x2 *)((const int64_t *)d.p + (w0 << 6)) + lane;
-                        i64x2 v[8];
-#pragma unroll
-                        for (int j = 0; j < 8; j++) if (j < K / 2) v[j] = base[j * kWave];
-#pragma unroll
-                        for (int j = 0; j < 8; j++) if (j < K / 2) t = r_combine(rk, t, r_combine(rk, v[j].x, v[j].y));
-                        t = __shfl(wave_reduce(t, rk), 0, kWave);
-                    } else t = kind == 3 ? (int64_t)K * 64 : (w0 << 6);
-                    carry_x = r_combine(rk, carry_x, t);
-                    w0 += K - U;
-                    continue;
-                }
-            }
-            // operands of U words first (the words of a wave are processed in order: the carried run links them)
-            uint64_t hw_[U], okw_[U];
-            int64_t x_[U], prev_[U];
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const int64_t w = w0 + u < w_end ? w0 + u : w_end - 1;
-                const int64_t i = (w << 6) + lane;
-                hw_[u] = heads[w];
-                prev_[u] = w > 0 ? wordhd[w - 1] : -1;
-                const int64_t rem = n - (w << 6);
-                okw_[u] = rem < 64 ? (1ull << rem) - 1 : ~0ull;
-                x_[u] = kind < 3 ? ldk<decltype(kd)::value>(d, i < n ? i : 0) : (kind == 3 ? 1 : i);
-            }
-            if (vc) {
-                uint64_t t[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) t[u] = vc[w0 + u < w_end ? w0 + u : w_end - 1];
-#pragma unroll
-                for (int u = 0; u < U; u++) okw_[u] &= t[u];
-            }
-            if (vd) {
-                uint64_t t[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) t[u] = vd[w0 + u < w_end ? w0 + u : w_end - 1];
-#pragma unroll
-                for (int u = 0; u < U; u++) okw_[u] &= t[u];
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                if (w0 + u >= w_end) break;                    // wave-uniform
-                const int64_t w = w0 + u;
-                const uint64_t hw = hw_[u];
-                if (hw == 0 && okw_[u] == ~0ull && carry_h >= 0 && prev_[u] == carry_h) {
-                    // no run begins in this word and all 64 slots take part: the word continues the run the wave carries (long
-                    // runs -- a dense-domain GROUP BY has a handful -- are nearly all such words): one wave reduction, no segments
-                    carry_x = r_combine(rk, carry_x, __shfl(wave_reduce(x_[u], rk), 0, kWave));
-                    continue;
-                }
-                const uint64_t hm = hw & upto;                 // heads at or before this lane
-                const int64_t h = hm ? (w << 6) + 63 - __clzll((long long)hm) : prev_[u];
-                const bool ok = ((okw_[u] >> lane) & 1ull) != 0 && h >= 0;
-                int64_t x = ok ? x_[u] : r_identity(rk);
-                // lane segments = maximal stretches of consecutive active lanes with one head; an EPS slot
-                // inside a run splits it into several segments, each adds its part to the same out[h]
-                const int64_t hp = __shfl_up(h, 1, kWave);
-                const uint64_t okm = __ballot(ok);
-                const bool okp = lane > 0 && ((okm >> (lane - 1)) & 1ull);
-                const bool starts = lane == 0 || !ok || !okp || hp != h;
-                const uint64_t sm = __ballot(starts) & upto;
-                const int seg0 = 63 - __clzll((long long)sm);  // first lane of my segment (bit 0 is always set)
-#pragma unroll
-                for (int off = 1; off < kWave; off <<= 1) {
-                    const int64_t y = __shfl_up(x, off, kWave);
-                    if (lane - off >= seg0) x = r_combine(rk, x, y);
-                }
-                const int64_t hn = __shfl_down(h, 1, kWave);
-                const bool okn = lane < kWave - 1 && ((okm >> (lane + 1)) & 1ull);
-                const bool tail = ok && (lane == kWave - 1 || !okn || hn != h);
-                // runs that begin and end inside this word with every slot taking part are one segment nobody else adds
-                // to: a plain store and one validity update per word (a sparse GROUP BY has ~30 such runs per word,
-                // and their atomics on out[] and on the same word of vout[] were most of the kernel)
-                bool whole = false;
-                if ((hw >> lane) & 1) {
-                    const uint64_t later = lane == kWave - 1 ? 0 : hw >> (lane + 1);
-                    if (later) {
-                        const int q = lane + __ffsll((long long)later);       // lane of the next head (<= 63)
-                        const uint64_t range = (1ull << q) - (1ull << lane);
-                        whole = (okm & range) == range;
-                    }
-                }
-                const uint64_t wholem = __ballot(whole);
-                const bool mine = tail && ((wholem >> seg0) & 1);              // my segment is such a run
-                // the run carried over from the previous word: continue it in this word's first segment, or write it out
-                if (carry_h >= 0) {
-                    const bool ok0 = (okm & 1ull) != 0;
-                    const int64_t h0 = __shfl(h, 0, kWave);
-                    if (ok0 && h0 == carry_h) {
-                        if (tail && seg0 == 0) x = r_combine(rk, x, carry_x);
-                    } else if (lane == 0) {
-                        atomic_combine(rk, &out[carry_h], carry_x);
-                        atomicOr((unsigned long long *)&vout[carry_h >> 6], 1ull << (carry_h & 63));
-                    }
-                    carry_h = -1;
-                }
-                if ((okm >> (kWave - 1)) & 1ull) { carry_h = __shfl(h, kWave - 1, kWave); carry_x = __shfl(x, kWave - 1, kWave); }   // lane 63 is that segment's tail
-                if (mine) {
-                    out[h] = x;
-                } else if (tail && lane != kWave - 1) {
-                    atomic_combine(rk, &out[h], x);
-                    atomicOr((unsigned long long *)&vout[h >> 6], 1ull << (h & 63));
-                }
-                if (lane == 0 && wholem) atomicOr((unsigned long long *)&vout[w], wholem);   // runs from other words may set bits here too
-            }
-        }
-        if (carry_h >= 0 && lane == 0) {
-            atomic_combine(rk, &out[carry_h], carry_x);
-            atomicOr((unsigned long long *)&vout[carry_h >> 6], 1ull << (carry_h & 63));
-        }
-    }); });
+    seg_fold_body<false>(kind, d, vd, vc, heads, wordhd, n, out, nullptr, vout);
 }
 
 __global__ void k_seg_fill(int64_t *out, int64_t v, int64_t n) {
@@ -1577,13 +1198,6 @@ __global__ void k_seg_choose_fix(Src d, const uint64_t *vout, int64_t n, int64_t
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
         if (bit(vout, i)) out[i] = ld(d, out[i]);
-}
-
-static int seg_fold_grid(int64_t n) {            // a few thousand waves, each with a contiguous chunk of at least a few words
-    const int64_t nw = (n + 63) >> 6;
-    int64_t g = (nw + 15) / 16;                  // >= 4 words per wave (4 waves per block)
-    if (g > 2048) g = 2048;
-    return (int)(g < 1 ? 1 : g);
 }
 
 // scratch: heads bitmap (nwords) and wordhd (nwords + maxscan_blocks(nwords) int64) supplied by the caller

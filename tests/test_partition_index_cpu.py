@@ -48,7 +48,7 @@ def _one(pattern, text, what):
 
 
 def test_the_level_tests_sizes_still_sit_on_the_kernels_thresholds():
-    part, ops, index = _source("vdl_partition.hip"), _source("vdl_ops.hip"), _source("vdl_partition_index.h")
+    part, ops, index, folds = _source("vdl_partition.hip"), _source("vdl_ops.hip"), _source("vdl_partition_index.h"), _source("vdl_fold_body.h")
     scan = _one(r"void k_scan_counts\(.*?\n}\n", ops, "k_scan_counts")
     heads = _one(r"void k_sorted_heads_counted\(.*?\n}\n", part, "k_sorted_heads_counted")
     seen = {
@@ -56,7 +56,7 @@ def test_the_level_tests_sizes_still_sit_on_the_kernels_thresholds():
         "VDL_PART_STEPS": int(_one(r"#ifndef VDL_PART_STEPS\n#define VDL_PART_STEPS (\d+)\n#endif", part, "VDL_PART_STEPS")),
         "kFanBits": int(_one(r"constexpr int kFanBits = (\d+),", index, "kFanBits")),
         "kFenLevels": int(_one(r"kFenLevels = (\d+);", index, "kFenLevels")),
-        "kCompactWords": int(_one(r"constexpr int kCompactWords = (\d+);", ops, "kCompactWords")),
+        "kCompactWords": int(_one(r"constexpr int kCompactWords = (\d+);", folds, "kCompactWords")),
         "one-launch compaction up to kWave tiles": _one(r"if \(nb <= (\w+)\) \{[^\n]*\n\s*k_compact_count_scan<<<", ops, "launch_compact_offsets' threshold"),
         "K of k_scan_counts": int(_one(r"constexpr int K = (\d+);", scan, "K in k_scan_counts")),
         "block of k_scan_counts": int(_one(r"base \+= (\d+) \* K\)", scan, "the trip of k_scan_counts")),

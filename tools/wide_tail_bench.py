@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """What wide sums cost in the GROUP BY tail (DESIGN.md section 5.17 "The tail"): TPC-H Q3 over the catalog datagen.register_q3_columns
-builds in place, and the group-tail micro case of tools/op_roofline.py (a dense-domain Partition of 32 buckets, two Scatters, one
-FoldSum over the runs) over the generator's lineitem -- with the switch off and in mode 1 with the tail switch, and, with --parent DIR,
-against a build of the parent commit (DIR holds that commit's mplan2vdl_amd package with its libvdl.so built).  Taken as ALTERNATING
+builds in place (k_group_fold), and two micro cases of tools/op_roofline.py over the generator's lineitem with fusion off -- `tail`, its
+group tail (a dense-domain Partition of 32 buckets, two Scatters, one FoldSum over the runs: k_seg_fold), and `global`, its statements
+17-20 (one single-run FoldSum over a filtered vector: k_fold_global) -- with the switch off and in mode 1 with the tail switch, and, with
+--parent DIR, against a build of the parent commit, off and in mode 1 as well (DIR holds that commit's mplan2vdl_amd package with its
+libvdl.so built): this tree's off is held against the parent's off, its wide against the parent's wide.  Taken as ALTERNATING
 FRESH PROCESSES, `--repeats` per side: every process builds its columns, warms up, times `--steps` queries on the host (profiling off:
 no synchronisation between statements), and then runs three times more with per-statement events for the time of the fold statements
 (FoldSum / Min / Max / Count / Choose: the folds of one GROUP BY share a launch, which is timed under the first of them).
@@ -27,6 +29,11 @@ TAIL = "\n".join(["1,Load,lineitem.l_quantity", "2,Project,val,Id 1,l_quantity",
                   "21,RangeV,val,31,Id 4,0", "22,BitwiseAnd,val,Id 4,val,Id 21,val", "23,RangeC,val,0,32,1", "24,Partition,val,Id 22,val,Id 23,val",
                   "25,RangeV,val,0,Id 22,1", "26,Scatter,Id 22,Id 25,val,Id 24,val", "27,Scatter,Id 2,Id 25,val,Id 24,val",
                   "28,FoldSum,val,Id 26,val,Id 27,val", "29,Project,s,Id 28,val", "30,MaterializeCompact,Id 29"]) + "\n"
+GLOBAL = "\n".join(["3,Load,lineitem.l_extendedprice", "4,Project,val,Id 3,l_extendedprice", "5,Load,lineitem.l_discount", "6,Project,val,Id 5,l_discount",
+                    "12,RangeV,val,5,Id 6,0", "13,Greater,val,Id 6,val,Id 12,val", "14,RangeV,val,0,Id 13,1", "15,FoldSelect,val,Id 14,val,Id 13,val",
+                    "17,Gather,Id 4,Id 15,val", "18,RangeV,val,0,Id 17,0", "19,FoldSum,val,Id 18,val,Id 17,val", "20,Project,s,Id 19,val",
+                    "21,MaterializeCompact,Id 20"]) + "\n"
+MICRO = {"tail": (TAIL, ("lineitem.l_quantity", "lineitem.l_extendedprice")), "global": (GLOBAL, ("lineitem.l_extendedprice", "lineitem.l_discount"))}
 
 
 def child(args):
@@ -44,12 +51,13 @@ def child(args):
     else:
         rows = args.rows or datagen.LINEITEM_ROWS[args.sf]
         keep = None
-        for name in ("lineitem.l_quantity", "lineitem.l_extendedprice"):
+        text, columns = MICRO[args.case]
+        for name in columns:
             eng.generate(datagen.LINEITEM[name], 0, rows)
-        plan = eng.parse(TAIL)
+        plan = eng.parse(text)
         plan.set_fusion(False)
     if args.mode:
-        plan.set_wide_sums(args.mode, tail=True)               # (never called on the parent's package: it has no such switch)
+        plan.set_wide_sums(args.mode, tail=True)
     out = {"case": args.case, "mode": args.mode, "rows": rows, "root": root}
     try:
         plan.execute()
@@ -92,7 +100,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--case", default="q3")
-    ap.add_argument("--cases", default="q3,tail")
+    ap.add_argument("--cases", default="q3,tail,global")
     ap.add_argument("--mode", type=int, default=0)
     ap.add_argument("--root", default=None)
     ap.add_argument("--sf", default="sf10")
@@ -100,7 +108,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--parent", default=None, help="a tree of the parent commit, built: the third side")
+    ap.add_argument("--parent", default=None, help="a tree of the parent commit, built: two more sides, off and wide")
     ap.add_argument("--timeout", type=int, default=300)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -121,7 +129,8 @@ def main():
             raise SystemExit(1)
         return json.loads(p.stdout.decode().strip().splitlines()[-1])
 
-    sides = ([("parent", 0, args.parent)] if args.parent else []) + [("off", 0, None), ("wide", 1, None)]
+    sides = ([("parent", 0, args.parent), ("parent wide", 1, args.parent)] if args.parent else []) + [("off", 0, None), ("wide", 1, None)]
+    pairs = [("off", "parent"), ("wide", "parent wide")] if args.parent else []      # this tree's side, the parent's side it is held against
     cases = [c for c in args.cases.split(",") if c]
     got = {}
     try:
@@ -133,7 +142,7 @@ def main():
                         say("FAILED: %s %s: [%d] %s" % (case, side, r["error_code"], r["message"]))
                         raise SystemExit(1)
                     got.setdefault((case, side), []).append(r)
-                    say("round %d %-4s %-6s wall %s us  fold statements %s us" % (rep, case, side, spread(r["wall_us"]), spread(r["fold_us"])))
+                    say("round %d %-6s %-11s wall %s us  fold statements %s us" % (rep, case, side, spread(r["wall_us"]), spread(r["fold_us"])))
         say()
         base = "parent" if args.parent else "off"
         for case in cases:
@@ -144,15 +153,17 @@ def main():
                 rs = got[(case, side)]
                 wall = [statistics.median(r["wall_us"]) for r in rs]
                 fold = [statistics.median(r["fold_us"]) for r in rs]
-                med[side], width[side] = (statistics.median(wall), statistics.median(fold)), max(wall) - min(wall)
-                say("  %-6s wall %s   fold statements %s" % (side, spread(wall), spread(fold)))
+                med[side], width[side] = (statistics.median(wall), statistics.median(fold)), (max(wall) - min(wall), max(fold) - min(fold))
+                say("  %-11s wall %s   fold statements %s" % (side, spread(wall), spread(fold)))
             for side, _, _ in sides:
                 if side != base:
                     say("  %s / %s: wall %.3f  fold statements %.3f" % (side, base, med[side][0] / med[base][0], med[side][1] / max(med[base][1], 1e-9)))
-            if args.parent:
-                d = med["off"][0] - med["parent"][0]
-                say("  switch off - parent: %+.1f us wall; spread of the repeats: parent %.1f us, switch off %.1f us -> %s" %
-                    (d, width["parent"], width["off"], "within the spread" if abs(d) <= max(width["parent"], width["off"]) else "OUTSIDE the spread"))
+            for mine, theirs in pairs:                         # the margin: the larger of the two sides' own spread over the repeats
+                for what, k in (("wall", 0), ("fold statements", 1)):
+                    d = med[mine][k] - med[theirs][k]
+                    say("  %s - %s, %s: %+.1f us; spread of the repeats: %s %.1f us, %s %.1f us -> %s" %
+                        (mine, theirs, what, d, theirs, width[theirs][k], mine, width[mine][k],
+                         "within the spread" if abs(d) <= max(width[theirs][k], width[mine][k]) else "OUTSIDE the spread"))
             top = got[(case, "wide")][-1].get("largest_revenue")
             if top is not None:
                 say("  largest revenue: %d = %.3e of INT64_MAX (exact, mode 1)" % (top, top / I64_MAX))
