@@ -294,7 +294,7 @@ int vdl_exchange_finish(vdl_ctx *c, vdl_plan *p, const void *dev_recv, int64_t n
         // usually every travelling row holds a value in every vector (mask word = all ones): no bitmaps needed then
         bool all_valid = n_recv == 0 || m <= 1 || ex.skip_mask;
         if (!all_valid) {
-            BufP scratch = dev_alloc(c, sizeof(int64_t) * 3 * (size_t)fold_scratch_blocks());
+            BufP scratch = dev_alloc(c, sizeof(int64_t) * (size_t)fold_global_scratch_words(false));
             BufP r = dev_alloc(c, 3 * sizeof(int64_t));
             Src mk; mk.p = in + (int64_t)m * n_recv; mk.kind = SRC_I64;
             HIP_CHECK(launch_fold_global(1 /* min */, mk, nullptr, nullptr, n_recv, (int64_t *)scratch->p, (int64_t *)r->p, c->stream));

@@ -9,13 +9,23 @@
 // Order-independent and deterministic, because both sums are.
 //
 // k_wide_seg_fold and k_wide_fold_global_finish are the WIDE = true forms of the bodies in vdl_fold_body.h, k_wide_fold_global and
-// k_wide_group_fold those of the texts in vdl_fold_global.inc and vdl_group_fold.inc; the WIDE = false forms are the kernels of vdl_ops.hip.  One text each, so the same layouts, chunks, segments,
-// carried runs and atomics.
+// k_wide_group_fold those of the texts in vdl_fold_global.inc and vdl_group_fold.inc; the WIDE = false forms are the kernels of vdl_ops.hip.
+// One text each, so the same layouts, chunks, segments, carried runs and atomics.
+//
+// Nobody calls the three fold launchers here by name but launch_fold_global, launch_fold_runs and launch_group_fold of vdl_ops.hip, for a
+// call that brings a high output (vdl_kernels.h: one interface per route for both forms).  Each returns FINISHED high words: the finish
+// step of the global fold joins, the segmented fold joins at the heads, the group fold runs k_wide_join over its packed results.
 #include "vdl_device.h"
 #include "vdl_fold_body.h"
 #include "vdl_kernels.h"
 
 namespace vdl {
+
+// k_wide_group_fold's argument block: GroupFoldArgs and one high output per member, which the plain kernel's block does not carry
+struct WideGroupFoldArgs {
+    GroupFoldArgs g;
+    int64_t *out_hi[kMaxGroupFolds] = {};
+};
 
 namespace {
 
@@ -88,7 +98,7 @@ __global__ __launch_bounds__(256) void k_wide_seg_fold(Src d, const uint64_t *vd
     seg_fold_body<true>(0, d, vd, vc, heads, wordhd, n, out, out_hi, vout);
 }
 
-// ---- k_group_fold, wide: a FoldSum member with out_hi set leaves the sum of its high halves there ----
+// ---- k_group_fold, wide: a FoldSum member with out_hi set leaves the sum of its high halves there (joined afterwards) ----
 template <int NF>
 __global__ __launch_bounds__(256) void k_wide_group_fold(WideGroupFoldArgs A, unsigned vec16, const uint64_t *heads, int64_t m, const int64_t *offsets) {
     constexpr bool WIDE = true;
@@ -101,7 +111,6 @@ int wf_grid(int64_t n, int per_lane) { return grid_for(n, kWfBlock, per_lane); }
 
 }  // namespace
 
-int wide_fold_scratch_blocks() { return kFoldBlocks; }
 hipError_t launch_wide_fold_global(Src d, const uint64_t *vd, const uint64_t *vc, int64_t n, int64_t *scratch, int64_t *result, int64_t *result_hi, hipStream_t s) {
     (void)hipGetLastError();
     const int grid = fold_global_grid(n);
@@ -119,19 +128,22 @@ hipError_t launch_wide_fold_runs(Src d, const uint64_t *vd, const uint64_t *vc, 
     k_wide_join_heads<<<grid_for(nw, 256, 1), 256, 0, s>>>(heads, nw, out, out_hi);
     return launch_status();
 }
-hipError_t launch_wide_group_fold(const WideGroupFoldArgs &a, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s) {
+hipError_t launch_wide_group_fold(const GroupFoldArgs &g, int64_t *const *out_hi, int64_t groups, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s) {
     (void)hipGetLastError();
     const int64_t nb = (m + compact_tile() - 1) / compact_tile();
-    if (nb <= 0 || a.g.nfold <= 0) return hipSuccess;
-    if (a.g.nfold > kMaxGroupFolds) return hipErrorInvalidValue;
-    const unsigned vec16 = group_fold_vec16(a.g);
-    if (a.g.nfold <= 2) k_wide_group_fold<2><<<(int)(nb * kGroupSplit), 256, 0, s>>>(a, vec16, heads, m, offsets);
+    if (nb <= 0 || g.nfold <= 0) return hipSuccess;
+    if (g.nfold > kMaxGroupFolds) return hipErrorInvalidValue;
+    WideGroupFoldArgs a;
+    a.g = g;
+    for (int j = 0; j < g.nfold; j++) {
+        if (out_hi[j] && g.kind[j] != 0) return hipErrorInvalidValue;
+        a.out_hi[j] = out_hi[j];
+    }
+    const unsigned vec16 = group_fold_vec16(g);
+    if (g.nfold <= 2) k_wide_group_fold<2><<<(int)(nb * kGroupSplit), 256, 0, s>>>(a, vec16, heads, m, offsets);
     else k_wide_group_fold<4><<<(int)(nb * kGroupSplit), 256, 0, s>>>(a, vec16, heads, m, offsets);
-    return launch_status();
-}
-hipError_t launch_wide_join(const int64_t *lo, int64_t *hi, int64_t n, hipStream_t s) {
-    (void)hipGetLastError();
-    if (n > 0) k_wide_join<<<wf_grid(n, 4), kWfBlock, 0, s>>>(lo, hi, n);
+    for (int j = 0; j < g.nfold && groups > 0; j++)           // the join at the packed results
+        if (out_hi[j]) k_wide_join<<<wf_grid(groups, 4), kWfBlock, 0, s>>>(g.out[j], out_hi[j], groups);
     return launch_status();
 }
 hipError_t launch_wide_sign(const int64_t *lo, int64_t *hi, int64_t n, hipStream_t s) {

@@ -962,10 +962,10 @@ struct GenExec {
     }
 
     // ---- wide sums in the tail (vdl_plan_set_wide_sums_tail; DESIGN.md section 5.17 "The tail") ----------------------------------------
-    // A FoldSum result carries bits 64..127 of its exact sum in DVec::hi.  The accumulation is the split of vdl_fold_wide.hip: every
-    // FoldSum site launches the wide form of its kernel (launch_wide_group_fold / _fold_runs / _fold_global) INSTEAD of the plain one;
-    // it loads each term once and keeps the wrapped sum and the sum of the high halves x >> 32 side by side, and the join makes the
-    // high word per result (at the packed results, at the heads, in the finish step).  Project, Shuffle and
+    // A FoldSum result carries bits 64..127 of its exact sum in DVec::hi.  The accumulation is the split of vdl_fold_wide.hip: a
+    // FoldSum hands its fold route's launcher (launch_group_fold / _fold_runs / _fold_global) a high output, which selects the wide form
+    // of the kernel INSTEAD of the plain one; it loads each term once and keeps the wrapped sum and the sum of the high halves x >> 32
+    // side by side, and the launcher returns finished high words.  Project, Shuffle and
     // MaterializeCompact carry the high words; a RangeV takes the shape only; every other reader goes through wide_consume, which
     // queues the fits check and drops them.  The checks' flags are read once, at the run's end (wide_read_checks).
     bool wide_on = false;
@@ -985,15 +985,6 @@ struct GenExec {
             throw Error(VDL_ERR_UNSUPPORTED, "wide sums: FoldSum (Id " + std::to_string(n.id) + ") folds " + std::to_string(count) + " entries, more than the 2^31 the split of "
                                              "the terms into 32-bit halves is exact for; clear the switch to run it");
         wide_routes[route]++;
-    }
-    // a global FoldSum, wide: the record {value, slot, count} in o.data as ever with the value's high word as its fourth word, and that
-    // word again in o.hi
-    void wide_fold_global(const Node &n, DVec &o, Src d, const uint64_t *vd, const uint64_t *vc, int64_t count) {
-        wide_fold_begin(n, count, "k_fold_global");
-        o.data = dev_alloc(c, 4 * sizeof(int64_t));
-        BufP scratch = dev_alloc(c, sizeof(int64_t) * 4 * (size_t)wide_fold_scratch_blocks());
-        o.hi = dev_alloc(c, sizeof(int64_t));
-        HIP_CHECK(launch_wide_fold_global(d, vd, vc, count, (int64_t *)scratch->p, (int64_t *)o.data->p, (int64_t *)o.hi->p, s));
     }
     void wide_queue_check(const DVec &v, int what, const std::string &who) {
         if ((int)wide_checks.size() == kWideFlags) wide_read_checks();      // (a round trip of its own: 64 consumed sums in one run)
@@ -1055,13 +1046,46 @@ struct GenExec {
         }
     }
 
+    // ---- FoldSum / Min / Max / Count / Choose: every route, one helper per launcher.  Only the helpers ask whether a fold is wide. ----
+    static int fold_kind(Op op) { return op == Op::FoldSum ? 0 : op == Op::FoldMin ? 1 : op == Op::FoldMax ? 2 : op == Op::FoldCount ? 3 : op == Op::FoldChoose ? 4 : -1; }
+    static bool is_fold(Op op) { return fold_kind(op) >= 0; }
+
+    // One run over `count` operands (launch_fold_global): the ONEHOT record {value, slot, count} of a vector of nslots slots.  A wide
+    // FoldSum's record has the value's high word as its fourth word, and that word again in hi.
+    DVec fold_single_run(const Node &n, int64_t nslots, Src d, const uint64_t *vd, const uint64_t *vc, int64_t count) {
+        const int kind = fold_kind(n.op);
+        const bool wide = wide_on && kind == 0;
+        if (wide) wide_fold_begin(n, count, "k_fold_global");
+        DVec o;
+        o.kind = DVec::ONEHOT; o.n = nslots;
+        o.data = dev_alloc(c, sizeof(int64_t) * (size_t)fold_record_words(wide));
+        BufP scratch = dev_alloc(c, sizeof(int64_t) * (size_t)fold_global_scratch_words(wide));
+        if (wide) o.hi = dev_alloc(c, sizeof(int64_t));
+        HIP_CHECK(launch_fold_global(kind, d, vd, vc, count, (int64_t *)scratch->p, (int64_t *)o.data->p, s, wide ? (int64_t *)o.hi->p : nullptr));
+        return o;
+    }
+    // The runs whose heads / wordhd (launch_fold_heads) are given, over `count` slots or entries (launch_fold_runs): the values at the
+    // run heads, their bits set in vout (pre-zeroed), and a wide FoldSum's high words beside the values.
+    struct Folded { BufP data, hi; };
+    Folded fold_given_heads(const Node &n, Src d, const uint64_t *vd, const uint64_t *vc, const BufP &heads, const BufP &wordhd, int64_t count, const BufP &vout) {
+        const int kind = fold_kind(n.op);
+        const bool wide = wide_on && kind == 0;
+        if (wide) wide_fold_begin(n, count, "k_seg_fold");
+        const size_t bytes = sizeof(int64_t) * (size_t)std::max<int64_t>(count, 1);
+        Folded f;
+        f.data = dev_alloc(c, bytes);
+        if (wide) f.hi = dev_alloc(c, bytes);
+        HIP_CHECK(launch_fold_runs(kind, d, vd, vc, (const uint64_t *)heads->p, (const int64_t *)wordhd->p, count, (int64_t *)f.data->p, (uint64_t *)vout->p, s,
+                                   wide ? (int64_t *)f.hi->p : nullptr));
+        return f;
+    }
+
     // Fold `n` over m ENTRIES (every one holds a value, entry 0 starts the first run): control values at ctl, this fold's data at
     // dsrc.  sel = the selection the entries sit on (a prefix selection for vectors scattered into key order, or all n slots).
     // Results: SPARSE on the child selection of the run heads, packed.  Every fold of one GROUP BY shares the heads; with the
     // batch on they also share ONE launch (launch_group_fold) -- the sibling folds' operands are run ahead of their turn.
     DVec fold_entries(const Node &n, const SelP &sel, Src ctl_src, const void *ctl_key, const BufP &ctl_keep, Src dsrc, int64_t m, int64_t nslots) {
         auto V = [&](int id) -> const DVec & { return vec[(size_t)id]; };
-        const int kind = n.op == Op::FoldSum ? 0 : n.op == Op::FoldMin ? 1 : n.op == Op::FoldMax ? 2 : n.op == Op::FoldCount ? 3 : 4;
         // every entry holds a datum, so each run yields a result at its head: the run heads of this control
         // vector -- and the selection they form -- are computed once and shared by all folds over it
         // (a GROUP BY folds every aggregate over the same sorted key, Vlite.hs:1056-1060)
@@ -1090,7 +1114,7 @@ struct GenExec {
             for (int id : p->prog.order) {
                 const Node &f = p->prog.at(id);
                 if (id == n.id || f.a != n.a || (size_t)id >= needed_now.size() || !needed_now[(size_t)id] || done[(size_t)id]) continue;
-                if (f.op != Op::FoldSum && f.op != Op::FoldMin && f.op != Op::FoldMax && f.op != Op::FoldCount && f.op != Op::FoldChoose) continue;
+                if (!is_fold(f.op)) continue;
                 if (cur_over && cur_over->count(id)) continue;
                 ensure(f.b);
                 if (wide_on) wide_consume(f);                        // (a sibling runs here, not through exec)
@@ -1105,28 +1129,25 @@ struct GenExec {
             std::vector<BufP> outs(members.size()), his(members.size());
             const int64_t G = rh.count;
             for (size_t at = 0; at < members.size(); at += kMaxGroupFolds) {
-                WideGroupFoldArgs wa;
-                GroupFoldArgs &ga = wa.g;
+                GroupFoldArgs ga;
+                int64_t *out_hi[kMaxGroupFolds] = {};
                 for (size_t k = at; k < members.size() && k < at + kMaxGroupFolds; k++) {
-                    const Op fop = p->prog.at(members[k]).op;
-                    const int fk = fop == Op::FoldSum ? 0 : fop == Op::FoldMin ? 1 : fop == Op::FoldMax ? 2 : fop == Op::FoldCount ? 3 : 4;
+                    const Node &f = p->prog.at(members[k]);
+                    const int fk = fold_kind(f.op);
                     outs[k] = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(G, 1));
                     if (fk != 4 && G > 0)
                         HIP_CHECK(launch_fill_words((uint64_t *)outs[k]->p, fk == 1 ? (uint64_t)INT64_MAX : fk == 2 ? (uint64_t)INT64_MIN : 0ull, G, s));
-                    if (wide_on && fk == 0) {                      // (wide sums: the sum of the high halves lands beside the sum)
-                        wide_fold_begin(p->prog.at(members[k]), m, "k_group_fold");
+                    if (wide_on && fk == 0) {                      // (wide sums: the high words land beside the sums)
+                        wide_fold_begin(f, m, "k_group_fold");
                         his[k] = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(G, 1));
                         if (G > 0) HIP_CHECK(launch_fill_words((uint64_t *)his[k]->p, 0ull, G, s));
-                        wa.out_hi[ga.nfold] = (int64_t *)his[k]->p;
+                        out_hi[ga.nfold] = (int64_t *)his[k]->p;
                     }
                     ga.kind[ga.nfold] = fk; ga.data[ga.nfold] = srcs[k]; ga.out[ga.nfold] = (int64_t *)outs[k]->p;
                     ga.nfold++;
                 }
-                if (G > 0 && wide_on) HIP_CHECK(launch_wide_group_fold(wa, (const uint64_t *)rh.heads->p, m, (const int64_t *)rh.offsets->p, s));
-                else if (G > 0) HIP_CHECK(launch_group_fold(ga, (const uint64_t *)rh.heads->p, m, (const int64_t *)rh.offsets->p, s));
+                if (G > 0) HIP_CHECK(launch_group_fold(ga, (const uint64_t *)rh.heads->p, m, (const int64_t *)rh.offsets->p, s, wide_on ? out_hi : nullptr, G));
             }
-            for (size_t k = 0; k < members.size(); k++)
-                if (his[k]) HIP_CHECK(launch_wide_join((const int64_t *)outs[k]->p, (int64_t *)his[k]->p, G, s));
             for (size_t k = 1; k < members.size(); k++) {
                 vec[(size_t)members[k]] = make_sparse(rh.child, outs[k]);
                 vec[(size_t)members[k]].hi = his[k];
@@ -1143,21 +1164,73 @@ struct GenExec {
         }
         // FoldChoose takes a run's first element, and here every entry holds one: the values at the run heads, i.e. one
         // compaction by the head bitmap (every output column of a GROUP BY is such a fold, Vlite.hs:1056-1060)
-        if (kind == 4) return make_sparse(rh.child, compact_write(dsrc, rh.heads, m, rh.offsets, rh.count));
-        BufP data = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(m, 1));
-        BufP vout = zero_bitmap(m);
-        if (wide_on && kind == 0) {                         // the wide form: both sums in one pass, joined at the heads, packed like the values
-            wide_fold_begin(n, m, "k_seg_fold");
-            BufP high = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(m, 1));
-            HIP_CHECK(launch_wide_fold_runs(dsrc, nullptr, nullptr, (const uint64_t *)rh.heads->p, (const int64_t *)rh.wordhd->p, m,
-                                            (int64_t *)data->p, (int64_t *)high->p, (uint64_t *)vout->p, s));
-            DVec r = make_sparse(rh.child, compact_write(i64_src(data), rh.heads, m, rh.offsets, rh.count));
-            r.hi = compact_write(i64_src(high), rh.heads, m, rh.offsets, rh.count);
-            return r;
+        if (fold_kind(n.op) == 4) return make_sparse(rh.child, compact_write(dsrc, rh.heads, m, rh.offsets, rh.count));
+        const Folded f = fold_given_heads(n, dsrc, nullptr, nullptr, rh.heads, rh.wordhd, m, zero_bitmap(m));
+        DVec r = make_sparse(rh.child, compact_write(i64_src(f.data), rh.heads, m, rh.offsets, rh.count));
+        if (f.hi) r.hi = compact_write(i64_src(f.hi), rh.heads, m, rh.offsets, rh.count);      // (the high words, packed like the values)
+        return r;
+    }
+
+    // a Fold statement: which route it takes
+    DVec exec_fold(const Node &n) {
+        auto V = [&](int id) -> const DVec & { return vec[(size_t)id]; };
+        if (sparse_on && V(n.b).kind == DVec::SPARSE && V(n.a).kind == DVec::RANGE && V(n.a).step == 0 && V(n.a).n == V(n.b).n &&
+            V(n.b).sel->m > 0 && V(n.b).sel->idx && V(n.a).valid && V(n.a).valid == V(n.b).sel->bitmap) {
+            // one run over exactly the selected slots (the ungrouped aggregate of a filtered table, Vlite.hs:636-639):
+            // fold the entries; the result sits at the run's first slot = the selection's first slot
+            // (the record's slot is 0: the run starts at slot 0 of the vector, not at the selection's first slot)
+            const DVec &sd = V(n.b);
+            return fold_single_run(n, sd.n, i64_src(sd.data), nullptr, nullptr, sd.sel->m);
         }
-        HIP_CHECK(launch_fold_runs(kind, dsrc, nullptr, nullptr, (const uint64_t *)rh.heads->p, (const int64_t *)rh.wordhd->p, m,
-                                   (int64_t *)data->p, (uint64_t *)vout->p, s));
-        return make_sparse(rh.child, compact_write(i64_src(data), rh.heads, m, rh.offsets, rh.count));
+        const bool data_on_sel = V(n.a).kind == DVec::SPARSE &&
+                                 ((V(n.b).kind == DVec::SPARSE && V(n.a).sel == V(n.b).sel) ||
+                                  (V(n.b).kind == DVec::RANGE && V(n.b).step == 0 && V(n.b).n == V(n.a).n && subset(bitmap_of(V(n.a).sel), V(n.b).valid)));
+        // (the first run's result belongs in slot 0 of the vector: on the entries that is only the case when the selection
+        // starts at slot 0 -- always so for the prefix selections GROUP BY folds over; anything else takes the dense route)
+        if (sparse_on && data_on_sel && first_slot_of(V(n.a).sel) == 0) {
+            // runs skip EPS slots, so folding the m entries gives the same runs; results sit at run-first entries
+            const DVec &sc = V(n.a), &sd = V(n.b);
+            const SelP sel = sc.sel;
+            Src dsrc = sd.kind == DVec::SPARSE ? i64_src(sd.data) : src_of(sd);
+            return fold_entries(n, sel, i64_src(sc.data), sc.data->p, sc.data, dsrc, sel->m, sc.n);
+        }
+        // The same for a control vector that holds a value in EVERY slot (the key of a GROUP BY over an unfiltered table: Q18
+        // groups all lineitems by order): its n slots are the entries, the results live on the selection of the run heads.
+        // Only with the batch on and many short runs (fold_entries decides): a handful of long runs is what k_seg_fold is for.
+        if (sparse_on && group_batch_on && V(n.a).n > 0 && (V(n.a).kind == DVec::DENSE || V(n.a).kind == DVec::COLUMN) && !V(n.a).valid) {
+            const DVec &dc = V(n.a);
+            DVec dd = V(n.b);
+            if (dd.kind == DVec::EXPR && !dd.sel) dd = expr_force(dd);
+            const bool plain = (dd.kind == DVec::DENSE || dd.kind == DVec::COLUMN || dd.kind == DVec::RANGE) && !dd.valid && dd.n == dc.n;   // (all n slots are entries: a RANGE counts along them)
+            if (plain && sorted_heads.count(dc.kind == DVec::DENSE ? dc.data->p : dc.ptr)) {      // (the Partition saw it in order and counted its runs)
+                const SortedHeads &sh = sorted_heads[dc.kind == DVec::DENSE ? dc.data->p : dc.ptr];
+                if (sh.count * 64 >= dc.n)
+                    return fold_entries(n, prefix_selection(dc.n, dc.n), src_of(dc), dc.kind == DVec::DENSE ? dc.data->p : dc.ptr, dc.data, src_of(dd), dc.n, dc.n);
+            }
+        }
+        DVec ctl = densify(V(n.a)), d = densify(V(n.b));
+        if (ctl.n != d.n) throw Error(VDL_ERR_SHAPE, std::string(op_name(n.op, -1)) + " (Id " + std::to_string(n.id) + "): operand lengths differ");
+        if (ctl.kind == DVec::RANGE && ctl.step == 0) return fold_single_run(n, d.n, src_of(d), vp(d), vp(ctl), d.n);
+        // general control vector (grouped aggregates fold data scattered into key order)
+        const size_t nw = (size_t)std::max<int64_t>(nwords(d.n), 1);
+        DVec o;
+        o.kind = DVec::DENSE; o.n = d.n;
+        o.valid = dev_alloc(c, sizeof(uint64_t) * nw);
+        HIP_CHECK(launch_fill_words((uint64_t *)o.valid->p, 0, nwords(d.n), s));
+        // the folds of one GROUP BY all run over the same sorted key: the run heads of a stored key are computed once; those of a loaded
+        // column or a range are made on the spot
+        const void *kd = ctl.kind == DVec::DENSE && ctl.data ? ctl.data->p : nullptr;
+        DenseHeads made;
+        DenseHeads &dh = kd ? dense_heads[std::make_pair(kd, (const void *)(ctl.valid ? ctl.valid->p : nullptr))] : made;
+        if (!dh.heads) {
+            if (kd) { dh.ctl = ctl.data; dh.ctlv = ctl.valid; }     // keep the key's addresses from being reused
+            dh.heads = dev_alloc(c, sizeof(uint64_t) * nw);
+            dh.wordhd = dev_alloc(c, sizeof(int64_t) * (nw + (size_t)maxscan_blocks((int64_t)nw) + 1));
+            HIP_CHECK(launch_fold_heads(src_of(ctl), vp(ctl), d.n, (uint64_t *)dh.heads->p, (int64_t *)dh.wordhd->p, s));
+        }
+        const Folded f = fold_given_heads(n, src_of(d), vp(d), vp(ctl), dh.heads, dh.wordhd, d.n, o.valid);
+        o.data = f.data; o.hi = f.hi;
+        return o;
     }
 
     // a statement (and what it depends on) ahead of its turn: statements are pure, so order does not matter; the main loop skips it
@@ -1449,99 +1522,7 @@ struct GenExec {
             HIP_CHECK(launch_scatter(src_of(src), vp(src), src_of(pos), vp(pos), src.n, o.n, (int64_t *)o.data->p, (uint64_t *)o.valid->p, s));
             return o;
         }
-        case Op::FoldSum: case Op::FoldMin: case Op::FoldMax: case Op::FoldCount: case Op::FoldChoose: {
-            if (sparse_on && V(n.b).kind == DVec::SPARSE && V(n.a).kind == DVec::RANGE && V(n.a).step == 0 && V(n.a).n == V(n.b).n &&
-                V(n.b).sel->m > 0 && V(n.b).sel->idx && V(n.a).valid && V(n.a).valid == V(n.b).sel->bitmap) {
-                // one run over exactly the selected slots (the ungrouped aggregate of a filtered table, Vlite.hs:636-639):
-                // fold the entries; the result sits at the run's first slot = the selection's first slot
-                const DVec &sd = V(n.b);
-                const int kind = n.op == Op::FoldSum ? 0 : n.op == Op::FoldMin ? 1 : n.op == Op::FoldMax ? 2 : n.op == Op::FoldCount ? 3 : 4;
-                o.kind = DVec::ONEHOT; o.n = sd.n;
-                o.data = dev_alloc(c, 3 * sizeof(int64_t));
-                if (wide_on && kind == 0) { wide_fold_global(n, o, i64_src(sd.data), nullptr, nullptr, sd.sel->m); return o; }
-                BufP scratch = dev_alloc(c, sizeof(int64_t) * 3 * (size_t)fold_scratch_blocks());
-                // (the record's slot is 0: the run starts at slot 0 of the vector, not at the selection's first slot)
-                HIP_CHECK(launch_fold_global(kind, i64_src(sd.data), nullptr, nullptr, sd.sel->m, (int64_t *)scratch->p, (int64_t *)o.data->p, s));
-                return o;
-            }
-            const bool data_on_sel = V(n.a).kind == DVec::SPARSE &&
-                                     ((V(n.b).kind == DVec::SPARSE && V(n.a).sel == V(n.b).sel) ||
-                                      (V(n.b).kind == DVec::RANGE && V(n.b).step == 0 && V(n.b).n == V(n.a).n && subset(bitmap_of(V(n.a).sel), V(n.b).valid)));
-            // (the first run's result belongs in slot 0 of the vector: on the entries that is only the case when the selection
-            // starts at slot 0 -- always so for the prefix selections GROUP BY folds over; anything else takes the dense route)
-            if (sparse_on && data_on_sel && first_slot_of(V(n.a).sel) == 0) {
-                // runs skip EPS slots, so folding the m entries gives the same runs; results sit at run-first entries
-                const DVec &sc = V(n.a), &sd = V(n.b);
-                const SelP sel = sc.sel;
-                Src dsrc = sd.kind == DVec::SPARSE ? i64_src(sd.data) : src_of(sd);
-                return fold_entries(n, sel, i64_src(sc.data), sc.data->p, sc.data, dsrc, sel->m, sc.n);
-            }
-            // The same for a control vector that holds a value in EVERY slot (the key of a GROUP BY over an unfiltered table: Q18
-            // groups all lineitems by order): its n slots are the entries, the results live on the selection of the run heads.
-            // Only with the batch on and many short runs (fold_entries decides): a handful of long runs is what k_seg_fold is for.
-            if (sparse_on && group_batch_on && V(n.a).n > 0 && (V(n.a).kind == DVec::DENSE || V(n.a).kind == DVec::COLUMN) && !V(n.a).valid) {
-                const DVec &dc = V(n.a);
-                DVec dd = V(n.b);
-                if (dd.kind == DVec::EXPR && !dd.sel) dd = expr_force(dd);
-                const bool plain = (dd.kind == DVec::DENSE || dd.kind == DVec::COLUMN || dd.kind == DVec::RANGE) && !dd.valid && dd.n == dc.n;   // (all n slots are entries: a RANGE counts along them)
-                if (plain && sorted_heads.count(dc.kind == DVec::DENSE ? dc.data->p : dc.ptr)) {      // (the Partition saw it in order and counted its runs)
-                    const SortedHeads &sh = sorted_heads[dc.kind == DVec::DENSE ? dc.data->p : dc.ptr];
-                    if (sh.count * 64 >= dc.n)
-                        return fold_entries(n, prefix_selection(dc.n, dc.n), src_of(dc), dc.kind == DVec::DENSE ? dc.data->p : dc.ptr, dc.data, src_of(dd), dc.n, dc.n);
-                }
-            }
-            DVec ctl = densify(V(n.a)), d = densify(V(n.b));
-            if (ctl.n != d.n) throw Error(VDL_ERR_SHAPE, std::string(op_name(n.op, -1)) + " (Id " + std::to_string(n.id) + "): operand lengths differ");
-            const int kind = n.op == Op::FoldSum ? 0 : n.op == Op::FoldMin ? 1 : n.op == Op::FoldMax ? 2 : n.op == Op::FoldCount ? 3 : 4;
-            if (!(ctl.kind == DVec::RANGE && ctl.step == 0)) {
-                // general control vector (grouped aggregates fold data scattered into key order)
-                const size_t nw = (size_t)std::max<int64_t>(nwords(d.n), 1);
-                o.kind = DVec::DENSE; o.n = d.n;
-                o.data = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(d.n, 1));
-                o.valid = dev_alloc(c, sizeof(uint64_t) * nw);
-                HIP_CHECK(launch_fill_words((uint64_t *)o.valid->p, 0, nwords(d.n), s));
-                // the folds of one GROUP BY all run over the same sorted key: its run heads are computed once
-                const void *kd = ctl.kind == DVec::DENSE && ctl.data ? ctl.data->p : nullptr;
-                if (kd) {
-                    DenseHeads &dh = dense_heads[std::make_pair(kd, (const void *)(ctl.valid ? ctl.valid->p : nullptr))];
-                    if (!dh.heads) {
-                        dh.ctl = ctl.data; dh.ctlv = ctl.valid;                 // keep the key's addresses from being reused
-                        dh.heads = dev_alloc(c, sizeof(uint64_t) * nw);
-                        dh.wordhd = dev_alloc(c, sizeof(int64_t) * (nw + (size_t)maxscan_blocks((int64_t)nw) + 1));
-                        HIP_CHECK(launch_fold_heads(src_of(ctl), vp(ctl), d.n, (uint64_t *)dh.heads->p, (int64_t *)dh.wordhd->p, s));
-                    }
-                    if (wide_on && kind == 0) {                     // the wide form: both sums in one pass, joined at the heads
-                        wide_fold_begin(n, d.n, "k_seg_fold");
-                        o.hi = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(d.n, 1));
-                        HIP_CHECK(launch_wide_fold_runs(src_of(d), vp(d), vp(ctl), (const uint64_t *)dh.heads->p, (const int64_t *)dh.wordhd->p, d.n,
-                                                        (int64_t *)o.data->p, (int64_t *)o.hi->p, (uint64_t *)o.valid->p, s));
-                        return o;
-                    }
-                    HIP_CHECK(launch_fold_runs(kind, src_of(d), vp(d), vp(ctl), (const uint64_t *)dh.heads->p, (const int64_t *)dh.wordhd->p, d.n,
-                                               (int64_t *)o.data->p, (uint64_t *)o.valid->p, s));
-                    return o;
-                }
-                BufP heads = dev_alloc(c, sizeof(uint64_t) * nw);
-                BufP wordhd = dev_alloc(c, sizeof(int64_t) * (nw + (size_t)maxscan_blocks((int64_t)nw) + 1));
-                if (wide_on && kind == 0) {                         // the wide form over heads made here
-                    wide_fold_begin(n, d.n, "k_seg_fold");
-                    o.hi = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(d.n, 1));
-                    HIP_CHECK(launch_fold_heads(src_of(ctl), vp(ctl), d.n, (uint64_t *)heads->p, (int64_t *)wordhd->p, s));
-                    HIP_CHECK(launch_wide_fold_runs(src_of(d), vp(d), vp(ctl), (const uint64_t *)heads->p, (const int64_t *)wordhd->p, d.n,
-                                                    (int64_t *)o.data->p, (int64_t *)o.hi->p, (uint64_t *)o.valid->p, s));
-                    return o;
-                }
-                HIP_CHECK(launch_fold_segmented(kind, src_of(ctl), vp(ctl), src_of(d), vp(d), d.n, (uint64_t *)heads->p,
-                                                (int64_t *)wordhd->p, (int64_t *)o.data->p, (uint64_t *)o.valid->p, s));
-                return o;
-            }
-            o.kind = DVec::ONEHOT; o.n = d.n;
-            o.data = dev_alloc(c, 3 * sizeof(int64_t));
-            if (wide_on && kind == 0) { wide_fold_global(n, o, src_of(d), vp(d), vp(ctl), d.n); return o; }
-            BufP scratch = dev_alloc(c, sizeof(int64_t) * 3 * (size_t)fold_scratch_blocks());
-            HIP_CHECK(launch_fold_global(kind, src_of(d), vp(d), vp(ctl), d.n, (int64_t *)scratch->p, (int64_t *)o.data->p, s));
-            return o;
-        }
+        case Op::FoldSum: case Op::FoldMin: case Op::FoldMax: case Op::FoldCount: case Op::FoldChoose: return exec_fold(n);
         case Op::Partition: {
             if (sparse_on && V(n.a).kind == DVec::SPARSE) {
                 const DVec &sd = V(n.a);
@@ -1570,7 +1551,7 @@ struct GenExec {
             o.valid = dev_alloc(c, sizeof(uint64_t) * (size_t)std::max<int64_t>(nwords(d.n), 1));
             HIP_CHECK(launch_fill_words((uint64_t *)o.valid->p, 0, nwords(d.n), s));
             if (d.n == 0) return o;
-            BufP scratch = dev_alloc(c, sizeof(int64_t) * 3 * (size_t)fold_scratch_blocks());
+            BufP scratch = dev_alloc(c, sizeof(int64_t) * (size_t)fold_global_scratch_words(false));
             BufP mm = dev_alloc(c, 6 * sizeof(int64_t));
             HIP_CHECK(launch_fold_global(1, src_of(d), vp(d), nullptr, d.n, (int64_t *)scratch->p, (int64_t *)mm->p, s));
             HIP_CHECK(launch_fold_global(2, src_of(d), vp(d), nullptr, d.n, (int64_t *)scratch->p, (int64_t *)mm->p + 3, s));

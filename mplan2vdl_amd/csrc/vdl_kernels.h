@@ -200,22 +200,10 @@ VDL_HD inline void wide_join_low(int64_t wrapped, int64_t sh, int64_t *lo, int64
     wide_join_halves((int64_t)((uint64_t)wrapped - ((uint64_t)sh << 32)), sh, lo, hi);
 }
 constexpr int64_t kWideFoldMaxEntries = (int64_t)1 << 31;      // entries one wide fold takes: beyond it SH could wrap
-// vdl_fold_wide.hip: the wide forms of the FoldSum kernels -- one load per term, the wrapped sum and the sum of the high halves side by
-// side -- and what goes with them.
-//   fold_global: launch_fold_global for FoldSum; scratch 4 * wide_fold_scratch_blocks() int64; result = FOUR words, the record
-//       {value, slot, count} as ever and the value's high word behind it (0 when nothing was folded); result_hi[0] = that word again,
-//       for the readers that take a vector's high words as a buffer of their own.
-//   fold_runs: launch_fold_runs for FoldSum over the same heads / wordhd; out_hi[head] = the high word of out[head] (joined at the heads).
-//   group_fold: launch_group_fold; a FoldSum member with out_hi set (pre-filled with zeros like out) leaves the sum of its high halves
-//       there: launch_wide_join over the packed results afterwards.
-//   join: hi[i] (in: the SUM of the high halves of result i) becomes bits 64..127 of the exact sum whose low word is lo[i].
-//   sign: hi[i] = lo[i] >> 63.  fits: flag[0] (INT64_MAX before) = the first i < n holding a value (valid null = all do) with
-//   hi[i] != lo[i] >> 63; fits_record: flag[0] = 0 when the record's value does not fit.
-int wide_fold_scratch_blocks();
-hipError_t launch_wide_fold_global(Src d, const uint64_t *vd, const uint64_t *vc, int64_t n, int64_t *scratch, int64_t *result, int64_t *result_hi, hipStream_t s);
-hipError_t launch_wide_fold_runs(Src d, const uint64_t *vd, const uint64_t *vc, const uint64_t *heads, const int64_t *wordhd, int64_t n, int64_t *out, int64_t *out_hi,
-                                 uint64_t *vout /* pre-zeroed */, hipStream_t s);
-hipError_t launch_wide_join(const int64_t *lo, int64_t *hi, int64_t n, hipStream_t s);
+// The folds that take a high output (launch_fold_global, launch_fold_runs, launch_group_fold below) run the wide forms of their kernels
+// for it (vdl_fold_wide.hip): one load per term, the wrapped sum and the sum of the high halves side by side, joined per result.
+// What goes with them: sign: hi[i] = lo[i] >> 63.  fits: flag[0] (INT64_MAX before) = the first i < n holding a value (valid null = all
+// do) with hi[i] != lo[i] >> 63; fits_record: flag[0] = 0 when the record's value does not fit.
 hipError_t launch_wide_sign(const int64_t *lo, int64_t *hi, int64_t n, hipStream_t s);
 hipError_t launch_wide_fits(const int64_t *lo, const int64_t *hi, const uint64_t *valid, int64_t n, int64_t *flag, hipStream_t s);
 hipError_t launch_wide_fits_record(const int64_t *rec, const int64_t *hi, int64_t *flag, hipStream_t s);
@@ -248,12 +236,18 @@ struct FilterArgs {
 hipError_t launch_filter_columns(const FilterArgs &a, uint64_t *out, int64_t n, hipStream_t s);
 // FoldSelect with unit-length runs: out bitmap = (d != 0) & vd & vc
 hipError_t launch_select_bitmap(Src d, const uint64_t *vd, const uint64_t *vc, uint64_t *out, int64_t n, hipStream_t s);
-// Global (single-run) fold of `d` over slots valid in both bitmaps.
-// result[0] = value, result[1] = first slot whose control is valid (or -1), result[2] = number of data folded.
-// scratch: at least 3 * fold_scratch_blocks() int64.
-int fold_scratch_blocks();
-hipError_t launch_fold_global(int kind /*0 sum,1 min,2 max,3 count,4 choose*/, Src d, const uint64_t *vd, const uint64_t *vc,
-                              int64_t n, int64_t *scratch, int64_t *result, hipStream_t s);
+// The three fold routes.  kind: 0 sum, 1 min, 2 max, 3 count, 4 choose (first value).  Each has ONE launcher for its plain and its wide
+// form: a high output that is not null asks for kind 0 only, selects the wide kernels (at most kWideFoldMaxEntries entries) and holds, on
+// return, bits 64..127 of every exact sum whose bits 0..63 -- the same words as the plain form's -- are in the low output.
+//
+// Global (single-run) fold of `d` over slots valid in both bitmaps: result = fold_record_words(wide) words,
+// result[0] = value, result[1] = first slot whose control is valid (or -1), result[2] = number of data folded, and with result_hi
+// result[3] = the value's high word (0 when nothing was folded), which is in result_hi[0] as well, for the readers that take a vector's
+// high words as a buffer of their own.  scratch: fold_global_scratch_words(wide) int64.
+int64_t fold_record_words(bool wide);
+int64_t fold_global_scratch_words(bool wide);
+hipError_t launch_fold_global(int kind, Src d, const uint64_t *vd, const uint64_t *vc, int64_t n, int64_t *scratch, int64_t *result, hipStream_t s,
+                              int64_t *result_hi = nullptr);
 // element-wise op on two one-hot (fold result) vectors: valid iff both valid and same slot
 hipError_t launch_onehot_binary(int op, const int64_t *a, const int64_t *b, int64_t *out, hipStream_t s);
 // broadcast-constant operand: b_is_const selects (a op k) / (k op a)
@@ -315,6 +309,8 @@ hipError_t launch_sorted_heads_counted(const int64_t *d, int64_t n, uint64_t *he
 // heads are given (m entries, all holding a value; entry 0 is a head) and writes out[j][g] for the g-th run.  offsets = exclusive
 // prefix of the head counts per compaction tile (launch_compact_count + launch_compact_scan over `heads`).  kind: 0 sum, 1 min,
 // 2 max, 3 count, 4 choose (first value).  out[j] of kinds 0-3 must hold the reduction's identity (0 / INT64_MAX / INT64_MIN / 0).
+// out_hi (null: the plain kernel): a.nfold pointers, out_hi[j] = where the high words of FoldSum member j go (pre-filled with zeros like
+// out[j]; null for the members that are no wide sum), `groups` = the number of runs, i.e. of words behind each.
 constexpr int kMaxGroupFolds = 16;
 struct GroupFoldArgs {
     int nfold = 0;
@@ -322,13 +318,8 @@ struct GroupFoldArgs {
     Src data[kMaxGroupFolds];
     int64_t *out[kMaxGroupFolds] = {};
 };
-hipError_t launch_group_fold(const GroupFoldArgs &a, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s);
-// the wide form (vdl_fold_wide.hip, described with the other wide folds above)
-struct WideGroupFoldArgs {
-    GroupFoldArgs g;
-    int64_t *out_hi[kMaxGroupFolds] = {};
-};
-hipError_t launch_wide_group_fold(const WideGroupFoldArgs &a, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s);
+hipError_t launch_group_fold(const GroupFoldArgs &a, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s, int64_t *const *out_hi = nullptr,
+                             int64_t groups = 0);
 size_t partition_scratch_bytes(int64_t n, int64_t pcount);
 hipError_t launch_partition(Src data, const uint64_t *valid, int64_t n, int64_t pmin, int64_t pcount, void *scratch /* partition_scratch_bytes(n, pcount) */,
                             uint64_t *keys_a, int64_t *slots_a, uint64_t *keys_b, int64_t *slots_b,
@@ -336,14 +327,14 @@ hipError_t launch_partition(Src data, const uint64_t *valid, int64_t n, int64_t 
                             int64_t *order_out = nullptr /* instead of pos_out: the slots in rank order (order[pos[slot]] = slot), stored sequentially */,
                             int64_t *sorted_keys_out = nullptr /* with order_out: bucket + pmin in rank order (= the keys, when all lie inside the pivots) */);
 
-// Fold over a general control vector; kind 0 sum, 1 min, 2 max, 3 count, 4 choose
+// Fold over a general control vector: launch_fold_heads leaves the run heads (first slot of every run, EPS control slots skipped) and
+// the per-word lookup, launch_fold_runs folds `d` over them -- several folds share one control vector's heads.  out[head] = the run's
+// result, vout (pre-zeroed) = the heads of runs that folded something, out_hi[head] = the high word of out[head].
 // heads: nwords uint64; wordhd: nwords + maxscan_blocks(nwords) int64
 int64_t maxscan_blocks(int64_t n);
 hipError_t launch_fold_heads(Src ctl, const uint64_t *vc, int64_t n, uint64_t *heads, int64_t *wordhd, hipStream_t s);
 hipError_t launch_fold_runs(int kind, Src d, const uint64_t *vd, const uint64_t *vc, const uint64_t *heads, const int64_t *wordhd, int64_t n,
-                            int64_t *out, uint64_t *vout, hipStream_t s);
-hipError_t launch_fold_segmented(int kind, Src ctl, const uint64_t *vc, Src d, const uint64_t *vd, int64_t n, uint64_t *heads,
-                                 int64_t *wordhd, int64_t *out, uint64_t *vout, hipStream_t s);
+                            int64_t *out, uint64_t *vout, hipStream_t s, int64_t *out_hi = nullptr);
 
 // ---- row exchange for sharded Partition (see vdl_partition.hip) ------------------------------------
 constexpr int kMaxExSources = 62;
@@ -465,5 +456,13 @@ hipError_t launch_collate_table(const int8_t *heap, int64_t n, int gshift, const
 // the order step's text key: ranks[i] of the string code[i] names, -1 for a code that names none; state (two words, zero before): [0] = such rows, [1] = ~(the first of them)
 hipError_t launch_order_textkey(const int64_t *code, int64_t m, const int8_t *heap, int64_t n, const int32_t *table, int gshift, int64_t *ranks, uint64_t *state,
                                 hipStream_t s);
+
+
+// ---- internal: what launch_fold_global / launch_fold_runs / launch_group_fold (vdl_ops.hip) call for a high output (vdl_fold_wide.hip,
+// a translation unit of its own: vdl_ops.o holds no wide instantiation).  Nobody else calls these. ----
+hipError_t launch_wide_fold_global(Src d, const uint64_t *vd, const uint64_t *vc, int64_t n, int64_t *scratch, int64_t *result, int64_t *result_hi, hipStream_t s);
+hipError_t launch_wide_fold_runs(Src d, const uint64_t *vd, const uint64_t *vc, const uint64_t *heads, const int64_t *wordhd, int64_t n, int64_t *out, int64_t *out_hi,
+                                 uint64_t *vout, hipStream_t s);
+hipError_t launch_wide_group_fold(const GroupFoldArgs &a, int64_t *const *out_hi, int64_t groups, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s);
 
 }  // namespace vdl

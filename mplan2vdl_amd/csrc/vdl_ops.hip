@@ -368,7 +368,8 @@ hipError_t launch_select_bitmap(Src d, const uint64_t *vd, const uint64_t *vc, u
 
 // Global (single-run) fold (/root/reference/src/Vlite.hs:337-356 with an all-equal control
 // vector, Vlite.hs:636-639): two launches, per-block partials (vdl_fold_global.inc) then one block (vdl_fold_body.h).
-int fold_scratch_blocks() { return kFoldBlocks; }
+int64_t fold_record_words(bool wide) { return wide ? 4 : 3; }
+int64_t fold_global_scratch_words(bool wide) { return fold_record_words(wide) * kFoldBlocks; }      // a block's partial is a record
 
 __global__ __launch_bounds__(256) void k_fold_global(int kind, Src d, const uint64_t *vd, const uint64_t *vc, int64_t n,
                                                      int64_t *scratch) {
@@ -379,8 +380,9 @@ __global__ __launch_bounds__(256) void k_fold_global_finish(int kind, Src d, con
     fold_global_finish_body<false>(kind, d, scratch, nblocks, result, nullptr);
 }
 
-hipError_t launch_fold_global(int kind, Src d, const uint64_t *vd, const uint64_t *vc, int64_t n, int64_t *scratch,
-                              int64_t *result, hipStream_t s) {
+hipError_t launch_fold_global(int kind, Src d, const uint64_t *vd, const uint64_t *vc, int64_t n, int64_t *scratch, int64_t *result, hipStream_t s,
+                              int64_t *result_hi) {
+    if (result_hi) return kind == 0 ? launch_wide_fold_global(d, vd, vc, n, scratch, result, result_hi, s) : hipErrorInvalidValue;
     (void)hipGetLastError();   // see launch_status()
     const int grid = fold_global_grid(n);
     k_fold_global<<<grid, 256, 0, s>>>(kind, d, vd, vc, n, scratch);
@@ -676,7 +678,8 @@ __global__ __launch_bounds__(256) void k_group_fold(GroupFoldArgs a, unsigned ve
     int64_t *const *const out_hi = nullptr;
 #include "vdl_group_fold.inc"
 }
-hipError_t launch_group_fold(const GroupFoldArgs &a, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s) {
+hipError_t launch_group_fold(const GroupFoldArgs &a, const uint64_t *heads, int64_t m, const int64_t *offsets, hipStream_t s, int64_t *const *out_hi, int64_t groups) {
+    if (out_hi) return launch_wide_group_fold(a, out_hi, groups, heads, m, offsets, s);
     (void)hipGetLastError();
     const int64_t nb = (m + compact_tile() - 1) / compact_tile();
     if (nb <= 0 || a.nfold <= 0) return hipSuccess;
@@ -1215,7 +1218,8 @@ hipError_t launch_fold_heads(Src ctl, const uint64_t *vc, int64_t n, uint64_t *h
 }
 // the fold itself, over heads computed by launch_fold_heads for the same control vector (several folds share them)
 hipError_t launch_fold_runs(int kind, Src d, const uint64_t *vd, const uint64_t *vc, const uint64_t *heads, const int64_t *wordhd, int64_t n,
-                            int64_t *out, uint64_t *vout /* pre-zeroed */, hipStream_t s) {
+                            int64_t *out, uint64_t *vout /* pre-zeroed */, hipStream_t s, int64_t *out_hi) {
+    if (out_hi) return kind == 0 ? launch_wide_fold_runs(d, vd, vc, heads, wordhd, n, out, out_hi, vout, s) : hipErrorInvalidValue;
     (void)hipGetLastError();
     if (n <= 0) return hipSuccess;
     const int rk = (kind == 1 || kind == 4) ? R_MIN : kind == 2 ? R_MAX : R_SUM;
@@ -1223,12 +1227,6 @@ hipError_t launch_fold_runs(int kind, Src d, const uint64_t *vd, const uint64_t 
     k_seg_fold<<<seg_fold_grid(n), 256, 0, s>>>(kind, d, vd, vc, heads, wordhd, n, out, vout);
     if (kind == 4) k_seg_choose_fix<<<grid_for(n, 256, 4), 256, 0, s>>>(d, vout, n, out);
     return launch_status();
-}
-hipError_t launch_fold_segmented(int kind, Src ctl, const uint64_t *vc, Src d, const uint64_t *vd, int64_t n,
-                                 uint64_t *heads, int64_t *wordhd, int64_t *out, uint64_t *vout /* pre-zeroed */, hipStream_t s) {
-    hipError_t e = launch_fold_heads(ctl, vc, n, heads, wordhd, s);
-    if (e != hipSuccess) return e;
-    return launch_fold_runs(kind, d, vd, vc, heads, wordhd, n, out, vout, s);
 }
 
 

@@ -174,6 +174,40 @@ def test_a_long_run_crosses_the_fast_path_of_k_seg_fold(monkeypatch):
         e.close()
 
 
+RUNS_OF_A_COLUMN = wt.prog("1,Load,t.k", "2,Project,val,Id 1,k", "3,Load,t.v", "4,Project,val,Id 3,v",
+                           *["%d,%s" % (5 + 2 * i + j, body) for i, f in enumerate(wt.FOLDS)
+                             for j, body in enumerate(("%s,val,Id 2,val,Id 4,val" % f, "MaterializeCompact,Id %d" % (5 + 2 * i)))])
+
+
+@pytest.mark.parametrize("lens", [(3, 64, 61, 130), (1,), (65,), (2, 2, 1)], ids=["258", "1", "65", "value_returns"])
+def test_runs_of_a_loaded_control_column(lens):
+    """The control vector is a loaded column, the data another: no stored key whose heads could be cached, so the fold makes its heads
+    on the spot and runs k_seg_fold over them, every slot an entry.  Runs of 3, 64, 61 and 130: one ends where a bitmap word ends, one
+    spans three words.  In (2, 2, 1) the first control value returns: runs are not groups."""
+    n = sum(lens)
+    k = np.repeat(np.arange(len(lens)) + 1, lens).astype(np.int64)
+    if lens == (2, 2, 1):
+        k[-1] = 1
+    v = np.array(wt.EDGE_VALUES, np.int64)[np.random.default_rng(n).integers(0, len(wt.EDGE_VALUES), n)]
+    cols = {"t.k": k, "t.v": v}
+    heads = np.r_[0, np.cumsum(lens)[:-1]]
+    sums = {"tmp6": [int(x) for x in np.add.reduceat(v.astype(object), heads)]}      # (tmp6 = the MaterializeCompact of the FoldSum)
+    want = values(oracle_run(RUNS_OF_A_COLUMN, cols))
+    assert [wt.low(x) for x in sums["tmp6"]] == want["tmp6"] and len(want) == len(wt.FOLDS)
+    e = engine_with(cols)
+    try:
+        p = e.parse(RUNS_OF_A_COLUMN)
+        p.set_fusion(False)
+        plain = values(p.run()["results"])
+        assert plain == want, (lens, "switch off differs from the oracle")
+        res, words = wide_run(p, 1)
+        check_words(("column_runs", lens), plain, res, words, sums)
+        assert "k_seg_fold" in p.wide_note(), p.wide_note()
+        p.close()
+    finally:
+        e.close()
+
+
 # ---- 3. mode 2 -------------------------------------------------------------------------------------------------------------------------------
 def test_checked_mode_names_field_group_and_value():
     text, meta = wt.group_program(False, folds=["FoldSum", "FoldChoose"])
