@@ -644,6 +644,39 @@ int  vdl_plan_set_wide_sums_sharded(vdl_plan *plan, int on);
 int  vdl_plan_wide_sums_sharded(const vdl_plan *plan);
 int  vdl_comm_merge_host_wide(int world, int64_t n_words, const int32_t *ops, const int64_t *gathered, int64_t stride_words, int64_t *out_lo,
                               int64_t *out_hi, int64_t *status_out);
+/* ---- batched runs, sharded (DESIGN.md section 7 "Batches") ----
+ * vdl_run_batch_sharded: n plans in ONE sharded call.  After VDL_OK every plan holds, on every rank, what vdl_run_sharded of that plan
+ * alone would have left, bit for bit; no other entry point changes.  Every plan is classified from the plan alone, so every rank
+ * decides the same, before a kernel or a collective runs:
+ *   shared : the plan fuses as a whole, builds no semi-join set, takes the fold route and has wide sums off.  The shared plans' partial
+ *            words travel in ONE all-gather and are merged by ONE launch (k_merge_words_batch), whatever their number.  A rank's
+ *            block is the concatenation, in call order, of one segment per shared plan: [raw n_words][the words again with FoldChoose
+ *            entries resolved -- only if the plan has a VDL_REDUCE_FIRST word][status]; h = (first ? 2 : 1) * n_words + 1 words.
+ *            The local phase is per rank and free in its grouping: shared plans whose one scan is a global aggregate scan go
+ *            through vdl_run_batch's grouping and batch kernels, their slots' words written straight into the send block; every
+ *            other shared plan (a grouped scan -- also under vdl_set_batch_grouped --, lookup tables, no partner on this rank) runs its
+ *            own scans into its segment.  Ranks may group differently; the collective does not depend on it.
+ *   own    : everything else -- the set, exchange, front, chain and replicate routes, unfused fold plans, wide plans that
+ *            vdl_run_sharded accepts -- runs through vdl_run_sharded after the shared part, one at a time, in call order.
+ * An order is allowed only with vdl_plan_set_order_sharded (a shared plan's is applied on the host after the merge); an order without
+ * it, and a wide plan vdl_run_sharded would refuse, fail the whole call up front, the message naming the plan's index.  Argument
+ * errors as vdl_run_batch's; no communicator: VDL_ERR_ARG.
+ * Failures: a plan whose local phase fails on a rank -- a batch scan that throws fails its batch's plans there -- still takes part in
+ * the collective (its segment zeroed, its status set).  Every rank reads the same merged status words and the call fails with the
+ * LOWEST failing plan index: on the failing rank with its own code and message, elsewhere with VDL_ERR_UNSUPPORTED ("sharded run: the
+ * local phase failed on rank r ..."), both prefixed "plan i: ".  The other shared plans keep their answers; no own plan is started.
+ * Out of scope: a pipelined begin / end pair, wide sums in a batch, one pass shared between grouped plans.
+ * vdl_batch_sharded_layout (no device, no communicator needed): per plan its segment's offset (-1: an own plan) and height (0), and
+ * the block's words.  vdl_plan_batch_sharded_note: "collective 0: words [<off>,<off+h>) of <B>" or "own: <route> route", of the last
+ * of the two calls; vdl_plan_batch_note says, in vdl_run_batch's words, how this rank's local phase grouped a shared plan.
+ * vdl_comm_merge_host_batch: the merge rule of such blocks on the host (what k_merge_words_batch computes): plan q's segment at
+ * offsets[q] of every rank's block_words words, ops_concat / out_concat the plans' operators / merged words one after the other,
+ * status_out (may be null) {first non-zero status, its rank or -1} per plan. */
+int  vdl_run_batch_sharded(vdl_ctx *ctx, vdl_plan *const *plans, int n);
+int  vdl_batch_sharded_layout(vdl_ctx *ctx, vdl_plan *const *plans, int n, int64_t *offsets, int64_t *heights, int64_t *block_words);
+const char *vdl_plan_batch_sharded_note(const vdl_plan *plan);
+int  vdl_comm_merge_host_batch(int world, int n, const int64_t *n_words, const int64_t *offsets, const int32_t *ops_concat, const int64_t *gathered,
+                               int64_t block_words, int64_t *out_concat, int64_t *status_out);
 
 #ifdef __cplusplus
 }

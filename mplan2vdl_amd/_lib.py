@@ -140,6 +140,10 @@ def load():
         "vdl_run_sharded_end": (i32, [vp, vp, i32]),
         "vdl_comm_merge_host": (i32, [i32, i64, P(ctypes.c_int32), P(i64), i64, P(i64), P(i64)]),
         "vdl_comm_merge_host_wide": (i32, [i32, i64, P(ctypes.c_int32), P(i64), i64, P(i64), P(i64), P(i64)]),
+        "vdl_run_batch_sharded": (i32, [vp, P(vp), i32]),
+        "vdl_batch_sharded_layout": (i32, [vp, P(vp), i32, P(i64), P(i64), P(i64)]),
+        "vdl_plan_batch_sharded_note": (cp, [vp]),
+        "vdl_comm_merge_host_batch": (i32, [i32, i32, P(i64), P(i64), P(ctypes.c_int32), P(i64), i64, P(i64), P(i64)]),
     })
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here = the library does not export the ABI
@@ -165,6 +169,7 @@ ABI_SYMBOLS = [
     "vdl_plan_set_wide_sums", "vdl_plan_wide_sums", "vdl_output_high", "vdl_plan_wide_note", "vdl_wide_eval_bin",
     "vdl_plan_set_wide_sums_sharded", "vdl_plan_wide_sums_sharded", "vdl_comm_merge_host_wide",
     "vdl_plan_set_wide_sums_tail", "vdl_plan_wide_sums_tail", "vdl_output_high_device", "vdl_wide_join_halves",
+    "vdl_run_batch_sharded", "vdl_batch_sharded_layout", "vdl_plan_batch_sharded_note", "vdl_comm_merge_host_batch",
 ]
 
 

@@ -12,6 +12,8 @@
 //       ONE all-gather of the partial words (Q6: 2 words, Q1: 289) + a local merge kernel that applies each word's
 //       VDL_REDUCE_* operator over the ranks.  FoldChoose words travel as (global row id, value) pairs, so the
 //       MIN -> resolve -> SUM double round of the all-reduce formulation is gone.
+//   K such plans in one call (vdl_run_batch_sharded): still ONE all-gather -- a rank's block is one segment per plan -- and one
+//       launch of k_merge_words_batch; plans of other routes run through vdl_run_sharded inside the call.
 //   plans with a Partition (Q3, Q5, Q9, Q10, Q12, Q20):
 //       ONE all-gather of {status, rows per destination} (the only host synchronisation: receive sizes depend on it), then
 //       ONE grouped send/receive (ncclGroupStart .. ncclGroupEnd) that moves every column's piece for every peer.
@@ -76,7 +78,29 @@ static Rccl &rccl() {
         if (e_ != kNcclSuccess) throw Error(VDL_ERR_DEVICE, std::string(#expr) + " failed: " + rccl().GetErrorString(e_)); \
     } while (0)
 
+// The buffers of a sharded batch (vdl_run_batch_sharded), kept with the communicator by the LAYOUT of the call -- per shared plan its
+// word count and operators, and the world -- and reused by every call with that layout.  A rank's block is the concatenation, in call
+// order, of one segment per shared plan: [raw n_words][the words again with FoldChoose entries resolved, only where the plan has a
+// VDL_REDUCE_FIRST word][status]; ONE all-gather moves it, one launch (k_merge_words_batch) merges every plan's words.
+struct BatchShardState {
+    int n = 0;                              // shared plans
+    int64_t block = 0, words = 0;           // B = the sum of the heights, W = the sum of the word counts
+    std::vector<int64_t> off, nw, first;    // per shared plan: its segment's offset in the block, its words, the index of its first merged word
+    std::vector<char> any_first;
+    BufP ops, seg, send, recv, merged, status;
+    std::vector<int64_t> status_sent;       // what the status words of `send` hold (they are rewritten only when a plan's outcome differs)
+    int64_t *host = nullptr;                // pinned: n words of local statuses, then 2 n merged {status, rank}
+    hipEvent_t ev_local = nullptr, ev_merged = nullptr;     // engine stream -> communication stream; the communication stream has left the send block
+    int64_t height(int q) const { return (any_first[(size_t)q] ? 2 : 1) * nw[(size_t)q] + 1; }
+    ~BatchShardState() {
+        if (host) (void)hipHostFree(host);
+        if (ev_local) (void)hipEventDestroy(ev_local);
+        if (ev_merged) (void)hipEventDestroy(ev_merged);
+    }
+};
+
 struct CommState {
+    std::map<std::string, std::shared_ptr<BatchShardState>> batch_states;      // (first: destroyed last, after the stream its events were recorded on)
     enum Kind { RCCL, HOST } kind = HOST;
     int rank = 0, world = 1;
     ncclComm_t comm = nullptr;
@@ -916,6 +940,220 @@ static void wide_sharded_gate(vdl_ctx *c, vdl_plan *p, const char *entry) {
     throw Error(VDL_ERR_UNSUPPORTED, why);
 }
 
+// ---- sharded batches (vdl_run_batch_sharded; DESIGN.md section 7 "Batches") ------------------------------------------------------
+// Which plans of the call share its ONE collective, from the plans alone -- every rank decides the same, before a kernel or a
+// collective runs.  SHARED: the plan fuses as a whole, builds no semi-join set, takes the fold route and has wide sums off; its
+// partial words are a segment of the rank block.  OWN: everything else, run through vdl_run_sharded after the shared part, in call
+// order.  An order without vdl_plan_set_order_sharded and a wide plan the gate refuses fail the call here, with the plan's index.
+struct BatchLayout {
+    std::vector<int> shared;                // indices of the shared plans, in call order
+    std::vector<int64_t> off, height;       // per plan of the call: its segment (-1 / 0: an own plan)
+    std::vector<int64_t> nw;                // per shared plan
+    std::vector<std::vector<int32_t>> ops;
+    int64_t block = 0, words = 0;
+    std::string key;
+};
+static void batch_sharded_classify(vdl_ctx *c, vdl_plan *const *plans, int n, const char *entry, BatchLayout &L) {
+    L.off.assign((size_t)n, -1);
+    L.height.assign((size_t)n, 0);
+    std::ostringstream key;
+    for (int i = 0; i < n; i++) {
+        vdl_plan *p = plans[i];
+        try {
+            refuse_order_sharded(p, true);
+            wide_sharded_gate(c, p, entry);
+        } catch (const Error &e) {
+            throw Error(e.code, "plan " + std::to_string(i) + ": " + e.what());
+        }
+        bool semi = false;
+        if (p->use_fusion && p->fused.ok) for (const PreludeItem &it : p->fused.prelude) semi |= it.kind == PreludeItem::SEMI_BITMAP;
+        const bool shared = p->use_fusion && p->fused.ok && !semi && !p->wide && fold_route(c, p);
+        if (!shared) {
+            const std::string keep = c->err;
+            const char *route = nullptr;
+            const bool known = vdl_plan_sharded_route(c, p, &route, nullptr) == VDL_OK && route;
+            c->err = keep;
+            p->batch_sharded_note = std::string("own: ") + (known ? route : "no") + " route";
+            continue;
+        }
+        int64_t nw = 0;
+        const int32_t *ops = nullptr;
+        if (vdl_plan_partial_spec(p, &nw, &ops) != VDL_OK) throw Error(VDL_ERR_UNSUPPORTED, "plan " + std::to_string(i) + ": " + c->err);
+        bool any_first = false;
+        for (int64_t k = 0; k < nw; k++) any_first |= ops[k] == VDL_REDUCE_FIRST;
+        const int64_t h = (any_first ? 2 : 1) * nw + 1;
+        L.shared.push_back(i);
+        L.off[(size_t)i] = L.block;
+        L.height[(size_t)i] = h;
+        L.nw.push_back(nw);
+        L.ops.emplace_back(ops, ops + nw);
+        key << nw << ":";
+        for (int64_t k = 0; k < nw; k++) key << ops[k];
+        key << ";";
+        L.block += h;
+        L.words += nw;
+    }
+    for (int i : L.shared)
+        plans[i]->batch_sharded_note = "collective 0: words [" + std::to_string(L.off[(size_t)i]) + "," + std::to_string(L.off[(size_t)i] + L.height[(size_t)i]) + ") of " + std::to_string(L.block);
+    L.key = key.str();
+}
+
+static BatchShardState &batch_shard_state(vdl_ctx *c, CommState &m, const BatchLayout &L) {
+    const std::string key = std::to_string(m.world) + "|" + L.key;
+    auto hit = m.batch_states.find(key);
+    if (hit != m.batch_states.end()) return *hit->second;
+    if (m.batch_states.size() >= 64) {
+        // (buffers in flight belong to finished calls: every call ends with its finalisations waited for, or with its stream drained)
+        m.batch_states.clear();
+    }
+    auto st = std::make_shared<BatchShardState>();
+    const int n = (int)L.shared.size();
+    st->n = n; st->block = L.block; st->words = L.words;
+    std::vector<int64_t> seg;
+    std::vector<int32_t> ops;
+    int64_t first = 0;
+    for (int q = 0; q < n; q++) {
+        const int i = L.shared[(size_t)q];
+        st->off.push_back(L.off[(size_t)i]);
+        st->nw.push_back(L.nw[(size_t)q]);
+        st->first.push_back(first);
+        st->any_first.push_back(L.height[(size_t)i] > L.nw[(size_t)q] + 1);
+        seg.push_back(L.off[(size_t)i]); seg.push_back(L.nw[(size_t)q]); seg.push_back(first);
+        ops.insert(ops.end(), L.ops[(size_t)q].begin(), L.ops[(size_t)q].end());
+        first += L.nw[(size_t)q];
+    }
+    const size_t W1 = (size_t)std::max<int64_t>(L.words, 1);
+    st->ops = dev_alloc(c, sizeof(int32_t) * W1);
+    st->seg = dev_alloc(c, sizeof(int64_t) * seg.size());
+    st->send = dev_alloc(c, sizeof(int64_t) * (size_t)L.block);
+    st->recv = dev_alloc(c, sizeof(int64_t) * (size_t)L.block * (size_t)m.world);
+    st->merged = dev_alloc(c, sizeof(int64_t) * W1);
+    st->status = dev_alloc(c, sizeof(int64_t) * 2 * (size_t)n);
+    HIP_CHECK(hipHostMalloc((void **)&st->host, sizeof(int64_t) * 3 * (size_t)n, hipHostMallocDefault));
+    for (int k = 0; k < 3 * n; k++) st->host[k] = 0;
+    if (!ops.empty()) HIP_CHECK(hipMemcpyAsync(st->ops->p, ops.data(), sizeof(int32_t) * ops.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(st->seg->p, seg.data(), sizeof(int64_t) * seg.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemsetAsync(st->send->p, 0, sizeof(int64_t) * (size_t)L.block, c->stream));       // (the status words: VDL_OK until a plan fails)
+    HIP_CHECK(hipStreamSynchronize(c->stream));                        // (`seg` and `ops` are this function's)
+    st->status_sent.assign((size_t)n, 0);
+    HIP_CHECK(hipEventCreateWithFlags(&st->ev_local, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&st->ev_merged, hipEventDisableTiming));
+    m.batch_states[key] = st;
+    return *st;
+}
+
+static void run_batch_sharded(vdl_ctx *c, vdl_plan *const *plans, int n) {
+    CommState &m = comm_of(c);
+    BatchLayout L;
+    batch_sharded_classify(c, plans, n, "vdl_run_batch_sharded", L);
+    need_device(c);
+    for (int i = 0; i < n; i++) { plans[i]->order_note.clear(); plans[i]->batch_note.clear(); plans[i]->batch_code_bytes = 0; }
+    const int ns = (int)L.shared.size();
+    if (ns > 0) {
+        BatchShardState &st = batch_shard_state(c, m, L);
+        int64_t *send = (int64_t *)st.send->p;
+        const bool overlap = m.kind == CommState::RCCL;
+        hipStream_t cs = overlap ? m.stream : c->stream;
+        std::vector<vdl_plan *> sp((size_t)ns);
+        std::vector<int64_t *> outs((size_t)ns);
+        for (int q = 0; q < ns; q++) { sp[(size_t)q] = plans[L.shared[(size_t)q]]; outs[(size_t)q] = send + st.off[(size_t)q]; }
+        // ---- the local phase: per rank, free in its grouping; every outcome travels in the plan's status word ----
+        std::vector<int64_t> rc((size_t)ns, VDL_OK);
+        std::vector<std::string> why((size_t)ns);
+        std::vector<BatchLocal> local;
+        try {
+            batch_local_scans(c, sp.data(), ns, outs.data(), local);
+        } catch (const std::exception &) {
+            // (the grouping itself: no plan was scanned -- each runs alone below and reports for itself)
+            local.assign((size_t)ns, BatchLocal{});
+        }
+        for (int q = 0; q < ns; q++) {
+            vdl_plan *p = sp[(size_t)q];
+            if (local[(size_t)q].batched) { rc[(size_t)q] = local[(size_t)q].rc; why[(size_t)q] = local[(size_t)q].err; continue; }
+            // alone on this rank: a grouped scan, a plan with lookup tables, a plan without a partner here -- as vdl_run_sharded's local phase
+            p->order_inside = true;
+            int r = vdl_run_local(c, p, outs[(size_t)q]);
+            p->order_inside = false;
+            if (r == VDL_OK && st.any_first[(size_t)q]) {
+                const int64_t nw = st.nw[(size_t)q];
+                try { HIP_CHECK(hipMemcpyAsync(outs[(size_t)q] + nw, outs[(size_t)q], sizeof(int64_t) * (size_t)nw, hipMemcpyDeviceToDevice, c->stream)); }
+                catch (const Error &e) { r = e.code; c->err = e.what(); }
+                if (r == VDL_OK) r = vdl_resolve_first(c, p, outs[(size_t)q] + nw);
+            }
+            if (r != VDL_OK) { rc[(size_t)q] = r; why[(size_t)q] = c->err; }
+        }
+        // a failed plan: its segment zeroed, its status set; the status words of the others stay (or go back to) VDL_OK
+        for (int q = 0; q < ns; q++) {
+            const int64_t h = st.height(q);
+            if (rc[(size_t)q] != VDL_OK) HIP_CHECK(hipMemsetAsync(outs[(size_t)q], 0, sizeof(int64_t) * (size_t)(h - 1), c->stream));
+            if (rc[(size_t)q] != st.status_sent[(size_t)q]) {
+                st.host[q] = rc[(size_t)q];                    // (pinned; the last call that wrote it has ended)
+                HIP_CHECK(hipMemcpyAsync(outs[(size_t)q] + h - 1, st.host + q, sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+                st.status_sent[(size_t)q] = rc[(size_t)q];
+            }
+        }
+        // ---- the collective: one gather, one merge, on the communication stream behind the batch's own event ----
+        if (overlap) {
+            HIP_CHECK(hipEventRecord(st.ev_local, c->stream));
+            HIP_CHECK(hipStreamWaitEvent(cs, st.ev_local, 0));
+        }
+        int64_t *merged = (int64_t *)st.merged->p, *hstatus = st.host + ns;
+        {
+            StreamSwap on_comm(c, cs);
+            const int64_t *gathered = send;                        // (one rank: no gather, the merge reads the send block)
+            if (m.world > 1) {
+                all_gather(c, send, st.recv->p, sizeof(int64_t) * (size_t)st.block, cs);
+                gathered = (const int64_t *)st.recv->p;
+            }
+            HIP_CHECK(launch_merge_words_batch(gathered, m.world, st.block, (const int64_t *)st.seg->p, ns, st.words, (const int32_t *)st.ops->p, merged,
+                                               (int64_t *)st.status->p, cs));
+            HIP_CHECK(hipMemcpyAsync(hstatus, st.status->p, sizeof(int64_t) * 2 * (size_t)ns, hipMemcpyDeviceToHost, cs));     // ahead of the words
+            // ---- finalisation, per plan, of its merged segment ----
+            for (int q = 0; q < ns; q++) {
+                if (rc[(size_t)q] != VDL_OK) continue;             // (it failed here: nothing of its own to finalise)
+                const int r = vdl_finalize_begin(c, sp[(size_t)q], merged + st.first[(size_t)q], 0);
+                if (r != VDL_OK) { rc[(size_t)q] = r; why[(size_t)q] = c->err; }
+            }
+            if (overlap) {
+                HIP_CHECK(hipEventRecord(st.ev_merged, cs));
+                HIP_CHECK(hipStreamWaitEvent(c->stream, st.ev_merged, 0));     // the next call's local phase writes the send block again
+            }
+            HIP_CHECK(hipStreamSynchronize(cs));                   // the status words are read below, whichever plans finalise
+        }
+        // Every rank reads the same status words: the lowest failing plan fails the call, the others keep their answers.
+        int bad = -1, bad_rc = VDL_OK;
+        std::string bad_why;
+        for (int q = 0; q < ns; q++) {
+            vdl_plan *p = sp[(size_t)q];
+            const int i = L.shared[(size_t)q];
+            int r = (int)rc[(size_t)q];
+            std::string w = why[(size_t)q];
+            if (r == VDL_OK) {
+                r = vdl_finalize_end(c, p, 0);
+                if (r != VDL_OK) w = c->err;
+            }
+            p->batch_words = false;
+            if (r == VDL_OK && hstatus[2 * q] != VDL_OK) {
+                r = VDL_ERR_UNSUPPORTED;
+                w = "sharded run: the local phase failed on rank " + std::to_string(hstatus[2 * q + 1]) + " (status " + std::to_string(hstatus[2 * q]) +
+                    "); the merged words are not an answer";
+            }
+            if (r == VDL_OK && p->order.set && p->order.sharded) {
+                r = guard(c, [&] { order_outputs_on_host(c, p); });
+                if (r != VDL_OK) w = c->err;
+            }
+            if (r != VDL_OK) p->outs.clear();
+            if (r != VDL_OK && bad < 0) { bad = i; bad_rc = r; bad_why = w; }
+        }
+        if (bad >= 0) throw Error(bad_rc, "plan " + std::to_string(bad) + ": " + bad_why);       // (no own plan is started, on any rank)
+    }
+    for (int i = 0; i < n; i++) {
+        if (L.off[(size_t)i] >= 0) continue;
+        const int r = vdl_run_sharded(c, plans[i]);
+        if (r != VDL_OK) throw Error(r, "plan " + std::to_string(i) + ": " + c->err);
+    }
+}
+
 }  // namespace eng
 }  // namespace vdl
 
@@ -1091,6 +1329,63 @@ int vdl_run_sharded(vdl_ctx *c, vdl_plan *p) {
     });
     if (rc != VDL_OK) return rc;
     return fold_route(c, p) ? vdl_run_sharded_end(c, p, 0) : VDL_OK;
+}
+
+/* K plans in one sharded call (vdl.h): the shared plans' partial words travel in ONE all-gather and are merged by ONE launch; the
+ * others run through vdl_run_sharded afterwards, in call order */
+int vdl_run_batch_sharded(vdl_ctx *c, vdl_plan *const *plans, int n) {
+    if (const int rc = batch_args_check(c, plans, n, "vdl_run_batch_sharded")) return rc;
+    return guard(c, [&] { run_batch_sharded(c, plans, n); });
+}
+
+int vdl_batch_sharded_layout(vdl_ctx *c, vdl_plan *const *plans, int n, int64_t *offsets, int64_t *heights, int64_t *block_words) {
+    if (const int rc = batch_args_check(c, plans, n, "vdl_batch_sharded_layout")) return rc;
+    return guard(c, [&] {
+        BatchLayout L;
+        batch_sharded_classify(c, plans, n, "vdl_batch_sharded_layout", L);
+        for (int i = 0; i < n; i++) {
+            if (offsets) offsets[i] = L.off[(size_t)i];
+            if (heights) heights[i] = L.height[(size_t)i];
+        }
+        if (block_words) *block_words = L.block;
+    });
+}
+
+const char *vdl_plan_batch_sharded_note(const vdl_plan *p) { return p ? p->batch_sharded_note.c_str() : ""; }
+
+/* ... and the merge of a sharded BATCH's blocks (what k_merge_words_batch applies): plan q's segment starts at offsets[q] of every rank's
+ * block_words words and is [raw n_words[q]][resolved n_words[q], only if one of its operators is VDL_REDUCE_FIRST][status];
+ * ops_concat / out_concat hold the plans' operators / merged words one after the other, status_out {status, rank} per plan */
+int vdl_comm_merge_host_batch(int world, int n, const int64_t *n_words, const int64_t *offsets, const int32_t *ops_concat, const int64_t *gathered, int64_t block_words,
+                              int64_t *out_concat, int64_t *status_out) {
+    if (world < 1 || n < 1 || !n_words || !offsets || !gathered || block_words < 1) return VDL_ERR_ARG;
+    int64_t first = 0;
+    for (int q = 0; q < n; q++) {
+        const int64_t nw = n_words[q];
+        if (nw < 0 || (nw && (!ops_concat || !out_concat))) return VDL_ERR_ARG;
+        bool any_first = false;
+        for (int64_t i = 0; i < nw; i++) any_first |= ops_concat[first + i] == VDL_REDUCE_FIRST;
+        const int64_t h = (any_first ? 2 : 1) * nw + 1;
+        if (offsets[q] < 0 || offsets[q] + h > block_words) return VDL_ERR_ARG;
+        first += nw;
+    }
+    first = 0;
+    for (int q = 0; q < n; q++) {
+        const int64_t nw = n_words[q];
+        bool any_first = false;
+        for (int64_t i = 0; i < nw; i++) any_first |= ops_concat[first + i] == VDL_REDUCE_FIRST;
+        for (int64_t i = 0; i < nw; i++) out_concat[first + i] = merge_word(gathered + offsets[q], world, nw, ops_concat[first + i], i, block_words);
+        if (status_out) {
+            const int64_t at = offsets[q] + (any_first ? 2 : 1) * nw;
+            status_out[2 * q] = 0; status_out[2 * q + 1] = -1;
+            for (int r = world - 1; r >= 0; r--) {
+                const int64_t x = gathered[(int64_t)r * block_words + at];
+                if (x != 0) { status_out[2 * q] = x; status_out[2 * q + 1] = r; }
+            }
+        }
+        first += nw;
+    }
+    return VDL_OK;
 }
 
 /* The merge of the gathered partial words on the HOST: the same per-word rule the device kernel applies (merge_word,

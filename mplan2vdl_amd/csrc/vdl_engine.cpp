@@ -1524,19 +1524,23 @@ int vdl_run(vdl_ctx *c, vdl_plan *p) { return run_plan(c, p, nullptr); }
 
 // ---- batched runs: plans that differ in their literals alone share one pass over the columns -----------
 namespace {
-// Groups the plans (vdl_specialise.cpp says which may share a scan and why not), cuts every group into batches of at most
-// batch_cap plans (grouped scans: batch_group_cap) and runs each batch as one scan; every other plan runs alone through vdl_run.
-// A plan of a grouped batch whose rows carry keys outside the pivots is rerun alone inside the call; its partners keep their answers.
-// check_only (vdl_batch_jit_check): the grouping, the builds and the notes, nothing loaded or run.
-void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
+// The grouping half of a batched run (vdl_specialise.cpp says which plans may share a scan and why not): every group cut into batches
+// of at most batch_cap plans (grouped scans: batch_group_cap); alone[i] = why plan i runs alone, "" for a plan of a batch.
+struct BatchGrouping {
     std::vector<BatchMember> members;
+    std::vector<std::string> alone;
+    std::vector<std::vector<BatchMember *>> batches;
+};
+void batch_group(vdl_ctx *c, vdl_plan *const *plans, int n, bool grouped_on, BatchGrouping &G) {
+    std::vector<BatchMember> &members = G.members;
     members.reserve((size_t)n);
-    std::vector<std::string> alone((size_t)n);
+    std::vector<std::string> &alone = G.alone;
+    alone.assign((size_t)n, std::string());
     for (int i = 0; i < n; i++) {
         vdl_plan *p = plans[i];
         p->batch_note.clear();
         p->batch_code_bytes = 0;
-        alone[(size_t)i] = batch_alone_reason(p, c->batch_grouped);
+        alone[(size_t)i] = batch_alone_reason(p, grouped_on);
         if (!alone[(size_t)i].empty()) continue;
         BatchMember m;
         m.index = i;
@@ -1551,7 +1555,7 @@ void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
             if (g[0]->cols_key == m.cols_key && g[0]->shape_key == m.shape_key) { g.push_back(&m); placed = true; break; }
         if (!placed) groups.push_back({&m});
     }
-    std::vector<std::vector<BatchMember *>> batches;
+    std::vector<std::vector<BatchMember *>> &batches = G.batches;
     for (auto &g : groups) {
         if (g.size() == 1) {
             bool same_cols = false;
@@ -1568,52 +1572,72 @@ void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
             batches.emplace_back(g.begin() + (std::ptrdiff_t)at, g.begin() + (std::ptrdiff_t)(at + k));
         }
     }
-    struct Events {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    };
+}
+struct BatchEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~BatchEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+// The scan half: batch b of the grouping as ONE scan, slot q's words left at outs[ms[q]->index] -- the caller's pointers (a sharded
+// batch: into its send block) or, with outs null, the plans' own word buffers.  Every plan of the batch is given the word layout a
+// finalisation reads, and its note; nothing is finalised here.  Returns the kernel's name.
+std::string batch_scan_one(vdl_ctx *c, const std::vector<BatchMember *> &ms, size_t b, bool check_only, int64_t *const *outs_given, BatchEvents &ev) {
+    const int K = (int)ms.size();
+    bool tune = true, profiling = false;
+    int64_t *outs[kMaxBatch] = {};
+    for (int q = 0; q < K; q++) {
+        vdl_plan *p = ms[(size_t)q]->p;
+        tune = tune && p->jit_tune;
+        profiling = profiling || p->profiling;
+        if (check_only) continue;
+        const MScanDesc &d = *ms[(size_t)q]->desc;
+        const bool grouped = ms[(size_t)q]->grouped;
+        const int64_t nw = grouped ? d.pcount * (d.nagg + 1) + 1 : d.nagg + 1;
+        if (outs_given) outs[q] = outs_given[ms[(size_t)q]->index];
+        else {
+            if (!p->words || p->words_cap < nw) { p->words = dev_alloc(c, sizeof(int64_t) * (size_t)nw); p->words_cap = nw; }
+            outs[q] = (int64_t *)p->words->p;
+        }
+        p->order_note.clear();
+        if (!p->bound || p->bound_version != c->binding_version()) {
+            // finalize_begin / finalize_end read the plan's word layout: one global scan, its words first -- or one grouped scan, whose
+            // pivots and aggregate count they take from its descriptor.  The plan stays unbound -- its own kernels are built when it is
+            // run alone
+            p->bound = false;
+            p->reduce_ops.clear();
+            p->n_words = plan_words(p, &p->reduce_ops, nullptr);
+            p->word_offset.assign(grouped ? 0 : 1, 0);
+            p->gword_offset.assign(grouped ? 1 : 0, 0);
+            if (grouped) p->mdesc.assign(1, d);
+            p->batch_words = true;
+        }
+    }
+    if (profiling && !check_only && !outs_given) { HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); }
+    std::string name;
+    size_t code_bytes = 0;
+    try {
+        name = batch_scan(c, ms, tune, check_only, outs, ev.a, ev.b, &code_bytes);
+    } catch (const Error &e) {
+        throw Error(e.code, "plan " + std::to_string(ms[0]->index) + " (batch " + std::to_string(b) + "): " + e.what());
+    }
+    for (int q = 0; q < K; q++) {
+        ms[(size_t)q]->p->batch_note = "batch " + std::to_string(b) + ": slot " + std::to_string(q) + " of " + std::to_string(K) + ", " + name;
+        ms[(size_t)q]->p->batch_code_bytes = code_bytes;
+    }
+    return name;
+}
+// A batched run: the grouping, each batch as one scan and its plans' finalisation; every other plan runs alone through vdl_run.
+// A plan of a grouped batch whose rows carry keys outside the pivots is rerun alone inside the call; its partners keep their answers.
+// check_only (vdl_batch_jit_check): the grouping, the builds and the notes, nothing loaded or run.
+void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
+    BatchGrouping G;
+    batch_group(c, plans, n, c->batch_grouped, G);
+    std::vector<std::string> &alone = G.alone;
+    const std::vector<std::vector<BatchMember *>> &batches = G.batches;
     for (size_t b = 0; b < batches.size(); b++) {
         const std::vector<BatchMember *> &ms = batches[b];
         const int K = (int)ms.size();
-        bool tune = true, profiling = false;
-        int64_t *outs[kMaxBatch] = {};
-        for (int q = 0; q < K; q++) {
-            vdl_plan *p = ms[(size_t)q]->p;
-            tune = tune && p->jit_tune;
-            profiling = profiling || p->profiling;
-            if (check_only) continue;
-            const MScanDesc &d = *ms[(size_t)q]->desc;
-            const bool grouped = ms[(size_t)q]->grouped;
-            const int64_t nw = grouped ? d.pcount * (d.nagg + 1) + 1 : d.nagg + 1;
-            if (!p->words || p->words_cap < nw) { p->words = dev_alloc(c, sizeof(int64_t) * (size_t)nw); p->words_cap = nw; }
-            outs[q] = (int64_t *)p->words->p;
-            p->order_note.clear();
-            if (!p->bound || p->bound_version != c->binding_version()) {
-                // finalize_begin / finalize_end read the plan's word layout: one global scan, its words first -- or one grouped scan, whose
-                // pivots and aggregate count they take from its descriptor.  The plan stays unbound -- its own kernels are built when it is
-                // run alone
-                p->bound = false;
-                p->reduce_ops.clear();
-                p->n_words = plan_words(p, &p->reduce_ops, nullptr);
-                p->word_offset.assign(grouped ? 0 : 1, 0);
-                p->gword_offset.assign(grouped ? 1 : 0, 0);
-                if (grouped) p->mdesc.assign(1, d);
-                p->batch_words = true;
-            }
-        }
-        Events ev;
-        if (profiling && !check_only) { HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); }
-        std::string name;
-        size_t code_bytes = 0;
-        try {
-            name = batch_scan(c, ms, tune, check_only, outs, ev.a, ev.b, &code_bytes);
-        } catch (const Error &e) {
-            throw Error(e.code, "plan " + std::to_string(ms[0]->index) + " (batch " + std::to_string(b) + "): " + e.what());
-        }
-        for (int q = 0; q < K; q++) {
-            ms[(size_t)q]->p->batch_note = "batch " + std::to_string(b) + ": slot " + std::to_string(q) + " of " + std::to_string(K) + ", " + name;
-            ms[(size_t)q]->p->batch_code_bytes = code_bytes;
-        }
+        BatchEvents ev;
+        const std::string name = batch_scan_one(c, ms, b, check_only, nullptr, ev);
         if (check_only) continue;
         for (int q = 0; q < K; q++) finalize_begin(c, ms[(size_t)q]->p, (const int64_t *)ms[(size_t)q]->p->words->p, 0);
         float ms_scan = 0;
@@ -1666,6 +1690,43 @@ int batch_args_ok(vdl_ctx *c, vdl_plan *const *plans, int n, const char *who) {
     return VDL_OK;
 }
 }  // namespace
+
+extern "C++" {                 // (engine-internal: declared in vdl_engine_internal.h, called from vdl_comm.cpp)
+namespace vdl {
+namespace eng {
+int batch_args_check(vdl_ctx *c, vdl_plan *const *plans, int n, const char *who) { return batch_args_ok(c, plans, n, who); }
+// The local phase of a sharded batch (vdl_comm.cpp: vdl_run_batch_sharded): run_batches' grouping and scan halves over plans whose one
+// scan is a global aggregate scan, slot words left at outs[i], no finalisation -- the words are one rank's partial words.  Grouped
+// scans are not grouped here whatever vdl_set_batch_grouped says: the grouped batch kernel finishes as a single rank would.  A batch
+// whose scan throws fails ITS plans (code and message in `res`) and nobody else's: the caller still owes its peers the collective.
+void batch_local_scans(vdl_ctx *c, vdl_plan *const *plans, int n, int64_t *const *outs, std::vector<BatchLocal> &res) {
+    res.assign((size_t)n, BatchLocal{});
+    BatchGrouping G;
+    batch_group(c, plans, n, false, G);
+    for (size_t b = 0; b < G.batches.size(); b++) {
+        const std::vector<BatchMember *> &ms = G.batches[b];
+        int rc = VDL_OK;
+        std::string why;
+        try {
+            BatchEvents ev;
+            (void)batch_scan_one(c, ms, b, false, outs, ev);
+        } catch (const Error &e) { rc = e.code; why = e.what(); }
+        catch (const std::bad_alloc &) { rc = VDL_ERR_NOMEM; why = "out of host memory"; }
+        catch (const std::exception &e) { rc = VDL_ERR_ARG; why = e.what(); }
+        for (const BatchMember *m : ms) {
+            BatchLocal &r = res[(size_t)m->index];
+            r.batched = true;
+            r.rc = rc;
+            r.err = why;
+            if (rc != VDL_OK) m->p->batch_words = false;
+        }
+    }
+    for (int i = 0; i < n; i++)
+        if (!res[(size_t)i].batched) plans[i]->batch_note = "alone: " + G.alone[(size_t)i];
+}
+}  // namespace eng
+}  // namespace vdl
+}  // extern "C++"
 
 int vdl_run_batch(vdl_ctx *c, vdl_plan *const *plans, int n) {
     if (const int rc = batch_args_ok(c, plans, n, "vdl_run_batch")) return rc;

@@ -360,6 +360,7 @@ struct vdl_plan {
     std::string batch_note;                  // what the last vdl_run_batch / vdl_batch_jit_check did with this plan ("" after a plain vdl_run)
     size_t batch_code_bytes = 0;             // the code size of the batch kernel that served the plan in that call, 0 = none did
     bool batch_words = false;                // vdl_run_batch: n_words / word_offset are set for a finalisation although the plan is not bound
+    std::string batch_sharded_note;          // what the last vdl_run_batch_sharded / vdl_batch_sharded_layout did with this plan (vdl_plan_batch_sharded_note)
     // by scan role ("scan<k>", "front.select", "front.take", "dim<k>", "semi<k>"), of the scan bound last (note_roles): the catalog
     // columns it read from their byte or packed images, "name:width ..." (vdl_plan_image_columns); those it read from their step
     // images, "name:s ..." (vdl_plan_step_columns); the target columns its lookups read from their images, "name:width ..."
@@ -640,6 +641,15 @@ bool run_projection(vdl_ctx *c, vdl_plan *p, std::map<int, DVec> &over);     // 
 bool general_partial_spec(const vdl_plan *p, std::vector<int32_t> &ops, std::string &why);
 void general_run_local(vdl_ctx *c, vdl_plan *p, int64_t *dev_words);
 void general_finalize(vdl_ctx *c, vdl_plan *p, const int64_t *dev_words);
+// ---- the halves of a batched run that a sharded batch calls (vdl_engine.cpp; vdl_run_batch_sharded in vdl_comm.cpp) ----
+int batch_args_check(vdl_ctx *c, vdl_plan *const *plans, int n, const char *who);       // vdl_run_batch's argument errors, under the caller's name
+struct BatchLocal {
+    bool batched = false;      // the plan's words were written by a batch scan (else its batch note says why it is left to the caller)
+    int rc = 0;                // ... which failed with this code and message on this rank
+    std::string err;
+};
+// grouping and scans of the plans whose one scan is a global aggregate scan: slot words at outs[i], nothing finalised
+void batch_local_scans(vdl_ctx *c, vdl_plan *const *plans, int n, int64_t *const *outs, std::vector<BatchLocal> &res);
 
 template <typename F>
 int guard(vdl_ctx *c, F &&f) {

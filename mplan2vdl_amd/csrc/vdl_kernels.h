@@ -216,6 +216,11 @@ hipError_t launch_wide_fits_record(const int64_t *rec, const int64_t *hi, int64_
 hipError_t launch_or_sets(const uint64_t *gathered, int world, int64_t words, uint64_t *out, hipStream_t s);
 hipError_t launch_merge_words(const int64_t *gathered, int world, int64_t n_words, int64_t stride, const int32_t *ops, int64_t *out,
                               int64_t *status_out, hipStream_t s);
+// the merge of a sharded batch (vdl_run_batch_sharded): rank blocks of block_words = the plans' segments one after the other, each
+// [raw nw][resolved nw, only where the plan has a FIRST word][status]; seg (device) = {offset, nw, index of its first word in out} per plan,
+// n plans, total_words = the sum of the nw; out = every plan's merged words one after the other, status_out = 2 words per plan
+hipError_t launch_merge_words_batch(const int64_t *gathered, int world, int64_t block_words, const int64_t *seg, int n, int64_t total_words, const int32_t *ops,
+                                    int64_t *out, int64_t *status_out, hipStream_t s);
 // the wide merge (vdl_mscan_wide.hip): out / out_hi = merge_word_wide of every word, status_out as launch_merge_words; one lane per word
 hipError_t launch_merge_words_wide(const int64_t *gathered, int world, int64_t n_words, int64_t stride, const int32_t *ops, int64_t *out,
                                    int64_t *out_hi, int64_t *status_out, hipStream_t s);

@@ -472,6 +472,41 @@ hipError_t launch_merge_words(const int64_t *gathered, int world, int64_t n_word
     k_merge_words<<<(int)((std::max<int64_t>(n_words, 1) + 255) / 256), 256, 0, s>>>(gathered, world, n_words, stride, ops, out, status_out);
     return launch_status();
 }
+// The merge of a sharded BATCH (vdl_run_batch_sharded): a rank block of `block` words is the concatenation of one segment per plan,
+// [raw nw][resolved nw, where the plan has a FIRST word][status]; seg holds {offset in the block, nw, index of the plan's first word
+// among all W merged words} per plan.  One lane per merged word: it finds its plan by binary search on the first-word indices (the
+// last plan whose index is <= its own: a plan without words shares its index with its successor and is never chosen) and applies
+// merge_word inside that plan's segment, the rank stride being the whole block.  n further lanes leave {first non-zero status, its
+// rank} per plan, as k_merge_words does for one: a segment's status is its last word, the word before the next segment.
+__global__ __launch_bounds__(256) void k_merge_words_batch(const int64_t *__restrict__ g, int world, int64_t block, const int64_t *__restrict__ seg, int n, int64_t W,
+                                                           const int32_t *__restrict__ ops, int64_t *__restrict__ out, int64_t *__restrict__ status_out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < W) {
+        int lo = 0, hi = n - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (seg[3 * mid + 2] <= t) lo = mid; else hi = mid - 1;
+        }
+        const int64_t off = seg[3 * lo], nw = seg[3 * lo + 1], i = t - seg[3 * lo + 2];
+        if (i < nw) out[t] = merge_word(g + off, world, nw, ops[t], i, block);
+    } else if (t < W + n) {
+        const int q = (int)(t - W);
+        const int64_t at = (q + 1 < n ? seg[3 * (q + 1)] : block) - 1;
+        int64_t st = 0, who = -1;
+        for (int r = world - 1; r >= 0; r--) {
+            const int64_t x = g[(int64_t)r * block + at];
+            if (x != 0) { st = x; who = r; }
+        }
+        status_out[2 * q] = st; status_out[2 * q + 1] = who;
+    }
+}
+hipError_t launch_merge_words_batch(const int64_t *gathered, int world, int64_t block_words, const int64_t *seg, int n, int64_t total_words, const int32_t *ops,
+                                    int64_t *out, int64_t *status_out, hipStream_t s) {
+    (void)hipGetLastError();
+    if (n < 1 || world < 1 || total_words < 0 || block_words < n + total_words || !gathered || !seg || !status_out || (total_words && (!ops || !out))) return hipErrorInvalidValue;
+    k_merge_words_batch<<<(int)((total_words + n + 255) / 256), 256, 0, s>>>(gathered, world, block_words, seg, n, total_words, ops, out, status_out);
+    return launch_status();
+}
 __global__ void k_onehot_dense(const int64_t *oh, int64_t *out, uint64_t *valid, int64_t n) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t slot = oh[2] > 0 ? oh[1] : -1;

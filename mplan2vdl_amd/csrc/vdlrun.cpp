@@ -36,7 +36,13 @@
 // --batch FILE (repeatable; needs --jit or --jit-tune): the program on stdin and the programs in the files run as ONE vdl_run_batch --
 // those that differ in their literals alone share one scan of the columns, the others run alone inside the same call -- and one reply
 // is printed per line, stdin's first.  The options (--order-by included) apply to every program.  One line per program "vdlrun:
-// batch: <vdl_plan_batch_note>" goes to stderr.  Not with --gpus: a sharded run takes one plan.
+// batch: <vdl_plan_batch_note>" goes to stderr.  With --gpus only together with --batch-sharded.
+//   ... | vdlrun --gpus N --jit --batch b.vdl --batch-sharded ...                  several programs in one sharded call
+// --batch-sharded (needs --gpus, --batch and --jit or --jit-tune): every rank calls vdl_run_batch_sharded with the programs -- those that
+// fuse as a whole on the fold route share ONE all-gather and ONE merge, the others run through vdl_run_sharded inside the call -- the rank
+// replies are marked replicated and rank 0's are printed, stdin's first, then the --batch programs' in their order.  One line per program
+// "vdlrun: batch-sharded: <vdl_plan_batch_sharded_note>; <vdl_plan_batch_note>" goes to stderr (rank 0's).  Without it --gpus refuses
+// --batch before any rank starts: vdl_run_sharded takes one plan.
 //   ... | vdlrun --wide-sums ...  |  vdlrun --checked-sums ...                       exact 128-bit SUM results
 // --wide-sums (vdl_plan_set_wide_sums 1): the reply keeps its shape and every value is printed as the exact decimal integer, of any
 // size (JSON has no limit; Python's json reads them as ints and resolve.py passes ints through).  --checked-sums (mode 2): a value
@@ -225,7 +231,7 @@ bool read_reply(const std::string &path, Reply &r) {
 struct Options {
     int64_t rows = 60175;           // SF0.01 lineitem, /root/reference/tests/tpchnoorder/bounds.csv:59
     uint64_t seed = 0x5EED0006ULL;
-    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0, lookup_images = 0;
+    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0, batch_sharded = 0, lookup_images = 0;
     int wide = -1;                  // --wide-sums 1 / --checked-sums 2; -1: as the plan was parsed (VDL_WIDE_SUMS)
     int wide_sharded = 0;           // --wide-sharded: vdl_plan_set_wide_sums_sharded
     int wide_tail = 0;              // --wide-tail: vdl_plan_set_wide_sums_tail (only together with --wide-sums | --checked-sums)
@@ -353,13 +359,20 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
             if (!got) { std::fprintf(stderr, "vdlrun: rank %d never saw the communicator id\n", rank); return 1; }
         }
         if ((rc = vdl_comm_init(ctx, rank, world, id))) return die(ctx, "vdl_comm_init", rc);
-        vdl_plan_set_sharded_table(plan, o.shard.c_str());
-        vdl_plan_set_row_offset(plan, row0);
-        int whole = 0;
-        const char *route = nullptr;
-        if ((rc = vdl_plan_sharded_route(ctx, plan, &route, &whole))) return die(ctx, "vdl_plan_sharded_route", rc);
-        reply.replicated = whole != 0;
-        if ((rc = vdl_run_sharded(ctx, plan))) return die(ctx, "vdl_run_sharded", rc);
+        for (vdl_plan *one : plans) { vdl_plan_set_sharded_table(one, o.shard.c_str()); vdl_plan_set_row_offset(one, row0); }
+        if (o.batch_sharded) {
+            // every program in ONE sharded call; what the call leaves on a rank is taken as the answer (rank 0's is printed)
+            reply.replicated = true;
+            if ((rc = vdl_run_batch_sharded(ctx, plans.data(), (int)plans.size()))) return die(ctx, "vdl_run_batch_sharded", rc);
+            if (rank == 0)
+                for (vdl_plan *one : plans) std::fprintf(stderr, "vdlrun: batch-sharded: %s; %s\n", vdl_plan_batch_sharded_note(one), vdl_plan_batch_note(one));
+        } else {
+            int whole = 0;
+            const char *route = nullptr;
+            if ((rc = vdl_plan_sharded_route(ctx, plan, &route, &whole))) return die(ctx, "vdl_plan_sharded_route", rc);
+            reply.replicated = whole != 0;
+            if ((rc = vdl_run_sharded(ctx, plan))) return die(ctx, "vdl_run_sharded", rc);
+        }
     }
     collect(plan, reply);
     for (size_t k = 1; k < plans.size() && more; k++) { more->emplace_back(); collect(plans[k], more->back()); }
@@ -398,6 +411,7 @@ int main(int argc, char **argv) {
         else if (a == "--shard" && i + 1 < argc) o.shard = argv[++i];
         else if (a == "--batch" && i + 1 < argc) o.batch_files.push_back(argv[++i]);
         else if (a == "--batch-grouped") o.batch_grouped = 1;
+        else if (a == "--batch-sharded") o.batch_sharded = 1;
         else if (a == "--lookup-images") o.lookup_images = 1;
         else if (a == "--wide-sums") o.wide = 1;
         else if (a == "--checked-sums") o.wide = 2;
@@ -416,7 +430,7 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--lookup-images] [--wide-sums | --checked-sums] [--wide-sharded] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--batch-sharded] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--lookup-images] [--wide-sums | --checked-sums] [--wide-sharded] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }
@@ -449,7 +463,11 @@ int main(int argc, char **argv) {
             return 3;
         }
     }
-    if (sharded && !o.describe && !o.batch_files.empty()) {
+    if (o.batch_sharded && (!sharded || o.batch_files.empty() || !o.jit)) {
+        std::fprintf(stderr, "usage: vdlrun --batch-sharded needs --gpus N, --batch FILE and --jit or --jit-tune: it runs the programs as one vdl_run_batch_sharded on every rank\n");
+        return 2;
+    }
+    if (sharded && !o.describe && !o.batch_files.empty() && !o.batch_sharded) {
         std::fprintf(stderr, "vdlrun: --batch is not served with --gpus: a sharded run takes one plan; run the batch on one GPU\n");
         return 3;
     }
@@ -476,8 +494,11 @@ int main(int argc, char **argv) {
         if (pid == 0) {
             dup2(2, 1);                                      // stdout carries the parent's reply only (RCCL prints a banner at start-up)
             Reply mine;
-            int rc = run_rank(o, text, r, o.gpus, dir, mine);
+            std::vector<Reply> more;
+            int rc = run_rank(o, text, r, o.gpus, dir, mine, &more);
             if (rc == 0 && !write_reply(std::string(dir) + "/out." + std::to_string(r), mine)) rc = 1;
+            for (size_t k = 0; k < more.size() && rc == 0 && r == 0; k++)       // (--batch-sharded: rank 0's further replies are the ones printed)
+                if (!write_reply(std::string(dir) + "/out.0." + std::to_string(k + 1), more[k])) rc = 1;
             std::fflush(nullptr);
             _exit(rc);
         }
@@ -506,10 +527,17 @@ int main(int argc, char **argv) {
             all.outs[k].hi.insert(all.outs[k].hi.end(), part.outs[k].hi.begin(), part.outs[k].hi.end());
         }
     }
+    std::vector<Reply> more(o.batch_sharded ? o.batch_texts.size() : 0);
+    for (size_t k = 0; k < more.size(); k++) {
+        const std::string path = std::string(dir) + "/out.0." + std::to_string(k + 1);
+        if (!failed && !read_reply(path, more[k])) failed++;
+        std::remove(path.c_str());
+    }
     for (int r = 0; r < o.gpus; r++) std::remove((std::string(dir) + "/out." + std::to_string(r)).c_str());
     std::remove((std::string(dir) + "/id").c_str());
     rmdir(dir);
     if (failed) { std::fprintf(stderr, "vdlrun: %d rank(s) failed\n", failed); return 1; }
     print_reply(all);
+    for (const Reply &m : more) print_reply(m);
     return 0;
 }

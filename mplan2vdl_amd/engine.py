@@ -272,6 +272,11 @@ class Plan:
         "alone: <reason>"; "" after a plain run() (vdl.h: vdl_plan_batch_note)."""
         return (self._e._L.vdl_plan_batch_note(self._h) or b"").decode()
 
+    def batch_sharded_note(self):
+        """What the last Engine.run_batch_sharded / batch_sharded_layout did with this plan: "collective <c>: words [<off>,<off+h>) of
+        <B>" or "own: <route> route" (vdl.h: vdl_plan_batch_sharded_note)."""
+        return (self._e._L.vdl_plan_batch_sharded_note(self._h) or b"").decode()
+
     def batch_code_bytes(self):
         """The code size of the batch kernel that served this plan in the last Engine.run_batch / batch_jit_check; 0 when it ran alone."""
         return int(self._e._L.vdl_plan_batch_code_bytes(self._h))
@@ -442,6 +447,32 @@ def comm_merge_host_wide(world, ops, gathered, stride_words=0):
     if rc != _lib.VDL_OK:
         raise VdlError(rc, "vdl_comm_merge_host_wide: bad argument")
     return lo, hi, (int(status[0]), int(status[1]))
+
+
+def comm_merge_host_batch(world, n_words, offsets, ops, gathered, block_words):
+    """vdl_comm_merge_host_batch: the merge of a sharded batch's gathered blocks, device-free.  Plan q has n_words[q] words, its
+    operators ops[q] (a list per plan) and its segment at offsets[q] of every rank's block of `block_words` int64: the raw words, the
+    words with FIRST entries resolved (only where the plan has a FIRST word), the rank's status.  Returns ([merged words per plan],
+    [(status, rank) per plan]) -- rank -1 = no rank failed."""
+    L = _lib.load()
+    n = len(n_words)
+    if len(offsets) != n or len(ops) != n or any(len(o) != w for o, w in zip(ops, n_words)):
+        raise ValueError("one offset and one operator list of n_words[q] entries per plan")
+    g = np.ascontiguousarray(gathered, dtype=np.int64)
+    if len(g) < world * int(block_words):
+        raise ValueError("gathered holds fewer than world * block_words values")
+    flat = [int(o) for per in ops for o in per]
+    c_ops = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    nw = np.ascontiguousarray(n_words, dtype=np.int64)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    out, status = np.zeros(max(len(flat), 1), np.int64), np.zeros(2 * max(n, 1), np.int64)
+    p64 = ctypes.POINTER(ctypes.c_int64)
+    rc = L.vdl_comm_merge_host_batch(int(world), n, nw.ctypes.data_as(p64), off.ctypes.data_as(p64), c_ops, g.ctypes.data_as(p64), int(block_words),
+                                     out.ctypes.data_as(p64), status.ctypes.data_as(p64))
+    if rc != _lib.VDL_OK:
+        raise VdlError(rc, "vdl_comm_merge_host_batch: bad argument")
+    cuts = np.cumsum([0] + [int(w) for w in n_words])
+    return [out[cuts[q]:cuts[q + 1]].copy() for q in range(n)], [(int(status[2 * q]), int(status[2 * q + 1])) for q in range(n)]
 
 
 def collate_host(heap, codes):
@@ -731,6 +762,23 @@ class Engine:
         plans, arr = self._handles(plans)
         self._check(self._L.vdl_run_batch(self._c, arr, len(plans)))
         return [p._collect(as_numpy) for p in plans]
+
+    def run_batch_sharded(self, plans, as_numpy=False):
+        """Run the plans in ONE sharded call (vdl.h: vdl_run_batch_sharded): the plans that fuse as a whole on the fold route share
+        one all-gather and one merge, the others run through run_sharded afterwards; the list of the dicts `Plan.run_sharded()`
+        returns, in the plans' order.  `Plan.batch_sharded_note()` and `Plan.batch_note()` say what became of each."""
+        plans, arr = self._handles(plans)
+        self._check(self._L.vdl_run_batch_sharded(self._c, arr, len(plans)))
+        return [p._collect(as_numpy) for p in plans]
+
+    def batch_sharded_layout(self, plans):
+        """([offset per plan, -1 = an own plan], [height per plan], block words) of the rank block run_batch_sharded would gather
+        (vdl_batch_sharded_layout; needs neither a device nor a communicator)."""
+        plans, arr = self._handles(plans)
+        n = len(plans)
+        off, h, b = (ctypes.c_int64 * max(n, 1))(), (ctypes.c_int64 * max(n, 1))(), ctypes.c_int64()
+        self._check(self._L.vdl_batch_sharded_layout(self._c, arr, n, off, h, ctypes.byref(b)))
+        return list(off)[:n], list(h)[:n], b.value
 
     def set_batch_grouped(self, on):
         """True: run_batch also batches plans whose one scan is a GROUP BY over table columns (vdl.h: vdl_set_batch_grouped; off by

@@ -19,14 +19,25 @@ Grouped batches (Engine.set_batch_grouped) on TPC-H Q1: always EIGHT literal set
 WIDTH, pinned by VDL_BATCH_WIDTH (8 sets at K = 4: two batches; at K = 3: 3 + 3 + 2; at K = 2: four), which also fixes the table
 replicas by the LDS rule (K = 4: R = 2, K = 3: R = 4, K = 2: R = 8).  Leg (a) is the eight tuned run()s, leg (b) run_batch of the
 eight; per-query figures divide by eight.  The batch kernels' time is the sum over the call's batches, the bytes n x the sum of the
-image widths per batch.  No CPU check: every answer of (b) must equal (a)'s, and (a)'s kernels are checked by the suite."""
+image widths per batch.  No CPU check: every answer of (b) must equal (a)'s, and (a)'s kernels are checked by the suite.
+
+    python tools/batch_bench.py --sharded [--rows N] [--k 2,4,8] [--repeats 3] [--steps 30] [--parent TREE] [--out FILE]
+
+Sharded batches (Engine.run_batch_sharded) on Q6 over one rank's shard (default 75 004 738 rows, an eighth of SF100) with a ONE-RANK
+RCCL communicator, as tools/wide_bench.py --sharded: no gather is performed, so the figures cover the kernels, the copies and the hop
+to the communication stream, not the interconnect.  Legs, each in fresh processes that alternate, --repeats per side:
+  (a)  K x run_sharded                            (a') K pipelined run_sharded_begin / _end steps over two slots
+  (b)  run_batch_sharded of the K plans           with --parent TREE (a checkout of the parent commit, built): (a) and (a') there too
+A process times --steps call sequences per K and reports their median; the table gives the median over the processes and min .. max,
+checks every answer against (a)'s, and says whether (b) beats (a') by more than the spread of the repeats."""
 import os
 import re
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# (--tree DIR: a child of --sharded imports the package, and with it the library, of another checkout -- the parent commit's build)
+sys.path.insert(0, sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else ROOT)
 import numpy as np
 import torch
 
@@ -41,7 +52,7 @@ def opt(name, default):
     return args[args.index(name) + 1] if name in args else default
 
 
-rows = int(opt("--rows", datagen.LINEITEM_ROWS["sf100"]))
+rows = int(opt("--rows", 75004738 if "--sharded" in args else datagen.LINEITEM_ROWS["sf100"]))      # (--sharded: an eighth of SF100, one rank's shard of an 8-rank job)
 widths = [int(x) for x in str(opt("--k", "1,2,4,8")).split(",")]
 repeats = int(opt("--repeats", 9))
 legs = opt("--legs", "ab")
@@ -106,6 +117,122 @@ def stats(v):
     return "median %8.3f ms   min %8.3f   max %8.3f" % (float(np.median(v)), min(v), max(v))
 
 
+# ---- --sharded: K literal sets over one rank's shard, as K sharded calls or as one sharded batch ------------------------------------------
+def sharded_child(leg):
+    """one fresh process, one leg, every K: prints one line "RESULT <json>" {K: [ms per call sequence, ...], "answers": {K: [...]}}"""
+    import json
+    steps = int(opt("--steps", 30))
+    torch.cuda.set_device(0)
+    eng = m.Engine(0)
+    for name in datagen.Q6_COLUMNS:
+        eng.generate(datagen.LINEITEM[name], 0, rows)
+    eng.comm_init_rccl(0, 1, eng.comm_unique_id())             # one rank: no gather; the kernels, the copies and the stream hop are all there
+    kmax = max(widths)
+    ps = [eng.parse(q6_text(k)) for k in range(kmax)]
+    for p in ps:
+        p.set_jit(True, tune=True, runtime_bounds=True)
+    first = [answer(p.run_sharded()["results"]) for p in ps]   # builds, tunes
+    out = {"answers": {}, "ms": {}}
+    for k in widths:
+        sub = ps[:k]
+        if leg == "a":
+            run = lambda: [answer(p.run_sharded()["results"]) for p in sub]
+        elif leg == "a2":                                       # pipelined: plan j + 1 begun before plan j is collected (two slots)
+            def run():
+                got = []
+                for j, p in enumerate(sub):
+                    p.run_sharded_begin(j & 1)
+                    if j:
+                        got.append(answer(sub[j - 1].run_sharded_end(1 - (j & 1))["results"]))
+                got.append(answer(sub[-1].run_sharded_end((len(sub) - 1) & 1)["results"]))
+                return got
+        else:
+            run = lambda: [answer(r["results"]) for r in eng.run_batch_sharded(sub)]
+        for _ in range(5):
+            got = run()
+        assert got == first[:k], (leg, k)
+        ts = []
+        for _ in range(steps):
+            ms, got = once(run)
+            ts.append(ms)
+        assert got == first[:k], (leg, k)
+        out["ms"][str(k)] = float(np.median(ts))
+        out["answers"][str(k)] = [str(x) for x in got]
+        if leg == "b":
+            out.setdefault("notes", {})[str(k)] = sub[0].batch_note() + " | " + sub[-1].batch_sharded_note()
+    print("RESULT " + json.dumps(out), flush=True)
+    for p in ps:
+        p.close()
+    eng.close()
+
+
+def sharded_main():
+    """(a) K x run_sharded, (a') K pipelined begin / end steps, (b) run_batch_sharded; with --parent TREE also (a) and (a') on that tree"""
+    import json
+    import subprocess
+    parent = opt("--parent", None)
+    sides = [("a", None), ("a2", None), ("b", None)] + ([("a", parent), ("a2", parent)] if parent else [])
+    label = {("a", False): "(a)  K x run_sharded", ("a2", False): "(a') K pipelined begin/end steps", ("b", False): "(b)  run_batch_sharded",
+             ("a", True): "parent (a)", ("a2", True): "parent (a')"}
+    say("Q6 over %d generated rows with images (one rank's shard), a ONE-RANK RCCL communicator: no gather is performed -- the figures cover" % rows)
+    say("the kernels, the copies and the hop to the communication stream, not the interconnect.  K tuned plans; every figure the median of %s"
+        % opt("--steps", 30))
+    say("timed call sequences in a fresh process; %d processes per side, alternating; median over them and min .. max" % repeats)
+    got = {s: [] for s in sides}
+    for _ in range(repeats):
+        for side in sides:
+            leg, tree = side
+            cmd = [sys.executable, os.path.abspath(__file__), "--sharded-child", leg, "--rows", str(rows), "--k", ",".join(map(str, widths)), "--steps", str(opt("--steps", 30))]
+            if tree:
+                cmd += ["--tree", tree]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+            line = [x for x in r.stdout.splitlines() if x.startswith("RESULT ")]
+            if r.returncode != 0 or not line:
+                say("side %s failed (exit %d): %s" % (side, r.returncode, r.stderr[-1500:]))
+                sys.exit(1)
+            got[side].append(json.loads(line[-1][7:]))
+            print("  ... %s%s: %s" % (leg, " (parent)" if tree else "", got[side][-1]["ms"]), flush=True)
+    ok = True
+    for k in widths:
+        say()
+        say("K = %d" % k)
+        med, span = {}, {}
+        for side in sides:
+            v = [g["ms"][str(k)] for g in got[side]]
+            med[side], span[side] = float(np.median(v)), max(v) - min(v)
+            say("  %-34s median %8.3f ms   min %8.3f   max %8.3f   per query %7.3f ms" % (label[(side[0], side[1] is not None)], med[side], min(v), max(v), med[side] / k))
+        same = all(g["answers"][str(k)] == got[("a", None)][0]["answers"][str(k)] for s in sides for g in got[s])
+        ok = ok and same
+        say("  every answer of every side equals (a)'s: %s" % same)
+        gain, spread = med[("a2", None)] - med[("b", None)], max(span[("a2", None)], span[("b", None)])
+        say("  (a') - (b) = %+.3f ms; the wider spread of the two sides' repeats is %.3f ms: (b) %s (a')" %
+            (gain, spread, "beats" if gain > spread else "does not beat by more than the spread of the repeats" if gain > 0 else "is slower than"))
+        say("  (a) - (b) = %+.3f ms" % (med[("a", None)] - med[("b", None)]))
+        if parent:
+            for leg in ("a", "a2"):
+                d = med[(leg, None)] - med[(leg, parent)]
+                say("  %s, this tree - parent: %+.3f ms (spreads %.3f / %.3f)" % (label[(leg, False)].strip(), d, span[(leg, None)], span[(leg, parent)]))
+        say("  notes of (b): %s" % got[("b", None)][0]["notes"][str(k)])
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        open(out_path, "w").write("\n".join(lines) + "\n")
+    sys.exit(0 if ok else 1)
+
+
+def answer(results):
+    return str(sorted(results.items())) if query == "q1" else next(iter(next(iter(results.values())).values()))
+
+
+if "--sharded-child" in args:
+    sharded_child(opt("--sharded-child", "a"))
+    sys.exit(0)
+if "--sharded" in args:
+    if "--k" not in args:
+        widths = [2, 4, 8]
+    if "--repeats" not in args:
+        repeats = 3
+    sharded_main()
+
 torch.cuda.set_device(0)
 e = m.Engine(0)
 e.use_torch_stream()
@@ -119,10 +246,6 @@ plans = [e.parse(q6_text(k)) for k in range(kmax)]
 for p in plans:
     p.set_jit(True, tune=True, runtime_bounds=True)      # (run-time bounds: the K plans of leg (a) share their code, as since round 11)
 t0 = time.perf_counter()
-def answer(results):
-    return str(sorted(results.items())) if query == "q1" else next(iter(next(iter(results.values())).values()))
-
-
 answers = [answer(p.run()["results"]) for p in plans]
 say("first runs of the %d plans (tuning, compiles): %.1f s" % (kmax, time.perf_counter() - t0))
 say("leg (a) kernel of plan 0: %s" % re.findall(r"-> ([^;]*);", plans[0].jit_note())[-1:])
