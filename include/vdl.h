@@ -205,6 +205,9 @@ int  vdl_plan_set_jit_bounds(vdl_plan *plan, int at_run_time);
  * may be null.  (vdl_plan_jit_note also says, per scan of a plan that ran, how many of its builds came from a cache:
  * "from cache: 2 of 3 builds of scan 0; ".) */
 void vdl_jit_counters(int64_t *compiled, int64_t *from_disk, int64_t *from_memory);
+/* Prelude tables built in this process so far: LIKE tables, dimension bitmaps (by a scan or by their witness statements) and semi-join
+ * sets, one count per table and run.  A join batch (vdl_set_batch_joins) builds its tables once, K plans run alone K times. */
+void vdl_prelude_counters(int64_t *items);
 const char *vdl_plan_jit_note(const vdl_plan *plan);
 int  vdl_plan_jit_check(vdl_ctx *ctx, vdl_plan *plan);
 /* Which catalog columns the plan's scans read from their images, as bound at its last run or vdl_plan_jit_check: one entry
@@ -266,11 +269,33 @@ int  vdl_run(vdl_ctx *ctx, vdl_plan *plan);
  * outside the pivots, that plan alone is rerun inside the call, on the general path at once -- its note becomes "alone: rerun after batch <b>:
  * <reason>" -- and the other slots keep their answers.  VDL_BATCH_WIDTH=k (k >= 2) caps the width of every batch, grouped or global.
  * vdl_plan_batch_code_bytes: the code size of the batch kernel that served the plan in the last vdl_run_batch / vdl_batch_jit_check,
- * 0 when none did. */
+ * 0 when none did.
+ *
+ * Join batches (opt-in: vdl_set_batch_joins(ctx, 1), or VDL_BATCH_JOINS=1 in the environment when the context opens; off, every plan
+ * whose scan has derived columns or a prelude runs alone as above, with the same notes).  With the switch on the ONE scan of a plan may
+ * have derived columns -- lookups through a join index, bits of a dimension bitmap or a semi-join set, LIKE tables, differences, row
+ * ids, conditions -- and a prelude; it is global, or grouped with vdl_set_batch_grouped on as well.  Wide sums stay excluded.  Such plans
+ * share a batch when, beside the same columns (the lookup targets' addresses and widths included) and the same generated code under
+ * run-time bounds, (a) their preludes build the same tables -- the same LIKE heap and pattern, the same dimension or semi-join scan with
+ * all its bounds, the same witness statements -- and (b) their conditions (IN lists, disjunctions, CASE WHEN tests) hold the same
+ * literals.  What differs between the plans of a join batch are the range bounds of table columns and of filtered derived columns that
+ * are no conditions.  The prelude runs ONCE per batch, through the first plan, by the code a plan alone runs; the kernel reads the fact
+ * columns once, looks a row up once while any plan still wants it, computes every condition once per row, and keeps per row the set of
+ * plans whose filters have held so far.  One prelude item is left out of (a): a dimension bitmap that a semi-join scan tests for the
+ * very row whose bit it sets, made of range filters on the scanned table that the plan's scan applies itself with the same bounds
+ * (TPC-H Q4's quarter): the batch leaves it open -- every row selected --, so plans for different quarters build one set and each
+ * plan's own filter drops the rest.  A plan with no partner says "no other plan of the call builds the same lookup tables" or "its
+ * conditions' literals differ from every other plan's".  A batch whose semi-join set cannot stand for the emitted `mod` (the indexed
+ * table has more rows than the modulus) sends EVERY member back alone on the general path: "alone: rerun after batch <b>: <reason>".
+ * A join batch is at most 8 plans wide within slots x (1 + aggregates) <= 32 (global) or the grouped rule above; only the eager tile form
+ * is batched, the name carries ",derived" and ",batch<K>,rtb>".  Under vdl_plan_set_profiling the first plan of a join batch that
+ * finalises also carries "timeInMicrosecondsForBatchedPrelude": the time of the batch's one prelude.  vdl_run_batch_sharded does not
+ * read the switch. */
 int  vdl_run_batch(vdl_ctx *ctx, vdl_plan *const *plans, int n);
 const char *vdl_plan_batch_note(const vdl_plan *plan);
 int  vdl_batch_jit_check(vdl_ctx *ctx, vdl_plan *const *plans, int n);
 int  vdl_set_batch_grouped(vdl_ctx *ctx, int on);
+int  vdl_set_batch_joins(vdl_ctx *ctx, int on);
 int64_t vdl_plan_batch_code_bytes(const vdl_plan *plan);
 
 int  vdl_n_outputs(const vdl_plan *plan);

@@ -74,6 +74,7 @@ def load():
         "vdl_plan_set_jit": (i32, [vp, i32]),
         "vdl_plan_set_jit_bounds": (i32, [vp, i32]),
         "vdl_jit_counters": (None, [P(i64), P(i64), P(i64)]),
+        "vdl_prelude_counters": (None, [P(i64)]),
         "vdl_plan_jit_note": (ctypes.c_char_p, [vp]),
         "vdl_plan_image_columns": (i32, [vp, P(ctypes.c_char_p)]),
         "vdl_plan_step_columns": (i32, [vp, P(ctypes.c_char_p)]),
@@ -86,6 +87,7 @@ def load():
         "vdl_plan_batch_note": (cp, [vp]),
         "vdl_plan_batch_code_bytes": (i64, [vp]),
         "vdl_set_batch_grouped": (i32, [vp, i32]),
+        "vdl_set_batch_joins": (i32, [vp, i32]),
         "vdl_n_outputs": (i32, [vp]),
         "vdl_output": (i32, [vp, i32, P(cp), P(cp), P(P(i64)), P(ctypes.c_size_t)]),
         "vdl_plan_set_device_outputs": (i32, [vp, i32]),
@@ -160,7 +162,7 @@ ABI_SYMBOLS = [
     "vdl_set_column_images", "vdl_encode_steps", "vdl_column_steps_info", "vdl_download_steps_image", "vdl_declare_steps_image", "vdl_set_step_images",
     "vdl_plan_step_columns", "vdl_declare_column_image", "vdl_set_lookup_images", "vdl_plan_lookup_columns",
     "vdl_parse", "vdl_plan_free", "vdl_plan_describe", "vdl_plan_is_fused", "vdl_plan_set_fusion",
-    "vdl_plan_set_profiling", "vdl_plan_set_jit", "vdl_plan_set_jit_bounds", "vdl_jit_counters", "vdl_plan_jit_note", "vdl_plan_jit_check", "vdl_plan_image_columns", "vdl_plan_set_trace", "vdl_n_traced", "vdl_traced", "vdl_run", "vdl_run_batch", "vdl_batch_jit_check", "vdl_plan_batch_note", "vdl_plan_batch_code_bytes", "vdl_set_batch_grouped", "vdl_n_outputs", "vdl_output", "vdl_plan_set_device_outputs", "vdl_output_device", "vdl_n_timings", "vdl_timing",
+    "vdl_plan_set_profiling", "vdl_plan_set_jit", "vdl_plan_set_jit_bounds", "vdl_jit_counters", "vdl_prelude_counters", "vdl_plan_jit_note", "vdl_plan_jit_check", "vdl_plan_image_columns", "vdl_plan_set_trace", "vdl_n_traced", "vdl_traced", "vdl_run", "vdl_run_batch", "vdl_batch_jit_check", "vdl_plan_batch_note", "vdl_plan_batch_code_bytes", "vdl_set_batch_grouped", "vdl_set_batch_joins", "vdl_n_outputs", "vdl_output", "vdl_plan_set_device_outputs", "vdl_output_device", "vdl_n_timings", "vdl_timing",
     "vdl_plan_set_order", "vdl_plan_order_note", "vdl_order_host", "vdl_plan_set_order_sharded", "vdl_order_merge_host",
     "vdl_build_collation", "vdl_collation_info", "vdl_plan_set_order_text", "vdl_collate_host", "vdl_collate_device",
     "vdl_plan_scan_stats", "vdl_plan_scan_traffic", "vdl_plan_partial_spec", "vdl_plan_sharded_route", "vdl_run_local", "vdl_finalize", "vdl_finalize_begin", "vdl_finalize_end", "vdl_plan_set_row_offset", "vdl_plan_set_sharded_table", "vdl_resolve_first", "vdl_exchange_spec", "vdl_exchange_begin", "vdl_exchange_pack",

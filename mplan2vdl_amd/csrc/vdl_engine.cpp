@@ -6,6 +6,7 @@
 //   * general : any other program runs statement by statement with one kernel per operator;
 //               RangeV/RangeC, Project, Shuffle and identity Gathers never touch memory.
 // This file runs things; how a planned scan and the catalog's columns become kernel arguments is vdl_bind.cpp.
+#include <atomic>
 #include <chrono>
 
 #include "vdl_genexec.h"
@@ -243,7 +244,11 @@ static hipFunction_t front_kernel(vdl_ctx *c, vdl_plan *p, const std::string &ro
 // that hold the dimension selections (filters on the dimension table, joins of dimensions with further dimensions) and
 // their validity bitmaps become the lookup tables of the fact scan; LIKE patterns are evaluated once per heap offset.
 // Part of the query: runs on every execution.  `wanted[k]`: item k is referred to by a scan that is about to run.
-void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) {
+// open (a join batch, batch_open_items): [k] = the dimension bitmap k is not built -- no table, every row of its table selected
+// (g_prelude_items: prelude tables built in this process so far -- LIKE tables, dimension bitmaps by scan or by witness, semi-join sets;
+// vdl_prelude_counters: what shows that a join batch builds its tables once and K plans alone K times)
+static std::atomic<int64_t> g_prelude_items{0};
+void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked, const std::vector<char> *open = nullptr) {
     const FusedPlan &F = p->fused;
     p->prelude_buf.assign(F.prelude.size(), nullptr);
     p->prelude_n.assign(F.prelude.size(), 0);
@@ -253,6 +258,9 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         if (wanted[k] && F.prelude[k].scan)
             for (const ScanColumn &sc : F.prelude[k].cols) if (sc.prelude >= 0) wanted[(size_t)sc.prelude] = 1;
     const bool scans = !getenv("VDL_NO_DIM_SCAN");
+    // (an open bitmap: no words -- a lookup without a table selects every row -- over the rows of its table)
+    for (size_t k = 0; open && k < F.prelude.size(); k++)
+        if (wanted[k] && (*open)[k]) p->prelude_n[k] = find_col(c, F.prelude[k].cols[0].name).n;
     for (size_t k = 0; k < F.prelude.size(); k++) {
         const PreludeItem &it = F.prelude[k];
         if (!wanted[k] || it.kind != PreludeItem::LIKE_LUT) continue;
@@ -265,17 +273,19 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         p->prelude_buf[k] = dev_alloc(c, sizeof(int64_t) * (size_t)std::max<int64_t>(heap.n, 1));
         p->prelude_n[k] = heap.n;
         HIP_CHECK(launch_like(offs, nullptr, heap.n, hs, nullptr, heap.n, pat, (int64_t *)p->prelude_buf[k]->p, c->stream));
+        g_prelude_items++;
     }
     std::vector<int> witnesses;
     for (size_t k = 0; k < F.prelude.size(); k++)
-        if (wanted[k] && F.prelude[k].kind == PreludeItem::DIM_BITMAP && !(scans && F.prelude[k].scan)) witnesses.push_back(F.prelude[k].witness);
+        if (wanted[k] && F.prelude[k].kind == PreludeItem::DIM_BITMAP && !(scans && F.prelude[k].scan) && !(open && (*open)[k])) witnesses.push_back(F.prelude[k].witness);
     if (!witnesses.empty()) {
         GenExec g(c, p);
         g.run_nodes(witnesses, nullptr);
         for (size_t k = 0; k < F.prelude.size(); k++) {
-            if (!wanted[k] || F.prelude[k].kind != PreludeItem::DIM_BITMAP || (scans && F.prelude[k].scan)) continue;
+            if (!wanted[k] || F.prelude[k].kind != PreludeItem::DIM_BITMAP || (scans && F.prelude[k].scan) || (open && (*open)[k])) continue;
             const DVec &v = g.vec[(size_t)F.prelude[k].witness];
             p->prelude_n[k] = v.n;
+            g_prelude_items++;
             if (v.kind == DVec::SPARSE) p->prelude_buf[k] = g.bitmap_of(v.sel);
             else p->prelude_buf[k] = g.densify(v).valid;                  // null: every dimension row holds a value
         }
@@ -290,9 +300,11 @@ void run_prelude_items(vdl_ctx *c, vdl_plan *p, const std::vector<char> &asked) 
         const PreludeItem &it = F.prelude[k];
         const bool semi = it.kind == PreludeItem::SEMI_BITMAP;
         if (!wanted[k] || !it.scan || !(semi || (scans && it.kind == PreludeItem::DIM_BITMAP))) continue;
+        if (open && (*open)[k]) continue;
         MScanCols cols;
         host_descs.push_back(std::make_shared<MScanDesc>());
         MScanDesc *d = host_descs.back().get();
+        g_prelude_items++;
         const int64_t n = bind_prelude_scan(c, p, k, cols, *d);
         patch_prelude(p, it.cols, cols, *d);
         if (semi) {
@@ -798,6 +810,7 @@ int vdl_open(vdl_ctx **out, int device) {
     int rc = guard(c, [&] {
         c->device = device;
         { const char *g = getenv("VDL_BATCH_GROUPED"); c->batch_grouped = g && *g && *g != '0'; }
+        { const char *g = getenv("VDL_BATCH_JOINS"); c->batch_joins = g && *g && *g != '0'; }
         { const char *g = getenv("VDL_LOOKUP_IMAGES"); c->lookup_images = g && *g && *g != '0'; }
         if (device >= 0) {
             int count = 0;
@@ -1237,6 +1250,7 @@ int vdl_plan_set_jit_bounds(vdl_plan *p, int at_run_time) {
     return VDL_OK;
 }
 void vdl_jit_counters(int64_t *compiled, int64_t *from_disk, int64_t *from_memory) { vdl::jit::counters(compiled, from_disk, from_memory); }
+void vdl_prelude_counters(int64_t *items) { if (items) *items = g_prelude_items.load(); }
 const char *vdl_plan_jit_note(const vdl_plan *p) { return p ? p->jit_note.c_str() : ""; }
 // "role: columns; role: columns" of the roles that have some, out of one of the three texts the plan keeps per role
 static int role_columns(const vdl_plan *p, const char **list, std::string vdl_plan::RoleColumns::*text, std::string &out) {
@@ -1531,7 +1545,8 @@ struct BatchGrouping {
     std::vector<std::string> alone;
     std::vector<std::vector<BatchMember *>> batches;
 };
-void batch_group(vdl_ctx *c, vdl_plan *const *plans, int n, bool grouped_on, BatchGrouping &G) {
+// (joins_on: vdl_set_batch_joins -- members also agree in their prelude's tables and their conditions' literals)
+void batch_group(vdl_ctx *c, vdl_plan *const *plans, int n, bool grouped_on, bool joins_on, BatchGrouping &G) {
     std::vector<BatchMember> &members = G.members;
     members.reserve((size_t)n);
     std::vector<std::string> &alone = G.alone;
@@ -1540,7 +1555,7 @@ void batch_group(vdl_ctx *c, vdl_plan *const *plans, int n, bool grouped_on, Bat
         vdl_plan *p = plans[i];
         p->batch_note.clear();
         p->batch_code_bytes = 0;
-        alone[(size_t)i] = batch_alone_reason(p, grouped_on);
+        alone[(size_t)i] = batch_alone_reason(p, grouped_on, joins_on);
         if (!alone[(size_t)i].empty()) continue;
         BatchMember m;
         m.index = i;
@@ -1552,15 +1567,25 @@ void batch_group(vdl_ctx *c, vdl_plan *const *plans, int n, bool grouped_on, Bat
     for (BatchMember &m : members) {
         bool placed = false;
         for (auto &g : groups)
-            if (g[0]->cols_key == m.cols_key && g[0]->shape_key == m.shape_key) { g.push_back(&m); placed = true; break; }
+            if (g[0]->cols_key == m.cols_key && g[0]->shape_key == m.shape_key && g[0]->prelude_key == m.prelude_key && g[0]->form_key == m.form_key) { g.push_back(&m); placed = true; break; }
         if (!placed) groups.push_back({&m});
     }
     std::vector<std::vector<BatchMember *>> &batches = G.batches;
     for (auto &g : groups) {
         if (g.size() == 1) {
-            bool same_cols = false;
-            for (const BatchMember &o : members) same_cols |= &o != g[0] && o.cols_key == g[0]->cols_key;
-            alone[(size_t)g[0]->index] = same_cols ? "its filter shapes differ from every other plan's" : members.size() > 1 ? "no other plan scans the same columns" : "no other plan of the call can share a scan";
+            // (a join scan: a plan of the same columns and code may still build other lookup tables or hold other literals in its conditions)
+            bool same_cols = false, same_shape = false, same_tables = false;
+            for (const BatchMember &o : members) {
+                if (&o == g[0] || o.cols_key != g[0]->cols_key) continue;
+                same_cols = true;
+                if (o.shape_key != g[0]->shape_key) continue;
+                same_shape = true;
+                same_tables |= o.prelude_key == g[0]->prelude_key;
+            }
+            alone[(size_t)g[0]->index] = same_tables  ? "its conditions' literals differ from every other plan's"
+                                         : same_shape ? "no other plan of the call builds the same lookup tables"
+                                         : same_cols  ? "its filter shapes differ from every other plan's"
+                                         : members.size() > 1 ? "no other plan scans the same columns" : "no other plan of the call can share a scan";
             continue;
         }
         const size_t cap = g[0]->grouped ? (size_t)batch_group_cap(*g[0]->desc, g[0]->replicas_alone) : (size_t)batch_cap_asked(g[0]->desc->nagg);
@@ -1575,7 +1600,8 @@ void batch_group(vdl_ctx *c, vdl_plan *const *plans, int n, bool grouped_on, Bat
 }
 struct BatchEvents {
     hipEvent_t a = nullptr, b = nullptr;
-    ~BatchEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    hipEvent_t p0 = nullptr, p1 = nullptr;     // a join batch under profiling: around its one prelude
+    ~BatchEvents() { for (hipEvent_t e : {a, b, p0, p1}) if (e) (void)hipEventDestroy(e); }
 };
 // The scan half: batch b of the grouping as ONE scan, slot q's words left at outs[ms[q]->index] -- the caller's pointers (a sharded
 // batch: into its send block) or, with outs null, the plans' own word buffers.  Every plan of the batch is given the word layout a
@@ -1584,6 +1610,24 @@ std::string batch_scan_one(vdl_ctx *c, const std::vector<BatchMember *> &ms, siz
     const int K = (int)ms.size();
     bool tune = true, profiling = false;
     int64_t *outs[kMaxBatch] = {};
+    if (!check_only && !ms[0]->p->fused.prelude.empty()) {
+        // a join batch: the members' preludes build the same tables (batch_group), so the first member's builds them ONCE -- the LIKE
+        // tables, the dimension bitmaps, the semi-join set, by the code and the kernels a plan alone runs -- and every member's binding
+        // is pointed at them.  (NeedGeneralPath: a semi-join set the fused plan cannot stand for; run_batches reruns every member alone)
+        vdl_plan *first = ms[0]->p;
+        std::vector<char> wanted(first->fused.prelude.size(), 0);
+        for (const ScanColumn &sc : scan_columns(first, 0)) if (sc.prelude >= 0) wanted[(size_t)sc.prelude] = 1;
+        const std::vector<char> open = batch_open_items(first);
+        bool timed = false;
+        for (BatchMember *m : ms) timed = timed || m->p->profiling;
+        if (timed && !outs_given) { HIP_CHECK(hipEventCreate(&ev.p0)); HIP_CHECK(hipEventCreate(&ev.p1)); HIP_CHECK(hipEventRecord(ev.p0, c->stream)); }
+        run_prelude_items(c, first, wanted, &open);
+        if (ev.p1) HIP_CHECK(hipEventRecord(ev.p1, c->stream));
+        for (BatchMember *m : ms) {
+            if (m->p != first) { m->p->prelude_buf = first->prelude_buf; m->p->prelude_n = first->prelude_n; m->p->prelude_rows = first->prelude_rows; }
+            patch_prelude(m->p, scan_columns(m->p, 0), m->cols, *m->desc);
+        }
+    }
     for (int q = 0; q < K; q++) {
         vdl_plan *p = ms[(size_t)q]->p;
         tune = tune && p->jit_tune;
@@ -1630,20 +1674,38 @@ std::string batch_scan_one(vdl_ctx *c, const std::vector<BatchMember *> &ms, siz
 // check_only (vdl_batch_jit_check): the grouping, the builds and the notes, nothing loaded or run.
 void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
     BatchGrouping G;
-    batch_group(c, plans, n, c->batch_grouped, G);
+    batch_group(c, plans, n, c->batch_grouped, c->batch_joins, G);
     std::vector<std::string> &alone = G.alone;
     const std::vector<std::vector<BatchMember *>> &batches = G.batches;
     for (size_t b = 0; b < batches.size(); b++) {
         const std::vector<BatchMember *> &ms = batches[b];
         const int K = (int)ms.size();
         BatchEvents ev;
-        const std::string name = batch_scan_one(c, ms, b, check_only, nullptr, ev);
+        std::string name;
+        try {
+            name = batch_scan_one(c, ms, b, check_only, nullptr, ev);
+        } catch (const NeedGeneralPath &e) {
+            // the shared prelude says that the fused plan does not hold for this data (a semi-join set taken mod N over a longer table): it
+            // says so for every member -- each is rerun alone on the general path at once, as a plan whose rows leave the pivots is below
+            const std::string why = e.what();
+            for (int q = 0; q < K; q++) {
+                vdl_plan *p = ms[(size_t)q]->p;
+                p->batch_words = false;
+                const int rc = run_plan(c, p, &why);
+                if (rc != VDL_OK) throw Error(rc, "plan " + std::to_string(ms[(size_t)q]->index) + ": " + c->err);
+                p->batch_note = "alone: rerun after batch " + std::to_string(b) + ": " + why;
+            }
+            continue;
+        }
         if (check_only) continue;
         for (int q = 0; q < K; q++) finalize_begin(c, ms[(size_t)q]->p, (const int64_t *)ms[(size_t)q]->p->words->p, 0);
         float ms_scan = 0;
         // (read once, whichever slots finalise: a slot that is rerun alone must not leave its partners a time of 0)
         if (ev.a) { HIP_CHECK(hipEventSynchronize(ev.b)); HIP_CHECK(hipEventElapsedTime(&ms_scan, ev.a, ev.b)); }
+        float ms_prelude = 0;
+        if (ev.p1) { HIP_CHECK(hipEventSynchronize(ev.p1)); HIP_CHECK(hipEventElapsedTime(&ms_prelude, ev.p0, ev.p1)); }
         std::vector<std::pair<int, std::string>> rerun;             // slots whose rows carry keys outside the pivots, with finalize_end's words
+        bool prelude_said = false;
         for (int q = 0; q < K; q++) {
             vdl_plan *p = ms[(size_t)q]->p;
             try {
@@ -1660,6 +1722,8 @@ void run_batches(vdl_ctx *c, vdl_plan *const *plans, int n, bool check_only) {
             }
             // the whole batch kernel's time, under a label of its own: never a per-query figure
             if (ev.a && p->profiling) p->timings.push_back({"timeInMicrosecondsForBatchedScan_" + name, (double)ms_scan * 1e3});
+            // (a join batch: its ONE prelude -- the LIKE tables, bitmaps and sets every slot reads --, on the first slot that finalised)
+            if (ev.p1 && p->profiling && !prelude_said) { p->timings.push_back({"timeInMicrosecondsForBatchedPrelude", (double)ms_prelude * 1e3}); prelude_said = true; }
         }
         // (after every slot's finalisation: the others keep their answers and notes.  The batch has shown that the plan's fused scan
         // meets keys outside its pivots: the rerun takes the general path at once, as vdl_run does after its own fused pass says so)
@@ -1702,7 +1766,7 @@ int batch_args_check(vdl_ctx *c, vdl_plan *const *plans, int n, const char *who)
 void batch_local_scans(vdl_ctx *c, vdl_plan *const *plans, int n, int64_t *const *outs, std::vector<BatchLocal> &res) {
     res.assign((size_t)n, BatchLocal{});
     BatchGrouping G;
-    batch_group(c, plans, n, false, G);
+    batch_group(c, plans, n, false, false, G);
     for (size_t b = 0; b < G.batches.size(); b++) {
         const std::vector<BatchMember *> &ms = G.batches[b];
         int rc = VDL_OK;
@@ -1744,6 +1808,11 @@ int64_t vdl_plan_batch_code_bytes(const vdl_plan *p) { return p ? (int64_t)p->ba
 int vdl_set_batch_grouped(vdl_ctx *c, int on) {
     if (!c) return VDL_ERR_ARG;
     c->batch_grouped = on != 0;
+    return VDL_OK;
+}
+int vdl_set_batch_joins(vdl_ctx *c, int on) {
+    if (!c) return VDL_ERR_ARG;
+    c->batch_joins = on != 0;
     return VDL_OK;
 }
 

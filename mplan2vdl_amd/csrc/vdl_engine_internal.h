@@ -229,6 +229,7 @@ struct vdl_ctx {
     // batched scans (vdl_run_batch) by shape, columns and width: the loaded kernel with its grid, the descriptors and partials on the device
     std::map<std::string, std::shared_ptr<BatchEntry>> batches;
     bool batch_grouped = false;        // vdl_run_batch also batches plans whose one scan is grouped (vdl_set_batch_grouped, VDL_BATCH_GROUPED=1)
+    bool batch_joins = false;          // ... and plans whose one scan has derived columns and a prelude (vdl_set_batch_joins, VDL_BATCH_JOINS=1)
     std::string err;
     // a few words of PINNED host memory for the round trips of the executors (survivor counts, sortedness verdicts): a copy
     // into pageable memory is staged by the runtime and cost 20-30 us of idle GPU each (Q3 at SF10: three of them per query)

@@ -422,7 +422,8 @@ std::string scan_source(Kind kind, const MsArgs &C, const MScanDesc &D, const Sh
         o << "extern \"C\" __global__ __launch_bounds__(256) void " << entry_name(kind, C, D, sh) << "(const vdl::MsArgs Cr, const vdl::MsBatch B) {\n"
              "    constexpr vdl::MsArgs C = vdl::jit_args();\n"
              "    constexpr vdl::MScanDesc D = vdl::jit_desc();\n"
-             "    vdl::mscan_body<" << sh.nc << ", " << sh.u << ", " << b << ", " << b << ", " << (sh.grouped ? "true" : "false") << ", false, false>(C, Cr, D, *B.d[0], B);\n}\n";
+             "    vdl::mscan_body<" << sh.nc << ", " << sh.u << ", " << b << ", " << b << ", " << (sh.grouped ? "true" : "false") << ", " << (sh.der ? "true" : "false")
+          << ", false>(C, Cr, D, *B.d[0], B);\n}\n";
     else if (kind == MSCAN)
         o << "extern \"C\" __global__ __launch_bounds__(256) void " << entry_name(kind, C, D, sh) << "(const vdl::MsArgs Cr, const vdl::MScanDesc *__restrict__ Dp) {\n"
              "    constexpr vdl::MsArgs C = vdl::jit_args();\n"

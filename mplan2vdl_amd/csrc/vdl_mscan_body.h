@@ -352,12 +352,12 @@ __device__ __forceinline__ void eval_pass(const MsArgs &C, const MScanDesc &D, c
 // a packed column are the packed image's, 32 unsigned bits, and those of a column or byte image of 1 or 2 bytes are handed in clamped
 // to one step outside its domain (vdl_specialise.cpp batch_launch), 32 signed bits, for every slot: they have one shape.
 template <int NC, int RW>
-__device__ __forceinline__ void eval_pass_narrow(const MsArgs &C, const MScanDesc &D, const MScanDesc &Dr, const int64_t (&v)[NC][RW], bool (&pass)[RW]) {
+__device__ __forceinline__ void eval_pass_narrow(const MsArgs &C, const MScanDesc &D, const MScanDesc &Dr, const int64_t (&v)[NC][RW], bool (&pass)[RW], uint32_t of = ~0u) {
 #pragma unroll
     for (int r = 0; r < RW; r++) pass[r] = true;
 #pragma unroll
     for (int c = 0; c < NC; c++) {
-        if ((C.filtered >> c) & 1u) {                      // wave-uniform (bits only below ncol)
+        if (((C.filtered & of) >> c) & 1u) {               // wave-uniform (bits only below ncol; `of`: the table columns of a join batch)
             int64_t lo, hi;
             range_bounds(D.flo[c], D.fhi[c], Dr.flo[c], Dr.fhi[c], lo, hi);
             if ((C.packed >> c) & 1u) {
@@ -557,6 +557,156 @@ __device__ __forceinline__ void derive(const MsArgs &C, const MsArgs &Cr, const 
     }
 }
 
+#ifdef VDL_BATCH
+// A filtered derived column of a join batch (vdl_set_batch_joins): slot q keeps its bit of m[r] while the value lies inside ITS bounds
+// (B.d[q]: scalar loads), in 64 bits -- a looked-up value, a difference, a bit or a condition has no narrow domain.
+template <int RW, int KB>
+__device__ __forceinline__ void batch_fold(const MScanDesc &D, const MsBatch &B, int c, const int64_t (&x)[RW], int (&m)[RW]) {
+#pragma unroll
+    for (int q = 0; q < KB; q++) {
+        int64_t lo, hi;
+        range_bounds(D.flo[c], D.fhi[c], B.d[q]->flo[c], B.d[q]->fhi[c], lo, hi);
+#pragma unroll
+        for (int r = 0; r < RW; r++) m[r] &= ~((int)!((x[r] >= lo) & (x[r] <= hi)) << q);
+    }
+}
+// derive() for the K plans of a join batch.  What derive() keeps in `alive` is two things here: valid[r] -- the row is inside the table
+// and every lookup so far was in range, which no slot's bounds decide -- and m[r], bit q set while slot q's filters have all held (on
+// entry: the filters on table columns).  A row is looked up while it is valid and SOME slot still wants it; every value is computed once;
+// a filter on a derived column narrows each slot's bit at once, so the lookups after it go out for the rows some slot still wants.
+// Lookup tables, their sizes and the conditions' tests are the same for every slot (the host batches only such plans) and are read
+// from slot 0's descriptor (Dr).
+template <int NC, int RW, int KB>
+__device__ __forceinline__ void derive_batch(const MsArgs &C, const MsArgs &Cr, const MScanDesc &D, const MScanDesc &Dr, const MsBatch &B, int64_t (&v)[NC][RW],
+                                             bool (&valid)[RW], int (&m)[RW], uint32_t only, const int64_t (&rowid)[RW]) {
+    if ((only & 1u) && D.dkind[0] == VC_ROWID) {
+#pragma unroll
+        for (int r = 0; r < RW; r++) v[0][r] = rowid[r] - Cr.rowid_base;
+    }
+#pragma unroll
+    for (int c = 1; c < NC; c++) {
+        if ((only >> c) & 1u) {                            // wave-uniform
+            const int kind = D.dkind[c], a = D.dsrc[c], b = D.dsrc2[c];
+            if (kind == VC_ROWID) {
+#pragma unroll
+                for (int r = 0; r < RW; r++) v[c][r] = rowid[r] - Cr.rowid_base;
+            } else if (kind == VC_FORM) {
+                // (the tests and the program as in derive(); a slice no slot wants any row of is skipped)
+                const int L = D.dtests[c];
+                bool live[RW];
+                uint64_t bits[RW];
+                uint32_t stk[RW];
+#pragma unroll
+                for (int r = 0; r < RW; r++) { live[r] = __ballot(valid[r] & (m[r] != 0)) != 0; bits[r] = 0; stk[r] = 0; }
+                VDL_SPEC_UNROLL
+                for (int j = 0; j < L; j++) {
+                    const int col = D.form[a + j].col;
+                    int64_t lo, hi;
+                    range_bounds(D.form[a + j].lo, D.form[a + j].hi, Dr.form[a + j].lo, Dr.form[a + j].hi, lo, hi);
+#pragma unroll
+                    for (int k = 0; k < NC; k++) {
+                        if (k < c && k == col) {           // scalar branch: one body runs
+#pragma unroll
+                            for (int r = 0; r < RW; r++)
+                                if (live[r]) bits[r] |= (uint64_t)((v[k][r] >= lo) & (v[k][r] <= hi)) << j;
+                        }
+                    }
+                }
+                VDL_SPEC_UNROLL
+                for (int s = a + L; s < a + b; s++) {
+                    const int op = D.form[s].op;
+                    if (op == FormStep::REF) {
+                        const int j = D.form[s].col;
+#pragma unroll
+                        for (int r = 0; r < RW; r++) stk[r] = (stk[r] << 1) | (uint32_t)((bits[r] >> j) & 1ull);
+                    } else if (op == FormStep::AND) {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) stk[r] = ((stk[r] >> 1) & ~1u) | (stk[r] & (stk[r] >> 1) & 1u);
+                    } else if (op == FormStep::OR) {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) stk[r] = (stk[r] >> 1) | (stk[r] & 1u);
+                    } else if (op == FormStep::NOT) {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) stk[r] ^= 1u;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) stk[r] = (stk[r] << 1) | (op == FormStep::TRUE_ ? 1u : 0u);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < RW; r++) v[c][r] = (int64_t)(stk[r] & 1u);
+            } else {
+            int64_t x[RW], y[RW];
+#pragma unroll
+            for (int r = 0; r < RW; r++) { x[r] = 0; y[r] = 0; }
+#pragma unroll
+            for (int k = 0; k < NC; k++) {                 // register files are not indexable: select the source column by comparison
+                if (k < c && k == a) {
+#pragma unroll
+                    for (int r = 0; r < RW; r++) x[r] = v[k][r];
+                }
+                if (k < c && k == b) {
+#pragma unroll
+                    for (int r = 0; r < RW; r++) y[r] = v[k][r];
+                }
+            }
+            if (VDL_IS_DIFF(kind)) {
+#pragma unroll
+                for (int r = 0; r < RW; r++) v[c][r] = (int64_t)((uint64_t)x[r] - (uint64_t)y[r]);
+#if VDL_SAT_DIFF
+                if (kind == VC_SUBS) {
+#pragma unroll
+                    for (int r = 0; r < RW; r++) if (((x[r] ^ y[r]) & (x[r] ^ v[c][r])) < 0) v[c][r] = x[r] < 0 ? INT64_MIN : INT64_MAX;
+                }
+#endif
+            } else {
+            const int64_t n = Dr.dn[c];
+            const char *t = (const char *)Cr.ptr[c];
+            const int w = C.width(c);
+            bool inside[RW], in[RW];
+            // a memory request only for a row that is valid, that some slot still wants and whose index lies inside the table
+#pragma unroll
+            for (int r = 0; r < RW; r++) { inside[r] = (x[r] >= 0) & (x[r] < n); in[r] = valid[r] & (m[r] != 0) & inside[r]; }
+            if (kind == VC_GATHER) {
+                int64_t q[RW];
+#pragma unroll
+                for (int r = 0; r < RW; r++) { q[r] = 0; if (in[r]) q[r] = load_scalar(t, w, x[r]); }
+#if VDL_LOOKUP_DECODE
+                if ((C.decode >> c) & 1u) {                 // wave-uniform
+#pragma unroll
+                    for (int r = 0; r < RW; r++) if (in[r]) q[r] = img_decode(q[r], D.ibase[c], D.iscale[c]);
+                }
+#endif
+#pragma unroll
+                for (int r = 0; r < RW; r++) { v[c][r] = q[r]; valid[r] = valid[r] & inside[r]; }
+            } else if (kind == VC_BITS) {
+                uint64_t word[RW];
+#pragma unroll
+                for (int r = 0; r < RW; r++) word[r] = ~0ull;                      // no bitmap: every dimension row is selected
+                if (t && n > 0) {
+#pragma unroll
+                    for (int r = 0; r < RW; r++) word[r] = ((const uint64_t *)t)[(in[r] ? x[r] : 0) >> 6];
+                }
+#pragma unroll
+                for (int r = 0; r < RW; r++) { v[c][r] = in[r] ? (int64_t)((word[r] >> (x[r] & 63)) & 1ull) : 0; valid[r] = valid[r] & inside[r]; }
+            } else if (kind == VC_LUT) {                    // outside the table: 0, not EPS
+#pragma unroll
+                for (int r = 0; r < RW; r++) { v[c][r] = 0; if (in[r]) v[c][r] = ((const int64_t *)t)[x[r]]; }
+            } else {                                        // VC_INRANGE
+#pragma unroll
+                for (int r = 0; r < RW; r++) { v[c][r] = 1; valid[r] = valid[r] & inside[r]; }
+            }
+            }
+            }
+            // a filter on the column takes effect at once, slot by slot: the lookups of the columns after it go out for the rows some slot
+            // still wants.  (ONE site for every kind: with a fold per kind the column loop outgrew what the compiler unrolls at four slots
+            // and more, and the row's columns went to scratch memory)
+            if ((C.filtered >> c) & 1u) batch_fold<RW, KB>(D, B, c, v[c], m);
+        }
+    }
+}
+#endif
+
 // term of one aggregate for the lane's rows: product of affine column factors (a + s*col), a constant,
 // or the row id (AGG_FIRST).  Everything read from `d` is wave-uniform (scalar loads).
 template <int NC, int RW>
@@ -714,7 +864,12 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
     // computed once; the filters and the accumulation run once per slot, against that slot's descriptor (B.d[q]: scalar loads), into
     // that slot's own count and accumulators -- VDL_BATCH x (1 + VDL_BATCH_NAGG) 64-bit values per lane, in registers (the host
     // caps the product at kMaxBatchWords), not in LDS lane slots: nothing is launched with dynamic LDS.
-    static_assert(!DER && !STAGED, "batched scans are aggregate scans over table columns that read nothing late");
+    // A JOIN batch (DER; vdl_set_batch_joins): the eager tile form of a scan with derived columns -- derive_batch() looks a row up once if
+    // any slot still wants it and leaves every row's set of slots, which the accumulation below then reads in place of the filters.
+    static_assert(!STAGED, "batched scans read nothing late");
+#ifdef VDL_PACKED
+    static_assert(!DER, "a join batch has the eager tile form alone");
+#endif
     static_assert(GROUPED ? VDL_BATCH >= 2 && VDL_BATCH <= kMaxBatchGrouped
                           : VDL_BATCH >= 2 && VDL_BATCH <= kMaxBatch && VDL_BATCH * (1 + VDL_BATCH_NAGG) <= kMaxBatchWords, "the slots' accumulators fit their registers");
     constexpr int KB = VDL_BATCH, NA = VDL_BATCH_NAGG, NA1 = NA > 0 ? NA : 1;
@@ -798,12 +953,33 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
         // (the stages arrive as generated straight-line code -- VDL_STAGED_PRE / _POST, vdl_jit.cpp: written as loops over
         // columns and stages with the stage numbers read from C, the compiler no longer folded the descriptor: 235 KB of code)
 #ifdef VDL_BATCH
+        // a join batch: the slots that want a row -- the filters on table columns per slot, narrowed by derive_batch(); 0 for a row that is
+        // past the table's end or whose lookup fell outside its table (EPS for every slot)
+        int want[RW];
+        if constexpr (DER) {
+#pragma unroll
+            for (int r = 0; r < RW; r++) want[r] = 0;
+#pragma unroll
+            for (int q = 0; q < KB; q++) {
+                bool pq[RW];
+                eval_pass_narrow<NC, RW>(C, D, *B.d[q], v, pq, ~C.derived);
+#pragma unroll
+                for (int r = 0; r < RW; r++) want[r] |= (int)pq[r] << q;
+            }
+            derive_batch<NC, RW, KB>(C, Cr, D, Dr, B, v, alive, want, C.derived, rowid);
+#pragma unroll
+            for (int r = 0; r < RW; r++) want[r] = alive[r] ? want[r] : 0;
+        }
         if (GROUPED) {
             int64_t acc[RW];
             group_key<NC, RW>(D, v, acc);
             int m[RW], off[RW];
 #pragma unroll
             for (int r = 0; r < RW; r++) m[r] = 0;
+            if constexpr (DER) {
+#pragma unroll
+                for (int r = 0; r < RW; r++) m[r] = want[r];
+            } else
 #pragma unroll
             for (int q = 0; q < KB; q++) {
                 bool pq[RW];
@@ -839,7 +1015,42 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
                     for (int r = 0; r < RW; r++) atomicMin((long long *)&mytab[off[r] + 1 + j], (long long)t[r]);
                 }
             }
-            (void)rows_left; (void)tile0; (void)tile_rows; (void)staged; (void)alive; (void)pass;
+            (void)rows_left; (void)tile0; (void)tile_rows; (void)staged; (void)alive; (void)pass; (void)want;
+            return;
+        } else if constexpr (DER) {
+            // the slots' counts (the wave's, as below), then aggregate by aggregate -- the loop over the descriptor's own count, as the
+            // unbatched form writes it: a join scan's descriptor did not fold with the terms kept side by side (NA x RW values) -- the
+            // term once, and every slot's rows of it into that slot's accumulator
+#pragma unroll
+            for (int q = 0; q < KB; q++) {
+                int here = 0;
+#pragma unroll
+                for (int r = 0; r < RW; r++) here += __popcll(__ballot((want[r] >> q) & 1));
+                bcnt[q] += here;
+            }
+            VDL_SPEC_UNROLL
+            for (int j = 0; j < nagg; j++) {
+                const int rk = rk_of(D.agg[j].kind);
+                int64_t t[RW];
+                eval_term<NC, RW>(D.agg[j], v, rowid, t);
+#pragma unroll
+                for (int q = 0; q < KB; q++) {
+                    int64_t s = r_identity(rk);
+                    if (rk == R_SUM) {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) s = (int64_t)((uint64_t)s + (uint64_t)(((want[r] >> q) & 1) ? t[r] : 0));
+                    } else if (rk == R_MIN) {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) s = (((want[r] >> q) & 1) && t[r] < s) ? t[r] : s;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < RW; r++) s = (((want[r] >> q) & 1) && t[r] > s) ? t[r] : s;
+                    }
+#pragma unroll
+                    for (int k = 0; k < NA; k++) if (k == j) bacc[q][k] = r_combine(rk, bacc[q][k], s);
+                }
+            }
+            (void)rows_left; (void)tile0; (void)tile_rows; (void)staged;
             return;
         } else {
             int64_t t[NA1][RW];
@@ -875,7 +1086,7 @@ __device__ __forceinline__ void mscan_body(const MsArgs &C, const MsArgs &Cr, co
                     bacc[q][j] = r_combine(rk, bacc[q][j], s);
                 }
             }
-            (void)rows_left; (void)tile0; (void)tile_rows; (void)staged;
+            (void)rows_left; (void)tile0; (void)tile_rows; (void)staged; (void)want;
             return;
         }
 #endif

@@ -503,8 +503,9 @@ void jit_check_scans(vdl_ctx *c, vdl_plan *p) {
 // Which plans share a scan is decided here, next to bind_form: the conditions are the packed form's (one global aggregate scan over
 // table columns) plus "the same columns" and "the same generated code under run-time bounds".  With vdl_set_batch_grouped a plan
 // whose one scan is a grouped scan over table columns shares a grouped batch by the same rules; a batch never mixes the two kinds
-// (their shape keys differ).
-std::string batch_alone_reason(const vdl_plan *p, bool grouped_on) {
+// (their shape keys differ).  With vdl_set_batch_joins the one scan may have derived columns and a prelude: plans then share a batch when,
+// beside the above, their preludes build the same tables (batch_prelude_key) and their conditions hold the same literals (batch_form_key).
+std::string batch_alone_reason(const vdl_plan *p, bool grouped_on, bool joins_on) {
     if (p->wide) return "wide sums are not batched";
     if (!p->use_fusion || !p->fused.ok) return "the plan is not fused";
     if (!p->use_jit) return "specialisation is off";
@@ -512,9 +513,9 @@ std::string batch_alone_reason(const vdl_plan *p, bool grouped_on) {
     if (!F.gscans.empty() && !grouped_on) return "grouped scans are not batched";
     const size_t nscans = F.scans.size() + F.gscans.size();
     if (nscans != 1) return "the plan has " + std::to_string(nscans) + " scans, a batch shares exactly one";
-    if (!F.prelude.empty()) return "scans with lookup tables or semi-join sets are not batched";
+    if (!F.prelude.empty() && !joins_on) return "scans with lookup tables or semi-join sets are not batched";
     for (const ScanColumn &sc : scan_columns(p, 0))
-        if (sc.kind != VC_DIRECT) return "scans with derived columns are not batched";
+        if (sc.kind != VC_DIRECT && !joins_on) return "scans with derived columns are not batched";
     if (F.gscans.empty() ? F.scans[0].never : F.gscans[0].never) return "its filters can hold for no row: there is nothing to scan";
     return "";
 }
@@ -525,6 +526,109 @@ static int batch_width_asked() {
     return w && atoi(w) >= 2 ? atoi(w) : kMaxBatch;
 }
 int batch_cap_asked(int nagg) { return std::min(batch_cap(nagg), batch_width_asked()); }
+// (a join batch has the same caps: a join scan keeps up to 12 columns per row in registers beside the slots' accumulators, and the units
+// of Q14, Q19, Q12 and Q4 at every width need no more scratch memory than the scan's own unit -- DESIGN.md section 5.12,
+// profiles/r26/join_batch_resources.txt; nothing reads a unit's scratch size when it is built)
+
+// ---- what a join batch's members must have in common beside columns and shape ----
+static void column_text(std::ostringstream &o, const ScanColumn &sc) {
+    o << "{" << sc.name << "," << sc.lo << "," << sc.hi << "," << sc.kind << "," << sc.idx << "," << sc.idx2 << "," << sc.prelude << "," << (sc.order_diff ? 1 : 0);
+    for (const FormStep &f : sc.form) o << "," << f.op << "/" << f.col << "/" << f.lo << "/" << f.hi;
+    o << "}";
+}
+// the statements a witness depends on, in text order and renumbered from 0: two programs whose dimension sides read alike give one text
+static void witness_text(std::ostringstream &o, const Program &P, int witness) {
+    std::vector<char> in(P.nodes.size(), 0);
+    std::vector<int> todo{witness};
+    auto known = [&](int id) { return id > 0 && (size_t)id < P.nodes.size() && P.nodes[(size_t)id].id == id; };
+    while (!todo.empty()) {
+        const int id = todo.back();
+        todo.pop_back();
+        if (!known(id) || in[(size_t)id]) continue;
+        in[(size_t)id] = 1;
+        const Node &n = P.at(id);
+        for (int x : {n.a, n.b, n.c}) todo.push_back(x);
+    }
+    std::map<int, int> number;
+    for (int id : P.order) if (known(id) && in[(size_t)id]) { const int k = (int)number.size(); number[id] = k; }
+    auto num = [&](int id) { const auto it = number.find(id); return it == number.end() ? -1 : it->second; };
+    for (int id : P.order) {
+        if (!known(id) || !in[(size_t)id]) continue;
+        const Node &n = P.at(id);
+        o << "(" << num(id) << ":" << (int)n.op << "," << n.bin << "," << num(n.a) << "," << num(n.b) << "," << num(n.c) << "," << n.imm0 << "," << n.imm1 << "," << n.imm2 << ","
+          << n.column << "," << n.pattern << "," << n.field << ")";
+    }
+}
+// Prelude items a join batch leaves OPEN (every row selected, nothing scanned): the dimension bitmap a semi-join scan tests for the
+// very row whose bit it is about to set, when that bitmap is a conjunction of range filters on columns of the plan's own scanned
+// table that the plan's scan applies itself, with the same bounds (TPC-H Q4: the quarter filters orders, and the set of orders with a
+// late lineitem is built from the lineitems of that quarter's orders).  The set then holds more rows of that table, and the scan's
+// own filters drop exactly those: the answer is the same, and the set no longer depends on the bounds that differ between the members.
+std::vector<char> batch_open_items(const vdl_plan *p) {
+    const FusedPlan &F = p->fused;
+    std::vector<char> open(F.prelude.size(), 0);
+    const std::vector<ScanColumn> &sc = scan_columns(p, 0);
+    const std::string &table = F.gscans.empty() ? F.scans[0].table : F.gscans[0].table;
+    for (const ScanColumn &user : sc) {
+        if (user.kind != VC_BITS || user.prelude < 0 || F.prelude[(size_t)user.prelude].kind != PreludeItem::SEMI_BITMAP) continue;
+        if (user.idx < 0 || sc[(size_t)user.idx].kind != VC_ROWID) continue;                  // (the bit of the row's own id)
+        const PreludeItem &semi = F.prelude[(size_t)user.prelude];
+        if (!semi.scan || semi.bits_of.substr(0, semi.bits_of.find('.')) != table) continue;
+        for (const ScanColumn &b : semi.cols) {
+            if (b.kind != VC_BITS || b.prelude < 0 || b.idx != semi.index_col || b.lo != 1 || b.hi != 1) continue;
+            const PreludeItem &dim = F.prelude[(size_t)b.prelude];
+            if (dim.kind != PreludeItem::DIM_BITMAP || !dim.scan || dim.never || dim.table != table) continue;
+            bool applied = !dim.cols.empty();
+            for (const ScanColumn &d : dim.cols) {
+                bool found = false;
+                for (const ScanColumn &own : sc) found |= own.kind == VC_DIRECT && d.kind == VC_DIRECT && own.name == d.name && own.lo == d.lo && own.hi == d.hi;
+                applied = applied && found;
+            }
+            // (no other user of the bitmap: every reference to it is this one)
+            int users = 0;
+            for (const ScanColumn &o : sc) users += o.prelude == b.prelude;
+            for (const PreludeItem &it : F.prelude) for (const ScanColumn &o : it.cols) users += o.prelude == b.prelude;
+            if (applied && users == 1) open[(size_t)b.prelude] = 1;
+        }
+    }
+    return open;
+}
+// The canonical text of every prelude item the plan's one scan refers to -- transitively: a dimension scan looks up earlier items --,
+// each under its index: equal text means the items build equal tables, and a scan column's `prelude` names the same item in both plans
+static std::string batch_prelude_key(const vdl_plan *p) {
+    const FusedPlan &F = p->fused;
+    const std::vector<char> open = batch_open_items(p);
+    std::vector<char> wanted(F.prelude.size(), 0);
+    for (const ScanColumn &sc : scan_columns(p, 0)) if (sc.prelude >= 0) wanted[(size_t)sc.prelude] = 1;
+    for (size_t k = F.prelude.size(); k-- > 0;)
+        if (wanted[k] && F.prelude[k].scan)
+            for (const ScanColumn &sc : F.prelude[k].cols) if (sc.prelude >= 0) wanted[(size_t)sc.prelude] = 1;
+    std::ostringstream o;
+    for (size_t k = 0; k < F.prelude.size(); k++) {
+        if (!wanted[k]) continue;
+        const PreludeItem &it = F.prelude[k];
+        o << "[" << k << ":" << (int)it.kind << ":";
+        if (open[k]) o << "open:" << it.table;                 // (left open: its bounds are the scan's own)
+        else if (it.kind == PreludeItem::LIKE_LUT) o << it.heap << ":" << it.pattern;
+        else if (it.scan) {
+            o << "scan:" << it.table << ":" << (it.never ? 1 : 0) << ":" << it.index_col << ":" << it.modulus << ":" << it.bits_of << ":";
+            for (const ScanColumn &sc : it.cols) column_text(o, sc);
+        } else witness_text(o, p->prog, it.witness);
+        o << "]";
+    }
+    return o.str();
+}
+// the leaf bounds of the scan's conditions (VC_FORM), as bound: inside one batch every condition is one function of the row
+static std::string batch_form_key(const MScanCols &cols, const MScanDesc &d) {
+    std::ostringstream o;
+    for (int k = 0; k < cols.ncol; k++) {
+        if (cols.kind[k] != VC_FORM) continue;
+        o << k << ":";
+        for (int f = d.dsrc[k]; f < d.dsrc[k] + d.dtests[k]; f++) o << d.form[f].col << "/" << d.form[f].lo << "/" << d.form[f].hi << ",";
+        o << ";";
+    }
+    return o.str();
+}
 // A grouped batch of K plans keeps 2^K - 1 class tables per replica in LDS: R x (((2^K - 1) x words) | 1) + 256 + nagg + 1 trash words within
 // kGroupLdsWords, R the largest power of two <= 8 that fits.  More slots mean fewer replicas, and the replicas are what keeps the lanes of a
 // wave off each other's words when a few groups hold most rows: a width is taken only while it leaves min(the replicas the scan has
@@ -548,7 +652,7 @@ int batch_group_cap(const MScanDesc &d, int replicas_alone) {
 static jit::Shape batch_shape(const BatchMember &m, const ScanForm &f, int k) {
     jit::Shape sh = jit_shape(m.cols, m.cfg, f, true);
     sh.grouped = m.grouped;
-    sh.der = false;
+    sh.der = m.derived;                                        // (a join batch: vdl_set_batch_joins)
     sh.batch = k;
     return sh;
 }
@@ -560,12 +664,15 @@ void batch_bind(vdl_ctx *c, vdl_plan *p, BatchMember &m) {
     bind_scan(c, p, 0, m.cols, *m.desc, &bpr, p->row_offset);      // (a batched plan has exactly one scan: batch_alone_reason)
     m.cfg = mscan_launch_config(m.cols, *m.desc, m.grouped, c->num_cus);      // (grouped: the key's canonical form and the replicas the scan has alone)
     m.replicas_alone = m.desc->replicas;
+    for (int i = 0; i < m.cols.ncol; i++) m.derived = m.derived || m.cols.kind[i] != VC_DIRECT;
     if (m.cfg.variant < 0) throw Error(VDL_ERR_UNSUPPORTED, "no multi-aggregate scan kernel variant for this shape");
     std::ostringstream k;
     k << m.cols.ncol << ":" << m.cols.n << ":" << m.cols.row0 << ":" << m.cols.image;
     for (int i = 0; i < m.cols.ncol; i++) k << ":" << m.cols.ptr[i] << "/" << m.cols.width[i];
     m.cols_key = k.str();
     m.shape_key = jit::entry_name(jit::MSCAN, mscan_args(m.cols), *m.desc, batch_shape(m, ScanForm{}, 0));
+    m.prelude_key = batch_prelude_key(p);
+    m.form_key = batch_form_key(m.cols, *m.desc);
 }
 
 }  // namespace eng
@@ -646,7 +753,8 @@ static void batch_launch(vdl_ctx *c, BatchEntry &e, const std::vector<BoundForm>
         // step outside it
         const MsArgs &a = bound[(size_t)q].args;
         for (int k = 0; k < a.ncol; k++) {
-            if (!((a.filtered >> k) & 1u) || ((a.packed >> k) & 1u) || a.width(k) >= 4) continue;
+            // (a filtered derived column of a join batch is compared in 64 bits: its bounds stay)
+            if (!((a.filtered >> k) & 1u) || ((a.packed >> k) & 1u) || ((a.derived >> k) & 1u) || a.width(k) >= 4) continue;
             const int64_t top = ((int64_t)1 << (8 * a.width(k) - 1));
             d.flo[k] = std::min(d.flo[k], top);
             d.fhi[k] = std::max(d.fhi[k], -top - 1);
@@ -669,7 +777,7 @@ static void batch_launch(vdl_ctx *c, BatchEntry &e, const std::vector<BoundForm>
 std::string batch_scan(vdl_ctx *c, const std::vector<BatchMember *> &ms, bool tune, bool check_only, int64_t *const *outs, hipEvent_t ev0, hipEvent_t ev1,
                        size_t *code_bytes) {
     const int K = (int)ms.size();
-    const bool grouped = ms[0]->grouped;
+    const bool grouped = ms[0]->grouped, derived = ms[0]->derived;
     if (K < 2 || (grouped ? K > kMaxBatchGrouped || batch_group_replicas(*ms[0]->desc, K) < 1 : K > batch_cap(ms[0]->desc->nagg)))
         throw Error(VDL_ERR_ARG, "a batch of " + std::to_string(K) + " plans does not fit the kernel");
     // (a grouped batch is generated for the replicas its width leaves: part of every slot's descriptor from here on)
@@ -698,9 +806,9 @@ std::string batch_scan(vdl_ctx *c, const std::vector<BatchMember *> &ms, bool tu
         // shape has it; tuned the eager form at 2, 3, 4 and the every-column packed form at 2, 4, by the tuner's rule; the staged, queue
         // and packed-late forms are not batched
         std::vector<std::pair<int, int>> cands = {{0, 0}};
-        // (a grouped batch has the eager tile form alone)
-        if (tune && pin_u > 0) cands = {{pin_u, pin_late == 6 && !grouped ? 6 : 0}};
-        else if (tune && !check_only && grouped) cands = {{2, 0}, {3, 0}, {4, 0}};
+        // (a grouped batch and a join batch have the eager tile form alone)
+        if (tune && pin_u > 0) cands = {{pin_u, pin_late == 6 && !grouped && !derived ? 6 : 0}};
+        else if (tune && !check_only && (grouped || derived)) cands = {{2, 0}, {3, 0}, {4, 0}};
         else if (tune && !check_only) cands = {{2, 0}, {3, 0}, {4, 0}, {2, 6}, {4, 6}};
         TimingEvents ev;
         if (cands.size() > 1) { HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b)); }

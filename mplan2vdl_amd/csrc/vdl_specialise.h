@@ -24,7 +24,8 @@ std::string builds_text(const vdl_plan *p, const std::string &role);
 // ---- batched runs (vdl_run_batch, vdl_batch_jit_check): plans that differ in their literals alone share one pass over the columns ----
 // why a plan cannot share a scan with any other, in the words its batch note carries; "" = it may
 // (grouped_on: vdl_set_batch_grouped -- a plan whose one scan is a grouped scan over table columns may share a grouped batch)
-std::string batch_alone_reason(const vdl_plan *p, bool grouped_on = false);
+// (joins_on: vdl_set_batch_joins -- the one scan may have derived columns and a prelude: a join batch)
+std::string batch_alone_reason(const vdl_plan *p, bool grouped_on = false, bool joins_on = false);
 // a plan's one scan as a batch sees it: its eager binding (made here, the plan's own bound state is not touched) and the two keys that
 // decide which plans go together -- the columns (addresses, widths, images, rows, row offset) and the shape of the generated code
 // under run-time bounds (jit::entry_name: the descriptor's text with the ranges' shapes in place of their values)
@@ -35,10 +36,17 @@ struct BatchMember {
     std::shared_ptr<MScanDesc> desc;
     ScanLaunch cfg;
     bool grouped = false;                       // the scan is the plan's one grouped scan
+    bool derived = false;                       // the scan has derived columns: a join batch (vdl_set_batch_joins)
     int replicas_alone = 1;                     // ... and has that many table replicas when the plan runs alone
     std::string cols_key, shape_key;
+    // join batches: the canonical text of the prelude items the scan refers to (equal text: equal lookup tables, built once per batch)
+    // and the leaf bounds of its conditions (a condition is computed once per row, from slot 0's descriptor)
+    std::string prelude_key, form_key;
 };
 void batch_bind(vdl_ctx *c, vdl_plan *p, BatchMember &m);
+// join batches: [k] = prelude item k is left open for the batch -- every row selected, nothing scanned -- because the plan's own scan
+// applies its filters with the same bounds (vdl_specialise.cpp says when)
+std::vector<char> batch_open_items(const vdl_plan *p);
 // the widest batch for scans of this many aggregates: kMaxBatch, or what kMaxBatchWords accumulators per lane allow
 int batch_cap(int nagg);
 // ... and under VDL_BATCH_WIDTH=k, which caps the width of any batch

@@ -55,6 +55,8 @@
 // whole run too -- their sums through the per-operator folds, exact where delivered and checked where another statement reads them.
 // --batch-grouped: programs whose one scan is a GROUP BY over table columns share a grouped batch too (vdl_set_batch_grouped); without it
 // they run alone, as "grouped scans are not batched".
+// --batch-joins: programs whose one scan has derived columns or a prelude (join scans) share a batch too (vdl_set_batch_joins); without
+// it they run alone, as "scans with derived columns are not batched" / "scans with lookup tables or semi-join sets are not batched".
 #include <signal.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -231,7 +233,7 @@ bool read_reply(const std::string &path, Reply &r) {
 struct Options {
     int64_t rows = 60175;           // SF0.01 lineitem, /root/reference/tests/tpchnoorder/bounds.csv:59
     uint64_t seed = 0x5EED0006ULL;
-    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0, batch_sharded = 0, lookup_images = 0;
+    int device = 0, fuse = 1, profile = 0, describe = 0, gpus = 1, jit = 0, jit_share = 0, encode = 0, encode_steps = 0, order_sharded = 0, batch_grouped = 0, batch_joins = 0, batch_sharded = 0, lookup_images = 0;
     int wide = -1;                  // --wide-sums 1 / --checked-sums 2; -1: as the plan was parsed (VDL_WIDE_SUMS)
     int wide_sharded = 0;           // --wide-sharded: vdl_plan_set_wide_sums_sharded
     int wide_tail = 0;              // --wide-tail: vdl_plan_set_wide_sums_tail (only together with --wide-sums | --checked-sums)
@@ -292,6 +294,7 @@ int run_rank(const Options &o, const std::string &text, int rank, int world, con
     int rc = vdl_open(&ctx, o.describe ? -1 : (world > 1 || !comm_dir.empty() ? rank : o.device));
     if (rc) return die(ctx, "vdl_open", rc);
     if (o.batch_grouped) vdl_set_batch_grouped(ctx, 1);
+    if (o.batch_joins) vdl_set_batch_joins(ctx, 1);
     if (o.lookup_images) vdl_set_lookup_images(ctx, 1);
     std::vector<vdl_plan *> plans;
     std::string loads = text;                                  // every program's text: what --data looks for Loads in
@@ -411,6 +414,7 @@ int main(int argc, char **argv) {
         else if (a == "--shard" && i + 1 < argc) o.shard = argv[++i];
         else if (a == "--batch" && i + 1 < argc) o.batch_files.push_back(argv[++i]);
         else if (a == "--batch-grouped") o.batch_grouped = 1;
+        else if (a == "--batch-joins") o.batch_joins = 1;
         else if (a == "--batch-sharded") o.batch_sharded = 1;
         else if (a == "--lookup-images") o.lookup_images = 1;
         else if (a == "--wide-sums") o.wide = 1;
@@ -430,7 +434,7 @@ int main(int argc, char **argv) {
         else if (a == "--profile") o.profile = 1;
         else if (a == "--describe") o.describe = 1;
         else {
-            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--batch-sharded] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--lookup-images] [--wide-sums | --checked-sums] [--wide-sharded] [--profile] [--describe] < program.vdl\n");
+            std::fprintf(stderr, "usage: vdlrun [--rows N | --data DIR] [--gpus N [--shard TABLE]] [--order-by FIELD[:asc|:desc][:text[=HEAP]],... ] [--limit N] [--order-sharded] [--batch FILE ...] [--batch-grouped] [--batch-joins] [--batch-sharded] [--seed S] [--device D] [--no-fuse] [--jit | --jit-tune] [--jit-share] [--encode] [--encode-steps] [--lookup-images] [--wide-sums | --checked-sums] [--wide-sharded] [--profile] [--describe] < program.vdl\n");
             return 2;
         }
     }

@@ -20,6 +20,15 @@ class VdlError(RuntimeError):
         self.code = code
 
 
+def prelude_counters():
+    """Prelude tables built in this process so far (vdl.h: vdl_prelude_counters): {"items": LIKE tables, dimension bitmaps and semi-join
+    sets, one count per table and run}."""
+    L = _lib.load()
+    a = ctypes.c_int64()
+    L.vdl_prelude_counters(ctypes.byref(a))
+    return {"items": a.value}
+
+
 def jit_counters():
     """Builds of specialised scan code in this process so far (vdl.h: vdl_jit_counters): {"compiled": by hiprtc, "from_disk": read
     from $VDL_JIT_CACHE, "from_memory": built earlier in this process}."""
@@ -784,6 +793,12 @@ class Engine:
         """True: run_batch also batches plans whose one scan is a GROUP BY over table columns (vdl.h: vdl_set_batch_grouped; off by
         default, VDL_BATCH_GROUPED=1 switches it on when the context opens)."""
         self._check(self._L.vdl_set_batch_grouped(self._c, 1 if on else 0))
+
+    def set_batch_joins(self, on):
+        """True: run_batch also batches plans whose one scan has derived columns and a prelude -- join scans such as TPC-H Q14, Q12, Q19
+        and Q4 -- when they build the same lookup tables and hold the same literals in their conditions (vdl.h: vdl_set_batch_joins; off
+        by default, VDL_BATCH_JOINS=1 switches it on when the context opens)."""
+        self._check(self._L.vdl_set_batch_joins(self._c, 1 if on else 0))
 
     def batch_jit_check(self, plans):
         """Group the plans and build the batch kernels against the registered columns without a device (vdl_batch_jit_check); the notes."""

@@ -21,6 +21,16 @@ replicas by the LDS rule (K = 4: R = 2, K = 3: R = 4, K = 2: R = 8).  Leg (a) is
 eight; per-query figures divide by eight.  The batch kernels' time is the sum over the call's batches, the bytes n x the sum of the
 image widths per batch.  No CPU check: every answer of (b) must equal (a)'s, and (a)'s kernels are checked by the suite.
 
+    python tools/batch_bench.py --query q14 [--k 2,4,8] ...
+
+Join batches (Engine.set_batch_joins) on TPC-H Q14: 600 M lineitems and 20 M parts as tools/lookup_bench.py sets them up
+(datagen.register_q14_columns, part.p_type encoded), K month windows (the month shifted by 30 days per set).  Leg (a) is K tuned
+run()s -- K LIKE tables over the p_type heap, K scans, up to K times the p_type lookups --, leg (b) run_batch of the K plans: the
+prelude once, the fact columns once, a row looked up once if any month wants it.  Beside the walls: the scan kernels' own time of
+both legs (timeInMicrosecondsForFusedScan summed over the K runs, timeInMicrosecondsForBatchedScan) and, per leg, wall minus
+kernels -- the prelude (k_like), the launches and the finalisation, which the engine does not time apart.  --legs a runs on a tree
+without the switch.  No CPU check: every answer of (b) must equal (a)'s, and (a)'s kernels are checked by the suite.
+
     python tools/batch_bench.py --sharded [--rows N] [--k 2,4,8] [--repeats 3] [--steps 30] [--parent TREE] [--out FILE]
 
 Sharded batches (Engine.run_batch_sharded) on Q6 over one rank's shard (default 75 004 738 rows, an eighth of SF100) with a ONE-RANK
@@ -60,6 +70,8 @@ query = opt("--query", "q6")
 COLUMNS = datagen.Q1_COLUMNS if query == "q1" else datagen.Q6_COLUMNS
 if query == "q1" and "--k" not in args:
     widths = [2, 3, 4]
+if query == "q14" and "--k" not in args:
+    widths = [2, 4, 8]
 out_path = opt("--out", None)
 lines = []
 
@@ -77,6 +89,8 @@ def literal_set(k):
 def q6_text(k):
     text = open(os.path.join(ROOT, "tests", "golden", query + ".vdl")).read()
     mp, seen = ({729999: 729999 - 30 * k} if k else {}) if query == "q1" else literal_set(k), set()      # (Q1: the cutoff, 30 days earlier per set)
+    if query == "q14":
+        mp = {728902: 728902 + 30 * k, 728932: 728932 + 30 * k} if k else {}                               # (Q14: the month window)
 
     def sub(mo):
         c = int(mo.group(2))
@@ -220,7 +234,7 @@ def sharded_main():
 
 
 def answer(results):
-    return str(sorted(results.items())) if query == "q1" else next(iter(next(iter(results.values())).values()))
+    return str(sorted(results.items())) if query in ("q1", "q14") else next(iter(next(iter(results.values())).values()))
 
 
 if "--sharded-child" in args:
@@ -236,8 +250,14 @@ if "--sharded" in args:
 torch.cuda.set_device(0)
 e = m.Engine(0)
 e.use_torch_stream()
-for name in COLUMNS:
-    e.generate(datagen.LINEITEM[name], 0, rows)
+if query == "q14":
+    e.set_lookup_images(True)                                             # (p_type is looked up through its 2-byte image, as lookup_bench's leg "on")
+    keep = datagen.register_q14_columns(e, rows, lookup_images=True)      # (600 M lineitems: 20 M parts)
+    if "b" in legs:
+        e.set_batch_joins(True)
+else:
+    for name in COLUMNS:
+        e.generate(datagen.LINEITEM[name], 0, rows)
 if query == "q1" and "b" in legs:
     e.set_batch_grouped(True)
 say("%s, %d rows of generated lineitem with images, %d alternating repeats, legs %s" % (query.upper(), rows, repeats, legs))
@@ -249,7 +269,7 @@ t0 = time.perf_counter()
 answers = [answer(p.run()["results"]) for p in plans]
 say("first runs of the %d plans (tuning, compiles): %.1f s" % (kmax, time.perf_counter() - t0))
 say("leg (a) kernel of plan 0: %s" % re.findall(r"-> ([^;]*);", plans[0].jit_note())[-1:])
-assert len({str(a) for a in answers}) == kmax, answers
+assert query == "q14" or len({str(a) for a in answers}) == kmax, answers      # (Q14's answer is a percentage: months may agree)
 
 
 def leg_a(k):
@@ -292,7 +312,28 @@ for k in widths:
     spread = max(max(ta) - min(ta), max(tb) - min(tb))
     say("  (a) / (b) = %.2f; medians differ by %.3f ms, the widest spread of repeats is %.3f ms" %
         (float(np.median(ta)) / float(np.median(tb)), float(np.median(ta)) - float(np.median(tb)), spread))
-    if k > 1:
+    if k > 1 and query == "q14":
+        # the kernels' own time of both legs; what is left of the wall is the prelude (k_like over the heap), the launches, the finalisation
+        for p in plans[:k]:
+            p.set_profiling(True)
+        ka, kb, wa, wb, pb = [], [], [], [], []
+        for _ in range(repeats):
+            ms, rs = once(lambda: [p.run() for p in plans[:k]])
+            wa.append(ms)
+            ka.append(sum(v for r in rs for key, v in r["timings"].items() if "FusedScan" in key) / 1e3)
+            ms, rs = once(lambda: e.run_batch(plans[:k]))
+            wb.append(ms)
+            kb.append(next(v for key, v in rs[0]["timings"].items() if "BatchedScan" in key) / 1e3)
+            pb.append(sum(v for r in rs for key, v in r["timings"].items() if "BatchedPrelude" in key) / 1e3)
+        for p in plans[:k]:
+            p.set_profiling(False)
+        say("  batch kernel: %s" % plans[0].batch_note().split(", ", 1)[1])
+        say("  under profiling (a): %d scan kernels %s; wall - kernels: median %.3f ms per call, %.3f per query" %
+            (k, stats(ka), float(np.median(np.array(wa) - np.array(ka))), float(np.median(np.array(wa) - np.array(ka))) / k))
+        say("  under profiling (b): batch kernel    %s; wall - kernel:  median %.3f ms per call" % (stats(kb), float(np.median(np.array(wb) - np.array(kb)))))
+        say("  (b) prelude, once per call (k_like over the p_type heap; timeInMicrosecondsForBatchedPrelude): %s" % stats(pb))
+        say("  (a run() alone launches the same k_like over the same heap once per plan: %d times per call of leg (a), not timed apart)" % k)
+    elif k > 1:
         note = plans[0].batch_note()
         name = note.split(", ", 1)[1]
         packed = ",packed," in name
@@ -316,7 +357,7 @@ for k in widths:
         say("  batch kernel time: median %d us (min %d, max %d); it reads %d bytes: %.2f TB/s = %.3f of the 8 TB/s peak; per query %.1f us" %
             (int(np.median(us)), min(us), max(us), nbytes, nbytes / kern / 1e12, nbytes / kern / PEAK, np.median(us) / k))
 
-if "--no-verify" not in args and query != "q1":
+if "--no-verify" not in args and query not in ("q1", "q14"):
     t0 = time.perf_counter()
     cols = {c: e.download(c) for c in datagen.Q6_COLUMNS}
     ok = all(cpu_q6(cols, k) == answers[k] for k in range(kmax))
